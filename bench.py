@@ -20,6 +20,11 @@ prints ONE JSON line.  Workloads = BASELINE.json configs:
 per launch / the launch's average duration measured with HIP events on the engine's own stream.
 `cpu_baseline` = the CPU oracle (oracle/, reference operation order, OpenMP over all host cores) timed on a bounded
 sample of the same workload on rank 0 at N=1 -- a reported baseline, not the thing measured.
+
+A plain run sets up, runs W warm-up steps, times exactly K steps on one buffer placement, writes its outputs when
+--dump-outputs DIR is given, and prints the line.  Everything else -- the median over 5 placements, the other device-image
+layout, cpu_baseline, the live HBM traffic and device-copy yardstick, the `f4` JPEG summary, the JPEG host-API and staging
+figures, the camera-shard parity check -- runs only with --full.
 """
 from __future__ import annotations
 
@@ -86,7 +91,8 @@ def parse_args():
     ap.add_argument("--unique-sets", type=int, default=2, help="distinct synthetic frame sets replicated over the batch")
     ap.add_argument("--placements", type=int, default=0,
                     help="buffer placements: the frame / output buffers are freed and re-allocated this many times and K steps are timed "
-                         "on each; the MEDIAN placement is reported (0 = 5 for the single-engine workloads, 1 for the camera-shard one)")
+                         "on each; the MEDIAN placement is reported (0 = 1 in a plain run; with --full 5 for the single-engine workloads, "
+                         "1 for the camera-shard one)")
     ap.add_argument("--output-pitch", default="aligned", type=lambda v: v if v in ("aligned", "dense") else int(v),
                     help="row pitch of the device-resident BEV images (bevw_set_output_pitch): aligned = rows of whole 64-byte sectors "
                          "(1080 -> 1088 pixels, cv::cuda::GpuMat style; what BevGenerator's default output_pitch='auto' selects on the tile "
@@ -99,6 +105,12 @@ def parse_args():
     ap.add_argument("--no-live-traffic", action="store_true", help="skip the two rocprofv3 --pmc child runs behind roofline.traffic (falls back to profiles/hbm_traffic.json)")
     ap.add_argument("--no-f4", action="store_true", help="skip the JPEG summary (`f4`) the default single-GPU run appends to its line")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: 5 placements, the other layout, cpu_baseline, live traffic, "
+                         "device-copy yardstick, f4 summary, JPEG host-API / staging figures, camera-shard parity (the --no-* switches apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all: "
+                         "whole images / files and a seeded sample of the rest of the batch)")
     return ap.parse_args()
 
 
@@ -225,6 +237,38 @@ def upload_replicated(buf, unique: np.ndarray, batch: int):
     per = unique[0].nbytes
     for b in range(batch):
         buf.upload(unique[b % unique.shape[0]], offset=b * per)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20240917
+
+
+def image_outputs(name: str, buf, n: int, h: int, w: int, image_bytes: int, row_bytes: int, whole: int = 2, rows: int = 512) -> dict:
+    """The dense uint8 [n, h, w, 3] images a caller of the timed path receives, read from the device buffer the last step wrote (rows
+    `row_bytes` apart, images `image_bytes` apart; padding columns dropped), as float32: the first `whole` images entire, and `rows`
+    rows drawn over the whole batch with a fixed seed (`<name>_rows_index` = their (image, row))."""
+    k = min(whole, n)
+    imgs = [buf.download((h, row_bytes), offset=i * image_bytes)[:, :w * 3].reshape(h, w, 3) for i in range(k)]
+    idx = np.random.default_rng(DUMP_SEED).integers(0, [n, h], size=(rows, 2))
+    idx = idx[np.lexsort((idx[:, 1], idx[:, 0]))]
+    sel = [buf.download((w * 3,), offset=int(i) * image_bytes + int(r) * row_bytes) for i, r in idx]
+    return {name + "_images": np.stack(imgs).astype(np.float32), name + "_rows": np.stack(sel).reshape(rows, w, 3).astype(np.float32),
+            name + "_rows_index": idx.astype(np.float64)}
+
+
+def file_outputs(name: str, files, whole: int = 4) -> dict:
+    """Encoded files: the bytes of the first `whole` files (concatenated, float32) and the length of every file (float64)."""
+    return {name + "_bytes": np.frombuffer(b"".join(bytes(f) for f in files[:whole]), np.uint8).astype(np.float32),
+            name + "_lengths": np.array([len(f) for f in files], np.float64)}
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (k, v.dtype)
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 class TimedOracle:
@@ -401,7 +445,7 @@ def jpeg_valu_profile(workload: str):
         return None
 
 
-def jpeg_measure(a, d, w, dev, workload, steps, warmup, cpu_seconds, host_api=True):
+def jpeg_measure(a, d, w, dev, workload, steps, warmup, cpu_seconds, host_api=True, full=True, dump_dir=None):
     """Row f4 workloads.  One step = one batch through the JPEG kernels with the inputs resident in HBM: decode = the files' entropy-coded bytes
     AS THEY ARE IN THE FILES -> frame sets (un-stuffing, entropy decoding, inverse DCT, colour: everything a decode needs is inside the timed
     region); encode = device images -> complete files in HBM; pipeline = decode + stitch + encode chained by events on their streams."""
@@ -436,11 +480,12 @@ def jpeg_measure(a, d, w, dev, workload, steps, warmup, cpu_seconds, host_api=Tr
     if mode in ("decode", "pipeline"):
         codec.decode_stage(files)
         codec.sync()
-        t0 = time.perf_counter()
-        for _ in range(3):   # the host side of a batch: header parsing + copy into pinned memory + H2D of the compressed bytes
-            codec.decode_stage(files)
-            codec.sync()
-        stage_ms = (time.perf_counter() - t0) / 3 * 1e3
+        if full:
+            t0 = time.perf_counter()
+            for _ in range(3):   # the host side of a batch: header parsing + copy into pinned memory + H2D of the compressed bytes
+                codec.decode_stage(files)
+                codec.sync()
+            stage_ms = (time.perf_counter() - t0) / 3 * 1e3
     if mode == "decode":
         units = batch * 4
         step = lambda: codec.decode_run_device(d_frames.ptr, fh * fw * 3, fw * 3)
@@ -484,7 +529,10 @@ def jpeg_measure(a, d, w, dev, workload, steps, warmup, cpu_seconds, host_api=Tr
     ev_ms = d.max(codec.timer_between(0, steps))
     info = codec.decode_info() if mode != "encode" else {}
     sizes = codec.files() if mode != "decode" else []
-    if mode == "pipeline" and host_api and not os.environ.get("BEVW_BENCH_NO_HOST_API"):   # (profiling passes count the kernels of the resident steps only)
+    if dump_dir and d.rank == 0:   # decode: the frame sets; encode / pipeline: the .jpg files
+        write_outputs(dump_dir, image_outputs("frames", d_frames, batch * 4, fh, fw, fh * fw * 3, fw * 3) if mode == "decode"
+                      else file_outputs("jpeg_files", sizes))
+    if mode == "pipeline" and host_api and full and not os.environ.get("BEVW_BENCH_NO_HOST_API"):   # (profiling passes count the kernels of the resident steps only)
         # the host API on the same data, nothing resident: host byte strings in, host byte strings out (PCIe and host staging included; never
         # `value`).  jpeg_stream = consecutive batches pipelined (a host thread stages batch i + 1 and this thread fetches batch i - 1 while the
         # GPU runs batch i); jpeg = one synchronous call per batch
@@ -544,7 +592,7 @@ def jpeg_measure(a, d, w, dev, workload, steps, warmup, cpu_seconds, host_api=Tr
            "ranks": d.world, "steps": steps, "warmup": warmup, "ms_per_step": wall / steps * 1e3, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
            "config": dict({"workload": workload, "batch_per_gpu": batch, "units_per_step": units, "device": _ffi.device_name(dev),
-                           "sharding": "files across ranks, no data-path collective"}, **extra),
+                           "sharding": "files across ranks, no data-path collective", "full": bool(full)}, **extra),
            "roofline": roof, "cpu_baseline": cpu}
     codec.close()
     d_frames.free()
@@ -553,7 +601,8 @@ def jpeg_measure(a, d, w, dev, workload, steps, warmup, cpu_seconds, host_api=Tr
 
 
 def main_jpeg(a, d, w, dev):
-    out = jpeg_measure(a, d, w, dev, a.workload, a.steps, a.warmup, 0.0 if a.no_cpu_baseline else min(a.cpu_seconds, 8.0))
+    out = jpeg_measure(a, d, w, dev, a.workload, a.steps, a.warmup, 0.0 if (a.no_cpu_baseline or not a.full) else min(a.cpu_seconds, 8.0),
+                       full=a.full, dump_dir=a.dump_outputs)
     if d.rank == 0:
         print(json.dumps(out), flush=True)
     d.close()
@@ -568,7 +617,7 @@ def f4_summary(a, d, dev):
 
     res = {}
     for name, cpu_s in (("jpeg_decode_b64", 2.5), ("jpeg_encode_b64", 2.0), ("jpeg_bev_jpeg_b64", 0.0)):
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", "12", "--warmup", "4", "--cpu-seconds", str(cpu_s)]
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", name, "--steps", "12", "--warmup", "4", "--cpu-seconds", str(cpu_s), "--full"]
         if cpu_s <= 0:
             cmd.append("--no-cpu-baseline")
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
@@ -587,7 +636,7 @@ def f4_summary(a, d, dev):
                 keep[k] = o["config"][k]
         res[name] = keep
     res["note"] = ("reference wire format: cv2.imread x 4 (main.py:74-77), cv2.imwrite (surroundBEV.py:340); inputs resident = compressed bytes / device images; "
-                   "each leg = `bench.py --workload <name> --steps 12 --warmup 4` in its own process")
+                   "each leg = `bench.py --workload <name> --steps 12 --warmup 4 --full` in its own process")
     return res
 
 
@@ -630,7 +679,16 @@ def main():
         d_in = _ffi.DeviceBuffer(batch * mine[0].nbytes, dev)
         upload_replicated(d_in, mine, batch)
         pipe = CS.ResidentShardPipeline(gen, batch)
-        make_buffers = lambda: ((), (lambda: pipe.step(d_in.ptr, None)))   # the pipeline owns its buffers: one placement
+        last_root = [None]
+
+        def shard_step():
+            last_root[0] = pipe.step(d_in.ptr, None)
+
+        def fetch():   # the stitch rank of group 0's last step holds the BEV batch, dense uint8 [B, BH, BW, 3]
+            if last_root[0] != d.rank or gen.group != 0:
+                return None
+            return image_outputs("bev", pipe.out, batch, bh, bw, bh * bw * 3, bw * 3)
+        make_buffers = lambda: ((), shard_step, fetch)   # the pipeline owns its buffers: one placement
         e = gen.engine
         sync = e.sync
         tstart = lambda: _ffi.check(_ffi.lib().bevw_timer_start(e.h))
@@ -649,7 +707,7 @@ def main():
             return float(ms.value)
         units_world = max(1, d.world // 4)
         parity = None
-        if d.world > 1:
+        if d.world > 1 and a.full:
             # Before anything is timed on more than one GPU: the same ranks, the same native RCCL exchange, two seeded frame sets through the
             # host-array call, and every group's stitch rank compares with BevGenerator on its own GPU -- bit-exact or the run stops.  (The rank > 0
             # branches of bevw_shard_gather_parts / bevw_shard_allgather_vsums can only execute on a multi-GPU box: tests/test_camera_shard.py::
@@ -669,7 +727,7 @@ def main():
                  "table_build_s": round(t_build, 3), "cameras_per_rank": len(gen.cams), "camera_groups": units_world,
                  "part_boxes": [list(b) for b in gen.boxes],
                  "transport": "single rank" if d.world == 1 else "rccl (native: ncclAllGather + grouped ncclSend/ncclRecv on the engine stream)"}
-        if d.rank == 0 and d.world == 1 and not a.no_cpu_baseline:
+        if d.rank == 0 and d.world == 1 and a.full and not a.no_cpu_baseline:
             cpu = cpu_baseline_bev(w, cfg, rig, unique, a.cpu_seconds)
     elif w["kind"] == "bev":
         cfg = {"S": W.CONFIG_S, "4K": W.CONFIG_4K}[w["cfg"]]
@@ -695,11 +753,12 @@ def main():
                 b_in = _ffi.DeviceBuffer(batch * unique[0].nbytes, dev)
                 b_out = _ffi.DeviceBuffer(batch * bh * g.out_pitch * 3, dev)
                 upload_replicated(b_in, unique, batch)
-                return (b_in, b_out), (lambda: g.run_device(b_in.ptr, batch, None, b_out.ptr, out_bytes=batch * g.out_image_bytes))
+                fetch = lambda: image_outputs("bev", b_out, batch, bh, bw, bh * g.out_pitch * 3, g.out_pitch * 3)
+                return (b_in, b_out), (lambda: g.run_device(b_in.ptr, batch, None, b_out.ptr, out_bytes=batch * g.out_image_bytes)), fetch
             return make_buffers, g.sync, g.timer_start, g.timer_stop, g.timer_mark, g.timer_between
         bev, t_build = engine(layouts[0])
         make_buffers, sync, tstart, tstop, tmark, tbetween = harness(bev)
-        if len(layouts) > 1 and not a.single_layout:
+        if len(layouts) > 1 and a.full and not a.single_layout:
             other_layout = (layouts[1], lambda: harness(engine(layouts[1])[0]))
         info = bev.plan_info()
         extra = {"frame": [fw, fh], "bev": [bw, bh], "blend": w["blend"], "balance": w["balance"],
@@ -708,7 +767,7 @@ def main():
                  "output_layout": ("device images [B][%d][%d][3] u8: rows padded to whole 64-byte sectors (bevw_set_output_pitch; host entry "
                                    "points return dense arrays, rows compacted inside the D2H copy)" % (bh, bev.out_pitch)) if bev.out_pitch != bw
                  else "device images [B][%d][%d][3] u8, dense (the reference's host layout)" % (bh, bw)}
-        if d.rank == 0 and d.world == 1 and not a.no_cpu_baseline:
+        if d.rank == 0 and d.world == 1 and a.full and not a.no_cpu_baseline:
             cpu = cpu_baseline_bev(w, cfg, rig, unique, a.cpu_seconds)
     else:
         import ctypes as C
@@ -726,7 +785,8 @@ def main():
             b_in = _ffi.DeviceBuffer(batch * imgs[0].nbytes, dev)
             b_out = _ffi.DeviceBuffer(batch * imgs[0].nbytes, dev)
             upload_replicated(b_in, imgs, batch)
-            return (b_in, b_out), (lambda: _ffi.check(L.bevw_remap_device(r, b_in.ptr, batch, b_out.ptr)))
+            fetch = lambda: image_outputs("undistorted", b_out, batch, fh, fw, imgs[0].nbytes, fw * 3)
+            return (b_in, b_out), (lambda: _ffi.check(L.bevw_remap_device(r, b_in.ptr, batch, b_out.ptr))), fetch
         sync = lambda: _ffi.check(L.bevw_remapper_sync(r))
         tstart = lambda: _ffi.check(L.bevw_remapper_timer_start(r))
 
@@ -742,7 +802,7 @@ def main():
             return float(ms.value)
         # (the remapper compiles its maps into a 1-camera unit plan; k_remap_lut, one thread per pixel, only when that plan is unusable)
         extra = {"frame": [fw, fh], "schedule": "tile_plan (1-camera plan of the undistort maps)"}
-        if d.rank == 0 and d.world == 1 and not a.no_cpu_baseline:
+        if d.rank == 0 and d.world == 1 and a.full and not a.no_cpu_baseline:
             cpu = cpu_baseline_undistort(w, K, D, ucfg, unique, a.cpu_seconds)
 
     # Placements.  The step time of these request-bound kernels follows the DRAM latency the physical pages of the OUTPUT buffer
@@ -750,12 +810,13 @@ def main():
     # an allocation do not matter, the channels are evenly loaded in fast and slow draws).  One allocation is one random draw, so the
     # buffers are freed and re-allocated `placements` times (a growing dummy allocation shifts the heap in between), W warm-up and
     # exactly K timed steps run on each, and the MEDIAN placement is what the line reports; all draws are listed next to it.
-    placements = a.placements or (1 if w["kind"] == "camera" else 5)
+    # A plain run times its K steps on one placement; --full keeps the median of 5.
+    placements = a.placements or (1 if (w["kind"] == "camera" or not a.full) else 5)
 
-    def measure(make_buffers, sync, tstart, tstop, tmark, tbetween):
+    def measure(make_buffers, sync, tstart, tstop, tmark, tbetween, dump_dir=None):
         draws, dummies = [], []
         for pi in range(placements):
-            bufs, step = make_buffers()
+            bufs, step, fetch = make_buffers()
             for _ in range(a.warmup):
                 step()
             sync()
@@ -775,6 +836,10 @@ def main():
             laps = sorted(tbetween(i, i + 1) for i in range(a.steps))
             lap_median = d.max(laps[len(laps) // 2] if len(laps) % 2 else 0.5 * (laps[len(laps) // 2 - 1] + laps[len(laps) // 2]))
             draws.append({"wall": wall, "ev_ms": ev_ms, "lap_median": lap_median, "lap_min": laps[0], "lap_max": laps[-1]})
+            if dump_dir and pi + 1 == placements:   # what the last timed step wrote, before its buffers go
+                arrays = fetch() if (w["kind"] == "camera" or d.rank == 0) else None
+                if arrays is not None:
+                    write_outputs(dump_dir, arrays)
             for b in bufs:
                 b.free()
             if pi + 1 < placements and bufs:
@@ -785,7 +850,7 @@ def main():
         mid = draws[order[placements // 2]] if placements % 2 else draws[order[placements // 2 - 1]]   # the (lower) median placement
         return mid, draws
 
-    mid, draws = measure(make_buffers, sync, tstart, tstop, tmark, tbetween)
+    mid, draws = measure(make_buffers, sync, tstart, tstop, tmark, tbetween, dump_dir=a.dump_outputs)
     wall, ev_ms, lap_median = mid["wall"], mid["ev_ms"], mid["lap_median"]
     laps = [mid["lap_min"], mid["lap_max"]]
     other = None
@@ -800,12 +865,12 @@ def main():
     # between two fresh 1 GiB buffers on THIS box, default-policy and streaming accesses, the better of the two
     copy_gbs = None
     under_profiler = "rocprofiler" in os.environ.get("LD_PRELOAD", "") or bool(os.environ.get("ROCP_TOOL_LIBRARIES"))   # (keep profiles of the step clean)
-    if d.rank == 0 and d.world == 1 and not os.environ.get("BEVW_BENCH_CHILD") and not under_profiler and not a.no_live_traffic:
+    if d.rank == 0 and d.world == 1 and a.full and not os.environ.get("BEVW_BENCH_CHILD") and not under_profiler and not a.no_live_traffic:
         try:
             copy_gbs = max(_ffi.device_copy_rate(1 << 30, 10, st, dev) for st in (False, True) for _ in range(3))   # (fresh buffers per trial: placements differ)
         except Exception:
             copy_gbs = None
-    lt = live_traffic(a, batch) if (d.rank == 0 and d.world == 1 and w["kind"] != "camera") else None
+    lt = live_traffic(a, batch) if (d.rank == 0 and d.world == 1 and w["kind"] != "camera" and a.full) else None
     traffic, traffic_fetch, traffic_write, traffic_source = lt if lt else static_traffic(a.workload, batch)
     agg = aggregate(units_world, batch, a.steps, wall, ev_ms, alg_bytes)
     value, launch_ms, achieved = agg["value"], agg["launch_ms"], agg["achieved_gbs"]
@@ -819,7 +884,7 @@ def main():
         "config": dict({"workload": a.workload, "batch_per_gpu": batch, "global_batch": batch * units_world,
                         "sharding": ("cameras across ranks, one send/recv of mask boxes per step" if w["kind"] == "camera"
                                      else "frames across ranks, no data-path collective"), "device": _ffi.device_name(dev),
-                        "unique_frame_sets": int(a.unique_sets)}, **extra),
+                        "unique_frame_sets": int(a.unique_sets), "full": bool(a.full)}, **extra),
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "frac_best_placement": alg_bytes * batch * a.steps / (min(x["ev_ms"] for x in draws) * 1e-3) / 1e9 / HBM_PEAK_GBS,
                      "frac_worst_placement": alg_bytes * batch * a.steps / (max(x["ev_ms"] for x in draws) * 1e-3) / 1e9 / HBM_PEAK_GBS,
@@ -835,7 +900,8 @@ def main():
                      # the same step priced at 64-byte sector granularity (workloads.SECTOR_GRANULAR_BYTES): what a minifying map must move at least
                      "sector_floor_bytes_per_unit": W.SECTOR_GRANULAR_BYTES.get(a.workload),
                      "frac_sector_floor": (W.SECTOR_GRANULAR_BYTES[a.workload] * batch / (launch_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if a.workload in W.SECTOR_GRANULAR_BYTES else None},
-        "placements": {"n": placements, "reported": "median placement (by wall time of its K steps)",
+        "placements": {"n": placements, "reported": "median placement (by wall time of its K steps)" if placements > 1
+                       else "the one placement" + ("" if (a.full or a.placements) else " (a plain run; --full reports the median of 5)"),
                        "ms_per_step": [round(x["wall"] / a.steps * 1e3, 4) for x in draws],
                        "kernel_ms_median": [round(x["lap_median"], 4) for x in draws]},
         "other_output_layout": other,
@@ -850,8 +916,8 @@ def main():
     elif other is not None and other["output_layout"] == "dense":
         out["value_dense"], out["frac_dense"], out["ms_per_step_dense"] = other["value"], other["frac"], other["ms_per_step"]
     else:
-        out["value_dense"] = out["frac_dense"] = out["ms_per_step_dense"] = None   # (--single-layout: not measured in this run)
-    if a.workload == "direct_stitch_b256" and d.world == 1 and not a.no_f4 and not a.single_layout:
+        out["value_dense"] = out["frac_dense"] = out["ms_per_step_dense"] = None   # (the other layout is measured only with --full, and not with --single-layout)
+    if a.workload == "direct_stitch_b256" and d.world == 1 and a.full and not a.no_f4 and not a.single_layout:
         try:
             out["f4"] = f4_summary(a, d, dev)
         except Exception as e:   # the headline must not depend on the JPEG legs

@@ -52,5 +52,24 @@ def repo_camera_jpegs() -> dict:
     return {n: z[f"{n}_img"].tobytes() for n in ("front", "back", "left", "right")}
 
 
+def reference_tree_jpegs() -> dict:
+    """Every .jpg file of the reference tree, {path in the tree: raw bytes}, as tests/golden/reference_jpegs.json lists them (written
+    by tests/golden/make_fixtures.py): six are inside repo_rig.npz, the other ten under tests/golden/reference_jpegs/."""
+    import json
+
+    golden = os.path.join(ROOT, "tests", "golden")
+    with open(os.path.join(golden, "reference_jpegs.json")) as f:
+        rec = json.load(f)
+    z = np.load(os.path.join(golden, "repo_rig.npz"))
+    out = {}
+    for p, r in rec.items():
+        if r["stored"].startswith("repo_rig.npz:"):
+            out[p] = z[r["stored"].split(":", 1)[1]].tobytes()
+        else:
+            with open(os.path.join(golden, r["stored"]), "rb") as f:
+                out[p] = f.read()
+    return out
+
+
 SUBSAMPLINGS = ((2, 0x22), (1, 0x21), (0, 0x11))   # Pillow's code, the SOF sampling byte of the luma component
 SIZES = ((8, 8), (16, 16), (1, 1), (3, 5), (17, 33), (40, 56), (100, 75), (64, 2), (2, 64), (5, 4), (4, 5), (33, 48))

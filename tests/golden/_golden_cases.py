@@ -20,6 +20,38 @@ def digest(arr: np.ndarray) -> str:
     return hashlib.sha256(str(a.dtype).encode() + str(a.shape).encode() + a.tobytes()).hexdigest()
 
 
+def value_digest(arr) -> str:
+    """Digest of shape and values, not of dtype: two arrays get the same one exactly when np.array_equal holds (no NaNs)."""
+    a = np.asarray(arr)
+    return hashlib.sha256(str(a.shape).encode() + (np.ascontiguousarray(a, np.float64) + 0.0).tobytes()).hexdigest()
+
+
+# tests/test_reference_structure.py and its generator (make_reference_structure_goldens.py): the (blend, balance, (CAR_WIDTH,
+# CAR_HEIGHT)) cases of test_reference_control_flow_equals_the_restatement and the board squares of ScaleImage
+REFERENCE_FLOWS = [(False, False, (250, 400)), (True, True, (200, 350)), (True, False, (250, 400)), (False, True, (200, 350))]
+REFERENCE_SQUARES = (4.0, 23.5)
+
+
+def reference_flow_key(blend, balance, car_size) -> str:
+    return "flow/%d%d/%dx%d" % (blend, balance, car_size[0], car_size[1])
+
+
+def jpeg_header_signature(raw: bytes) -> str:
+    """Digest of what a baseline decoder reads before the entropy-coded data: every marker segment from SOI up to and including the SOS
+    header except APPn and COM (so DQT, SOF, DHT, DRI, SOS -- tables, size, sampling, restart interval)."""
+    assert raw[:2] == b"\xff\xd8", "not a JPEG file"
+    i, segs = 2, []
+    while i + 4 <= len(raw):
+        assert raw[i] == 0xFF, "marker expected at %d" % i
+        m, n = raw[i + 1], int.from_bytes(raw[i + 2:i + 4], "big")
+        if not (0xE0 <= m <= 0xEF or m == 0xFE):
+            segs.append(raw[i:i + 2 + n])
+        if m == 0xDA:
+            return hashlib.sha256(b"".join(segs)).hexdigest()
+        i += 2 + n
+    raise AssertionError("no SOS marker")
+
+
 def probe(arr: np.ndarray, n: int = 4096) -> np.ndarray:
     """Deterministic strided sample for diagnostics when a digest differs."""
     flat = np.ascontiguousarray(arr).reshape(-1)

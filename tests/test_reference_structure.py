@@ -1,109 +1,84 @@
-"""Runs the REFERENCE's own Python modules (from /root/reference) with `cv2` replaced by the oracle's primitives
-(tests/_cv2_shim.py) and compares with the oracle's restatement of the whole path: same frames in, same bytes out.
-This pins the structure of the restatement -- operation order, mask polygons, seam lines, blend-weight loop, padding,
-luminance / white balance composition, pad / crop rules -- against the reference itself.  The reference tree exists only
-in the build container: everywhere else these tests skip (nothing here runs on the GPU box)."""
-import importlib.util
+"""Holds the oracle's restatement of the whole path against what the REFERENCE's own Python modules compute: same frames in,
+same bytes out.  This pins the structure of the restatement -- operation order, mask polygons, seam lines, blend-weight loop,
+padding, luminance / white balance composition, pad / crop rules -- against the reference itself.
+
+The reference side is stored: tests/golden/make_reference_structure_goldens.py runs the reference's surroundBEV.py and
+extrinsicCalib.py with `cv2` replaced by the oracle's primitives (tests/_cv2_shim.py) on the sample rig of
+tests/golden/repo_rig.npz and writes the value digest of every array compared here to tests/golden/reference_structure.json."""
+import json
 import os
 import sys
 
 import numpy as np
 import pytest
 
-REF = os.environ.get("BEVW_REFERENCE_ROOT", "/root/reference")
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+from conftest import ROOT
 
-CAMS = ("front", "back", "left", "right")
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import _golden_cases as GC  # noqa: E402
 
-
-def load_reference_module(relpath, name):
-    """Import one reference file as a module with the oracle-built cv2 and an empty argv (they parse args at import)."""
-    import _cv2_shim
-
-    _cv2_shim.install()
-    spec = importlib.util.spec_from_file_location(name, os.path.join(REF, relpath))
-    mod = importlib.util.module_from_spec(spec)
-    argv, sys.argv = sys.argv, [sys.argv[0]]
-    try:
-        spec.loader.exec_module(mod)
-    finally:
-        sys.argv = argv
-    return mod
+CAMS, SQUARES, flow_key = GC.CAMS, GC.REFERENCE_SQUARES, GC.reference_flow_key
 
 
 @pytest.fixture(scope="module")
-def ref_sb():
-    mod = load_reference_module("SurroundBirdEyeView/surroundBEV.py", "reference_surroundBEV")
-    yield mod
-    sys.modules.pop("cv2", None)
+def golden():
+    with open(os.path.join(ROOT, "tests", "golden", "reference_structure.json")) as f:
+        return json.load(f)
 
 
-def test_reference_rig_files_equal_the_fixture(ref_sb, repo_rig):
-    cam = ref_sb.Camera.__new__(ref_sb.Camera)
+def same(golden, key, arr):
+    assert key in golden, "%s is not in tests/golden/reference_structure.json" % key
+    assert GC.value_digest(arr) == golden[key], "%s differs from the reference's (shape %s)" % (key, np.shape(arr))
+
+
+def test_reference_rig_files_equal_the_fixture(golden, repo_rig):
     for n in CAMS:
-        base = os.path.join(REF, "SurroundBirdEyeView", "data", n)
         for kind, want in zip("KDH", repo_rig.rig[n]):
-            assert np.array_equal(np.load(os.path.join(base, "camera_%s_%s.npy" % (n, kind))), want)
-    del cam
+            same(golden, "rig/%s/%s" % (n, kind), want)
 
 
-@pytest.mark.parametrize("blend,balance,car_size", [(False, False, (250, 400)), (True, True, (200, 350)), (True, False, (250, 400)),
-                                                    (False, True, (200, 350))])
-def test_reference_control_flow_equals_the_restatement(ref_sb, oracle, repo_rig, blend, balance, car_size):
-    args = ref_sb.BevGenerator.get_args()
-    args.CAR_WIDTH, args.CAR_HEIGHT = car_size            # main.py:79-81 uses 200 x 350, the module default is 250 x 400
-    gen = ref_sb.BevGenerator(blend=blend, balance=balance)
+@pytest.mark.parametrize("blend,balance,car_size", GC.REFERENCE_FLOWS)
+def test_reference_control_flow_equals_the_restatement(golden, oracle, repo_rig, blend, balance, car_size):
+    k = flow_key(blend, balance, car_size)
     cfg = dict(oracle.DEFAULT_CFG, CAR_WIDTH=car_size[0], CAR_HEIGHT=car_size[1])
     ref = oracle.RefBevGenerator(repo_rig.rig, cfg, blend=blend, balance=balance)
     for i, n in enumerate(CAMS):
-        assert np.array_equal(gen.cameras[i].camera_mat_dst, ref.cameras[i].K_dst), n
-        assert np.array_equal(gen.cameras[i].bev_maps[0], ref.cameras[i].bev_maps[0]), n
-        assert np.array_equal(gen.cameras[i].bev_maps[1], ref.cameras[i].bev_maps[1]), n
-        assert np.array_equal(gen.masks[i].mask, ref.masks[i]), n + " mask"
+        same(golden, k + "/%s/K_dst" % n, ref.cameras[i].K_dst)
+        same(golden, k + "/%s/bev_map0" % n, ref.cameras[i].bev_maps[0])
+        same(golden, k + "/%s/bev_map1" % n, ref.cameras[i].bev_maps[1])
+        same(golden, k + "/%s/mask" % n, ref.masks[i])
         if blend:
-            assert np.array_equal(gen.masks[i].weight, np.repeat(ref.weights[i][:, :, None], 3, axis=2)
-                                  if ref.weights[i].ndim == 2 else ref.weights[i]), n + " weight"
+            same(golden, k + "/%s/weight" % n, np.repeat(ref.weights[i][:, :, None], 3, axis=2) if ref.weights[i].ndim == 2 else ref.weights[i])
     frames = repo_rig.frames()
-    car = ref_sb.padding(repo_rig.image("car"), cfg["BEV_WIDTH"], cfg["BEV_HEIGHT"])
-    assert np.array_equal(car, oracle.padding(repo_rig.image("car"), cfg["BEV_WIDTH"], cfg["BEV_HEIGHT"]))
-    for c in (None, car):
-        got = gen(*[f.copy() for f in frames], car=c)
+    car = oracle.padding(repo_rig.image("car"), cfg["BEV_WIDTH"], cfg["BEV_HEIGHT"])
+    same(golden, k + "/car_padded", car)
+    for tag, c in (("nocar", None), ("car", car)):
         want = ref(*frames, car=c)
-        assert got.dtype == np.uint8 and got.shape == want.shape
-        assert np.array_equal(got, want), "%d bytes differ" % np.count_nonzero(got != want)
+        assert golden[k + "/out_%s_dtype" % tag] == "uint8" and want.dtype == np.uint8
+        same(golden, k + "/out_%s" % tag, want)
 
 
-def test_reference_balance_helpers_equal_the_restatement(ref_sb, oracle, repo_rig):
+def test_reference_balance_helpers_equal_the_restatement(golden, oracle, repo_rig):
     frames = repo_rig.frames()
-    got = ref_sb.luminance_balance([f.copy() for f in frames])
-    want = oracle.luminance_balance(frames)
-    for g, w in zip(got, want):
-        assert np.array_equal(g, w)
-    img = repo_rig.image("back")
-    assert np.array_equal(ref_sb.color_balance(img.copy()), oracle.color_balance(img))
+    for i, w in enumerate(oracle.luminance_balance(frames)):
+        same(golden, "balance/luminance/%d" % i, w)
+    same(golden, "balance/color_back", oracle.color_balance(repo_rig.image("back")))
 
 
-def test_reference_excalib_preprocessing_equals_the_mirror_rules(oracle, repo_rig):
-    ec = load_reference_module("ExtrinsicCalibration/extrinsicCalib.py", "reference_extrinsicCalib")
-    try:
-        img = repo_rig.image("back")[:301, :403]
-        h, w = img.shape[:2]
-        center = ec.CenterImage.__new__(ec.CenterImage)
-        center.x, center.y = 100, 250
-        assert np.array_equal(center.translate(img), oracle.translate(img, w // 2 - 100, h // 2 - 250))
-        a = ec.args
-        gx, gy = np.meshgrid(np.arange(a.BORAD_WIDTH), np.arange(a.BORAD_HEIGHT))
-        for square in (4.0, 23.5):
-            corners = np.stack([100 + gx * square, 50 + gy * square], -1).reshape(-1, 2).astype(np.float32)
-            sc = ec.ScaleImage(corners)
-            ref = oracle.resize_linear(img, sc.scale_factor, sc.scale_factor)
-            if sc.scale_factor < 1:
-                want = np.zeros_like(img)
-                t, l = (h - ref.shape[0]) // 2, (w - ref.shape[1]) // 2
-                want[t:t + ref.shape[0], l:l + ref.shape[1]] = ref
-            else:
-                t, l = (ref.shape[0] - h) // 2, (ref.shape[1] - w) // 2
-                want = ref[t:t + h, l:l + w]
-            assert np.array_equal(sc(img), want), square
-    finally:
-        sys.modules.pop("cv2", None)
+def test_reference_excalib_preprocessing_equals_the_mirror_rules(golden, oracle, repo_rig):
+    img = repo_rig.image("back")[:301, :403]
+    h, w = img.shape[:2]
+    same(golden, "excalib/translate_100_250", oracle.translate(img, w // 2 - 100, h // 2 - 250))
+    assert golden["excalib/board"] == [7, 6]
+    for square in SQUARES:
+        factor = golden["excalib/scale/%g/factor" % square]
+        assert factor == 10.0 / square   # ScaleImage: args.SCALED_SIZE / the mean corner distance of the synthetic board (extrinsicCalib.py:91)
+        ref = oracle.resize_linear(img, factor, factor)
+        if factor < 1:
+            want = np.zeros_like(img)
+            t, l = (h - ref.shape[0]) // 2, (w - ref.shape[1]) // 2
+            want[t:t + ref.shape[0], l:l + ref.shape[1]] = ref
+        else:
+            t, l = (ref.shape[0] - h) // 2, (ref.shape[1] - w) // 2
+            want = ref[t:t + h, l:l + w]
+        same(golden, "excalib/scale/%g" % square, want)

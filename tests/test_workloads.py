@@ -91,6 +91,42 @@ def test_bench_shard_sizes():
     assert bench.shard_sizes(10, 4) == [3, 3, 2, 2] and sum(bench.shard_sizes(257, 8)) == 257
 
 
+def test_bench_output_dump(tmp_path):
+    """bench.py --dump-outputs: the dense images a caller receives (row padding dropped), the same seeded sample every time, float
+    only, at most 64 MB for the flagship's 1080 x 1080 BEV images with 1088-pixel device rows (the size does not depend on the batch)."""
+    import bench
+
+    class HostBuffer:   # DeviceBuffer.download over a host array
+        def __init__(self, a):
+            self.a = a.reshape(-1)
+
+        def download(self, shape, dtype=np.uint8, offset=0):
+            n = int(np.prod(shape))
+            assert offset + n <= self.a.size
+            return self.a[offset:offset + n].reshape(shape).copy()
+
+    n, h, w, pitch = 8, 1080, 1080, 1088
+    dense = np.random.default_rng(3).integers(0, 256, (n, h, w, 3), dtype=np.uint8)
+    padded = np.zeros((n, h, pitch, 3), np.uint8)
+    padded[:, :, :w] = dense
+    padded[:, :, w:] = 77
+    out = bench.image_outputs("bev", HostBuffer(padded), n, h, w, h * pitch * 3, pitch * 3)
+    assert np.array_equal(out["bev_images"], dense[:2])
+    idx = out["bev_rows_index"].astype(np.int64)
+    assert idx[:, 0].max() > n // 2 and np.array_equal(out["bev_rows"], dense[idx[:, 0], idx[:, 1]])
+    again = bench.image_outputs("bev", HostBuffer(padded), n, h, w, h * pitch * 3, pitch * 3)
+    assert all(np.array_equal(out[k], again[k]) for k in out)
+    files = bench.file_outputs("jpeg_files", [b"\xff\xd8ab", b"\xff\xd8c", b"\xff\xd8"])
+    assert files["jpeg_files_lengths"].tolist() == [4, 3, 2] and files["jpeg_files_bytes"].size == 9
+    bench.write_outputs(str(tmp_path / "d"), dict(out, **files))
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(k + ".npy" for k in list(out) + list(files))
+    assert sum(os.path.getsize(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")) <= 64 << 20
+    for f in os.listdir(tmp_path / "d"):
+        assert np.load(tmp_path / "d" / f).dtype in (np.float32, np.float64)
+    with pytest.raises(AssertionError):
+        bench.write_outputs(str(tmp_path / "e"), {"x": np.zeros(1, np.uint8)})
+
+
 def test_drop_in_top_level_import(tmp_path):
     """main.py:5-7 imports `SurroundBirdEyeView`, `IntrinsicCalibration`, `ExtrinsicCalibration` as top-level packages."""
     import subprocess

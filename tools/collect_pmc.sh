@@ -11,7 +11,7 @@ while read -r set; do
   [ -z "$set" ] && continue
   i=$((i+1))
   rm -rf /tmp/pmc_$i
-  timeout 90 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc_$i -- python $R/bench.py --workload $W --steps 3 --warmup 1 --no-cpu-baseline > /tmp/pmc_$i.log 2>&1
+  timeout 90 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc_$i -- python $R/bench.py --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline > /tmp/pmc_$i.log 2>&1
   f=$(find /tmp/pmc_$i -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then cp $f $O/pass_$i.csv; echo "pass $i ok: $set"; else echo "pass $i FAILED: $set"; tail -2 /tmp/pmc_$i.log; fi
 done <<'SETS'
