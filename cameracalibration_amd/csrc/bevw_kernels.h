@@ -1,8 +1,9 @@
-// bevw_kernels.h -- HIP kernels of libbevwarp (gfx950).  Table builders (run once per calibration) and the
-// per-frame kernels of the first, always-valid schedule (BEVW_SCHED_PER_PIXEL).  The tile-plan schedule lives in
-// bevw_plan.h.
+// bevw_kernels.h -- HIP kernels of libbevwarp (gfx950), compiled in bevwarp.hip only.  Table builders (run once per calibration)
+// and the per-frame kernels of the first, always-valid schedule (BEVW_SCHED_PER_PIXEL).  The tile-plan schedule lives in
+// bevw_plan.h (compiled in bevwarp_plan.hip); the two headers share only bevw_device.h and bevw_planapi.h.
 #pragma once
 #include "bevw_device.h"
+#include "bevw_planapi.h"
 
 namespace bevw {
 
@@ -376,13 +377,6 @@ static __global__ void k_lum_shift(const uint8_t *__restrict__ frames, size_t fr
         out[base + p * 3] = (uint8_t)b; out[base + p * 3 + 1] = (uint8_t)g; out[base + p * 3 + 2] = (uint8_t)r;
     }
 }
-
-// Static tables of one BevGenerator as the per-pixel schedule reads them.
-struct StitchTables {
-    const int16_t *lut1[4];
-    const uint16_t *lut2[4];
-    const uint8_t *mask[4];
-};
 
 // BevGenerator.__call__ (surroundBEV.py:312-325), schedule BEVW_SCHED_PER_PIXEL: one thread per BEV pixel loops the
 // four cameras: mask test -> LUT fetch -> fixed-point bilinear gather (with the luminance round trip on the fetched

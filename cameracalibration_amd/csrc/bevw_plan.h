@@ -23,7 +23,8 @@
 #include <algorithm>
 #include <vector>
 
-#include "bevw_kernels.h"
+#include "bevw_device.h"
+#include "bevw_planapi.h"
 
 namespace bevw {
 
@@ -35,42 +36,6 @@ constexpr uint32_t kHdrEmpty = 4u;         // no contributor at all (car rectang
 constexpr uint32_t kHdrBlock = 1024u;      // base tile is owned by a unit (bevw_unit.h): not on the per-tap kernel's list
 constexpr int kPlanLX = 8;                 // lanes along x -> 32 x 8 pixel base tiles
 constexpr int kPlanLY = 64 / kPlanLX;
-
-struct Plan {
-    void *entries = nullptr;     // uint2[ntiles][8][64]
-    void *hdr = nullptr;         // uint32[ntiles]
-    void *psums = nullptr;       // uint32[batch][ntiles][3]  (balance: per-tile channel sums)
-    size_t psums_cap = 0;
-    int psums_layout = -1;       // entries per frame the zeros of psums were laid out for (plan_stitch_impl)
-    // destination widths that are not a multiple of 4 pixels: the kernels' 12-byte stores need dword-aligned pixel quads,
-    // so they write rows of `pitch` = bw rounded up to 4 pixels into pad_out and k_plan_unpad compacts them (one more
-    // pass over the output instead of the per-pixel schedule)
-    int pitch = 0;
-    bool out_pitched = false;    // the caller's output images have rows of `pitch` pixels themselves (bevw_set_output_pitch): no scratch, no compaction
-    void *pad_out = nullptr, *pad_car = nullptr;
-    size_t pad_cap = 0;
-    int *d_max = nullptr;
-    int fw = 0, fh = 0, bw = 0, bh = 0;
-    int tiles_x = 0, tiles_y = 0, ntiles = 0;
-    int ncams = 4;
-    void *groups = nullptr;      // uint32[n_groups]: byte offsets (inside the frame set) of the sampled 4-texel groups
-    int n_groups = 0;
-    bool band_ok = false;        // the sampled-group list exists (balance schedule 1)
-    int max_contrib = 0;
-    bool usable = false;
-    void *list_slow = nullptr;   // base tiles no unit owns (frame-border footprints; everything when there are no units)
-    int n_slow = 0;
-    // unit schedule (bevw_unit.h): k-d partition compiled on the host
-    void *un_desc = nullptr, *un_entries = nullptr, *un_gsrc = nullptr;
-    void *un_gsrc_compact = nullptr;         // the units' group lists for the compact scratch of the balance schedule (unit_gsrc_compact); nullptr: not usable
-    size_t compact_stride = 0;               // bytes between the compact scratch copies of consecutive frame sets
-    void *list_un_all = nullptr;             // every unit in partition order, class in bits 28..31
-    int n_un_all = 0;
-    int n_un[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // units per class (diagnostics)
-    int n_unit_tiles = 0;                    // base tiles the units own
-    size_t un_lines = 0, un_sectors = 0;     // request arithmetic of the partition (per frame)
-    int un_skew = 0;
-};
 
 struct __attribute__((packed, aligned(1))) PackedU2 { uint32_t x, y; };
 __device__ __forceinline__ uint2 load_u2_unaligned(const uint8_t *p)
@@ -501,14 +466,6 @@ static __global__ void k_plan_unpad(const uint8_t *__restrict__ src, int bw, int
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-static inline void plan_release(Plan &p)
-{
-    void *ptrs[] = {p.un_desc, p.un_entries, p.un_gsrc, p.un_gsrc_compact, p.list_un_all, p.entries, p.hdr, p.groups, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
-    p = Plan();
-}
-
 static inline hipError_t plan_upload_list(const std::vector<uint32_t> &v, void **dptr)
 {
     *dptr = nullptr;
@@ -757,13 +714,6 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     return hipSuccess;
-}
-
-// the partial channel sums the last plan_stitch_impl call with sums left for frame `first` of the psums buffer, and their number per frame
-static inline const uint32_t *plan_sum_entries(const Plan &p, int first, int &nsum)
-{
-    nsum = p.psums_layout;
-    return static_cast<const uint32_t *>(p.psums) + (size_t)first * (size_t)(nsum > 0 ? nsum : 0) * 3;
 }
 
 // a plan that holds only a WIDE unit schedule (analytic projection mode: plan_analytic_units) -> one launch of k_plan_unit_wide

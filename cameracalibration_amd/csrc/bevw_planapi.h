@@ -1,11 +1,56 @@
-// bevw_planapi.h -- what the rest of the library sees of the tile plan (defined in bevwarp_plan.hip, the only translation unit that
-// instantiates the plan kernels of bevw_plan.h / bevw_unit.h).  Every function returns a BEVW_* status and leaves its message in
-// bevw_last_error().
+// bevw_planapi.h -- what the rest of the library sees of the tile plan: the Plan a handle owns, the tables it is compiled from and the
+// entry points.  Declarations only: the plan kernels (bevw_plan.h, bevw_unit.h) are compiled in bevwarp_plan.hip alone, which defines
+// everything declared here.  Every plan_* function that returns an int returns a BEVW_* status and leaves its message in bevw_last_error().
 #pragma once
 #include "bevw_host.h"
-#include "bevw_plan.h"
 
 namespace bevw {
+
+// Static tables of one BevGenerator as the per-pixel schedule and the plan compiler read them.
+struct StitchTables {
+    const int16_t *lut1[4];
+    const uint16_t *lut2[4];
+    const uint8_t *mask[4];
+};
+
+struct HsvTables;   // bevw_device.h
+
+// a compiled tile plan: its device buffers and the geometry they were built for (plan_build / plan_build_wide)
+struct Plan {
+    void *entries = nullptr;     // uint2[ntiles][8][64]
+    void *hdr = nullptr;         // uint32[ntiles]
+    void *psums = nullptr;       // uint32[batch][ntiles][3]  (balance: per-tile channel sums)
+    size_t psums_cap = 0;
+    int psums_layout = -1;       // entries per frame the zeros of psums were laid out for (plan_stitch_impl)
+    // destination widths that are not a multiple of 4 pixels: the kernels' 12-byte stores need dword-aligned pixel quads,
+    // so they write rows of `pitch` = bw rounded up to 4 pixels into pad_out and k_plan_unpad compacts them (one more
+    // pass over the output instead of the per-pixel schedule)
+    int pitch = 0;
+    bool out_pitched = false;    // the caller's output images have rows of `pitch` pixels themselves (bevw_set_output_pitch): no scratch, no compaction
+    void *pad_out = nullptr, *pad_car = nullptr;
+    size_t pad_cap = 0;
+    int *d_max = nullptr;
+    int fw = 0, fh = 0, bw = 0, bh = 0;
+    int tiles_x = 0, tiles_y = 0, ntiles = 0;
+    int ncams = 4;
+    void *groups = nullptr;      // uint32[n_groups]: byte offsets (inside the frame set) of the sampled 4-texel groups
+    int n_groups = 0;
+    bool band_ok = false;        // the sampled-group list exists (balance schedule 1)
+    int max_contrib = 0;
+    bool usable = false;
+    void *list_slow = nullptr;   // base tiles no unit owns (frame-border footprints; everything when there are no units)
+    int n_slow = 0;
+    // unit schedule (bevw_unit.h): k-d partition compiled on the host
+    void *un_desc = nullptr, *un_entries = nullptr, *un_gsrc = nullptr;
+    void *un_gsrc_compact = nullptr;         // the units' group lists for the compact scratch of the balance schedule (unit_gsrc_compact); nullptr: not usable
+    size_t compact_stride = 0;               // bytes between the compact scratch copies of consecutive frame sets
+    void *list_un_all = nullptr;             // every unit in partition order, class in bits 28..31
+    int n_un_all = 0;
+    int n_un[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // units per class (diagnostics)
+    int n_unit_tiles = 0;                    // base tiles the units own
+    size_t un_lines = 0, un_sectors = 0;     // request arithmetic of the partition (per frame)
+    int un_skew = 0;
+};
 
 // compile LUT + masks into a plan (table kernels, unit compiler on the host).  out_pitch: pixels per output row when the caller's images
 // are pitched (0: dense); blend: the handle applies blend weights (its units carry no two-quad two-contributor class)
@@ -29,5 +74,11 @@ int plan_build_wide(Plan &p, const std::vector<int16_t> sxy[4], const std::vecto
 int plan_stitch_wide(const Plan &p, hipStream_t st, const uint8_t *d_frames, int batch, bool blend, const uint8_t *d_car, uint8_t *d_out);
 
 bool plan_units_enabled();   // BEVW_PLAN_UNITS (default 1)
+
+// frees the plan's device buffers and leaves an empty Plan
+void plan_release(Plan &p);
+
+// the partial channel sums the last plan_stitch call with sums left for frame `first` of the psums buffer, and their number per frame
+const uint32_t *plan_sum_entries(const Plan &p, int first, int &nsum);
 
 }  // namespace bevw

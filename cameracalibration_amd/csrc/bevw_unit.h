@@ -1,4 +1,4 @@
-// bevw_unit.h -- the UNIT schedule of the tile plan (included by bevw_plan.h after bevw_block.h; round 3).
+// bevw_unit.h -- the UNIT schedule of the tile plan (included by bevw_plan.h after bevw_pair.h; round 3).
 //
 // Why.  The stitch is bound by the NUMBER of vector-L1 -> L2 requests.  Round 2's schedule paid, per
 // frame of BASELINE config 3, ~61 k source-line requests (13 k for the dense 64 x 32 block tiles, 48 k for the per-wave

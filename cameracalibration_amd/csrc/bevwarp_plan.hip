@@ -1,8 +1,23 @@
-// bevwarp_plan.hip -- the tile plan of libbevwarp.so: the one translation unit that instantiates the per-frame stitch kernels
-// (bevw_plan.h: k_stitch_plan; bevw_unit.h: k_plan_units, k_plan_unit_wide) and the plan compiler's kernels.  Interface: bevw_planapi.h.
-#include "bevw_planapi.h"
+// bevwarp_plan.hip -- the tile plan of libbevwarp.so: the one translation unit that includes bevw_plan.h and so compiles its kernels -- the
+// per-frame stitch kernels (bevw_plan.h: k_stitch_plan; bevw_unit.h: k_plan_units, k_plan_unit_wide) and the plan compiler's kernels.
+// The rest of the library sees only the declarations of bevw_planapi.h, all defined here.
+#include "bevw_plan.h"
 
 namespace bevw {
+
+void plan_release(Plan &p)
+{
+    void *ptrs[] = {p.un_desc, p.un_entries, p.un_gsrc, p.un_gsrc_compact, p.list_un_all, p.entries, p.hdr, p.groups, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
+    for (void *q : ptrs)
+        if (q) (void)hipFree(q);
+    p = Plan();
+}
+
+const uint32_t *plan_sum_entries(const Plan &p, int first, int &nsum)
+{
+    nsum = p.psums_layout;
+    return static_cast<const uint32_t *>(p.psums) + (size_t)first * (size_t)(nsum > 0 ? nsum : 0) * 3;
+}
 
 static UnitTuning unit_tuning_env()
 {

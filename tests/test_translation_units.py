@@ -1,0 +1,49 @@
+"""Every kernel of libbevwarp.so is compiled in exactly one translation unit.  bevwarp.hip sees the tile plan only through the
+declarations of bevw_planapi.h, and bevwarp_plan.hip does not include bevw_kernels.h: no code object carries a second copy of another
+unit's kernels, and no templated kernel is registered from two code objects under one host stub.  Checked on the gfx950 code object of
+each unit's object file (no GPU needed)."""
+import os
+import re
+import subprocess
+
+import pytest
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+LLVM_BIN = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))), "llvm", "bin")
+TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+
+
+def _kernels(obj: str, tmp: str) -> set:
+    """Names of the kernels (their kernel descriptors, `<name>.kd`) in the gfx950 code object of a unit's object file."""
+    stem = os.path.join(tmp, os.path.basename(obj))
+    subprocess.run([os.path.join(LLVM_BIN, "llvm-objcopy"), "--dump-section=.hip_fatbin=" + stem + ".fatbin", obj, stem + ".host"],
+                   check=True, capture_output=True, timeout=120)
+    subprocess.run([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=" + TARGET,
+                    "--input=" + stem + ".fatbin", "--output=" + stem + ".co"], check=True, capture_output=True, timeout=120)
+    syms = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "-s", stem + ".co"], check=True, capture_output=True, text=True,
+                          timeout=120).stdout
+    return set(re.findall(r"\s(\S+)\.kd$", syms, flags=re.M))
+
+
+@pytest.fixture(scope="module")
+def kernels(tmp_path_factory):
+    from cameracalibration_amd import build
+
+    build.build()
+    tmp = str(tmp_path_factory.mktemp("units"))
+    return {u: _kernels(os.path.join(build.OBJ, u.replace(".hip", ".o")), tmp) for u in build.UNITS}
+
+
+def test_no_kernel_in_two_units(kernels):
+    units = sorted(kernels)
+    for i, a in enumerate(units):
+        for b in units[i + 1:]:
+            assert not kernels[a] & kernels[b], (a, b, sorted(kernels[a] & kernels[b]))
+
+
+def test_kernels_live_in_their_own_unit(kernels):
+    plan_units = {k for k in kernels["bevwarp_plan.hip"] if "k_plan_units" in k}
+    assert len(plan_units) == 4, sorted(plan_units)   # k_plan_units<BLEND, SUMS>
+    assert any("k_stitch_plan" in k for k in kernels["bevwarp_plan.hip"])
+    assert any("k_stitch_pp" in k for k in kernels["bevwarp.hip"])
+    assert any("k_jpeg" in k for k in kernels["bevwarp_jpeg.hip"])
