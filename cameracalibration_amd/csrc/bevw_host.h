@@ -1,6 +1,7 @@
 // bevw_host.h -- host-side plumbing shared by the translation units of libbevwarp.so (bevwarp.hip: handles, tables, tools, the
 // camera-per-GPU exchange; bevwarp_plan.hip: the tile plan and its kernels; bevwarp_jpeg.hip: the JPEG codec): the thread-local
-// error string behind bevw_last_error(), the HIP_TRY / BEVW_TRY early-return macros, device / pinned buffers, the lap timer.
+// error string behind bevw_last_error(), the HIP_TRY / BEVW_TRY early-return macros, device / pinned buffers, the lap timer, and the two
+// launch helpers (batch chunks, compile-time flags).
 #pragma once
 #include "../../include/bevwarp.h"
 
@@ -10,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 // one string per thread and library (C++17 inline variable: the same object in every translation unit)
@@ -54,6 +56,24 @@ static inline int launch_check(const char *what)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(BEVW_E_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
     return BEVW_OK;
+}
+
+// f(first, count) over [0, n) in spans of at most `max`: a batch rides in grid.y or grid.z, which hold at most 65535 blocks
+template <typename F>
+static inline void for_each_chunk(int n, F &&f, int max = 65535)
+{
+    for (int first = 0; first < n; first += max) f(first, n - first < max ? n - first : max);
+}
+
+// f(std::integral_constant<bool, b>...) for the runtime flags b...: picks the kernel instantiation, f(bl, ba) launches k<bl, ba>.
+// Instantiates f -- and so the kernel -- for all 2^n combinations of the flags: only for kernels that exist in every combination.
+template <typename F>
+static inline void with_flags(F &&f) { f(); }
+template <typename F, typename... B>
+static inline void with_flags(F &&f, bool b, B... rest)
+{
+    if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 // Lap timer: HIP events recorded on an engine's own stream WITHOUT synchronising, read back after the caller's final sync

@@ -586,6 +586,40 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
 // nb: frames per block (0 = default); xcd_map: 1 = an XCD owns whole batch chunks; units: 0 = the per-tap kernel over every tile (debug)
 struct PlanTuning { int nb = 0; int xcd_map = 1; int units = 1; };
 
+// The PlanArgs fields the per-frame plan kernels share: geometry, unit tables, frames per block and the XCD map.  The caller adds its
+// tile list, its group count and what its kernel reads beyond these.
+static inline PlanArgs plan_args(const Plan &p, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out, const PlanTuning &tune)
+{
+    PlanArgs a = {};
+    a.frames = d_frames; a.car = d_car; a.out = d_out;
+    a.fw = p.fw; a.fh = p.fh; a.bw = p.bw; a.bh = p.bh; a.pitch = p.pitch;
+    a.tiles_x = p.tiles_x; a.ntiles = p.ntiles; a.ncams = p.ncams;
+    a.un_desc = static_cast<const UnitDesc *>(p.un_desc);
+    a.un_entries = static_cast<const uint4 *>(p.un_entries);
+    a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc);
+    a.un_skew = p.un_skew;
+    a.batch = batch;
+    // frames per block: enough chunks to give each of the 8 XCDs whole chunks, otherwise one frame per chunk.  A block reads its plan
+    // slice (4 bytes per pixel + the group list) once per chunk: 16 frames per block instead of 8 halve that traffic -- 1.8 M of the
+    // 13.6 M read requests of a config-3 step -- for -5 % (direct), -7 % (blend) (profiles/r03/sweeps.log; 32 frames: the tail of 8 long
+    // chunks costs more than it saves).
+    // Batches of 32 .. 127 frame sets: 8 frames per block even when that leaves fewer than 8 chunks (the 4K rig at batch 32: 4 chunks in
+    // plain chunk-major order, -9 % against 8 chunks of 4 frames).  An explicit BEVW_PLAN_NB is taken as it is.
+    int nb = tune.nb > 0 ? tune.nb : (batch >= 128 ? 16 : (batch >= 32 ? 8 : (batch >= 8 ? batch / 8 : 1)));
+    if (nb > batch) nb = batch;
+    a.nb = nb;
+    a.nchunks = (batch + nb - 1) / nb;
+    a.xcd_affine = (a.nchunks >= 8 && tune.xcd_map) ? tune.xcd_map : 0;
+    return a;
+}
+
+// blocks of a launch over a.ngroups groups per batch chunk: the XCD maps deal the chunks in whole rounds of 8 (plan_block_map)
+static inline unsigned plan_grid(const PlanArgs &a)
+{
+    if (a.xcd_affine >= 1) return (unsigned)(a.ngroups * (((a.nchunks + 7) / 8) * 8));
+    return (unsigned)(a.ngroups * a.nchunks);
+}
+
 // One step of the tile plan on `st`.
 //   balance   = luminance round trip per tap on RAW frames (per-tap kernel over every tile) + per-tile channel sums;
 //   d_scratch = the compact scratch plan_lum_band filled from d_frames (balance schedule 1): the units read IT (p.compact_stride bytes per
@@ -600,11 +634,9 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
                                           int psums_frames = 0, int psums_first = 0, const uint8_t *d_scratch = nullptr)
 {
     hipError_t e;
-    PlanArgs a = {};
-    a.frames = d_frames; a.plan = static_cast<const uint2 *>(p.entries); a.hdr = static_cast<const uint32_t *>(p.hdr);
-    a.deltas = d_deltas; a.tab = d_tab; a.car = d_car; a.out = d_out;
-    a.fw = p.fw; a.fh = p.fh; a.bw = p.bw; a.bh = p.bh;
-    a.pitch = p.pitch;
+    PlanArgs a = plan_args(p, d_frames, batch, d_car, d_out, tune);
+    a.plan = static_cast<const uint2 *>(p.entries); a.hdr = static_cast<const uint32_t *>(p.hdr);
+    a.deltas = d_deltas; a.tab = d_tab;
     const bool padded = p.pitch != p.bw, scratch = padded && !p.out_pitched;
     if (padded) {
         const size_t img = (size_t)p.pitch * p.bh * 3, need = scratch ? img * (size_t)batch : 0;
@@ -622,28 +654,10 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         }
         if (scratch) a.out = static_cast<uint8_t *>(p.pad_out);
     }
-    a.tiles_x = p.tiles_x; a.ntiles = p.ntiles;
-    a.ncams = p.ncams;
-    a.un_desc = static_cast<const UnitDesc *>(p.un_desc);
-    a.un_entries = static_cast<const uint4 *>(p.un_entries);
-    a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc);
-    a.un_skew = p.un_skew;
     // the units need 4-byte aligned frame sets (dword-addressed group loads) and are not combined with the per-tap luminance kernel
     const bool compact = d_scratch != nullptr;
     const bool use_units = !balance && tune.units && p.n_un_all > 0 && (((uintptr_t)d_frames) & 3u) == 0 &&
                            (!compact || (p.un_gsrc_compact != nullptr && (((uintptr_t)d_scratch) & 3u) == 0));
-    a.batch = batch;
-    // frames per block: enough chunks to give each of the 8 XCDs whole chunks, otherwise one frame per chunk.  A block reads its plan
-    // slice (4 bytes per pixel + the group list) once per chunk: 16 frames per block instead of 8 halve that traffic -- 1.8 M of the
-    // 13.6 M read requests of a config-3 step -- for -5 % (direct), -7 % (blend) (profiles/r03/sweeps.log; 32 frames: the tail of 8 long
-    // chunks costs more than it saves).
-    // Batches of 32 .. 127 frame sets: 8 frames per block even when that leaves fewer than 8 chunks (the 4K rig at batch 32: 4 chunks in
-    // plain chunk-major order, -9 % against 8 chunks of 4 frames).  An explicit BEVW_PLAN_NB is taken as it is.
-    int nb = tune.nb > 0 ? tune.nb : (batch >= 128 ? 16 : (batch >= 32 ? 8 : (batch >= 8 ? batch / 8 : 1)));
-    if (nb > batch) nb = batch;
-    a.nb = nb;
-    a.nchunks = (batch + nb - 1) / nb;
-    a.xcd_affine = (a.nchunks >= 8 && tune.xcd_map) ? tune.xcd_map : 0;
     const bool with_sums = balance || sums;
     // channel-sum entries per frame: one per unit + one per base tile left to the per-tap kernel (or one per tile without units).  Every
     // entry has exactly one writer per frame (no atomics, round 5: 2.4 M atomic adds per config-4 step cost 58 us of the 600), and every writer
@@ -660,25 +674,16 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
             p.psums = nullptr; p.psums_cap = 0;
             if ((e = hipMalloc(&p.psums, need)) != hipSuccess) return e;
             p.psums_cap = need;
-            p.psums_layout = -1;
         }
         p.psums_layout = a.nsum;   // (entries per frame of the layout in use: plan_sum_entries)
         a.psums = static_cast<uint32_t *>(p.psums) + (size_t)psums_first * a.nsum * 3;
     }
-    auto grid_blocks = [&]() -> unsigned {
-        if (a.xcd_affine >= 1) return (unsigned)(a.ngroups * (((a.nchunks + 7) / 8) * 8));
-        return (unsigned)(a.ngroups * a.nchunks);
-    };
     const dim3 block(256);
     if (use_units) {
         if (sums) a.car = nullptr;   // the car is added behind the gains
         a.tile_list = static_cast<const uint32_t *>(p.list_un_all); a.nlist = p.n_un_all; a.ngroups = p.n_un_all;
         if (compact) { a.frames = d_scratch; a.set_stride = (uint32_t)p.compact_stride; a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_compact); }
-        const dim3 grid(grid_blocks());
-        if (blend && sums) hipLaunchKernelGGL((k_plan_units<true, true>), grid, block, 0, st, a);
-        else if (blend) hipLaunchKernelGGL((k_plan_units<true, false>), grid, block, 0, st, a);
-        else if (sums) hipLaunchKernelGGL((k_plan_units<false, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_plan_units<false, false>), grid, block, 0, st, a);
+        with_flags([&](auto bl, auto sm) { hipLaunchKernelGGL((k_plan_units<bl, sm>), dim3(plan_grid(a)), block, 0, st, a); }, blend, sums);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const int n_tap = use_units ? p.n_slow : p.ntiles;
@@ -687,17 +692,10 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         a.nlist = n_tap; a.ngroups = (n_tap + 3) / 4;
         if (sums) a.car = nullptr;
         a.frames = d_frames; a.set_stride = 0;   // the per-tap kernel reads whole frames: RAW ones in the balance modes
-        const dim3 grid(grid_blocks());
-        if (balance || (compact && sums)) {
-            if (blend) hipLaunchKernelGGL((k_stitch_plan<true, true>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((k_stitch_plan<false, true>), grid, block, 0, st, a);
-        } else if (compact) {   // luminance round trip per tap, no channel sums (camera-per-GPU shards: the stitch rank balances the colours)
-            if (blend) hipLaunchKernelGGL((k_stitch_plan<true, true, false>), grid, block, 0, st, a);
-            else hipLaunchKernelGGL((k_stitch_plan<false, true, false>), grid, block, 0, st, a);
-        } else if (blend && sums) hipLaunchKernelGGL((k_stitch_plan<true, false, true>), grid, block, 0, st, a);
-        else if (blend) hipLaunchKernelGGL((k_stitch_plan<true, false>), grid, block, 0, st, a);
-        else if (sums) hipLaunchKernelGGL((k_stitch_plan<false, false, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((k_stitch_plan<false, false>), grid, block, 0, st, a);
+        // LUM: luminance round trip per tap (the RAW frames of balance, or the tiles no unit owns beside the compact scratch); compact
+        // without sums: camera-per-GPU shards, whose stitch rank balances the colours
+        with_flags([&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm>), dim3(plan_grid(a)), block, 0, st, a); },
+                   blend, balance || compact, balance || sums);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (with_sums && d_chsums != nullptr) {   // (nullptr: the caller's gain pass adds the partial sums itself: plan_sum_entries)
@@ -721,24 +719,9 @@ static inline hipError_t plan_unit_wide_launch(const Plan &p, hipStream_t st, co
                                                uint8_t *d_out, const PlanTuning &tune)
 {
     if (p.n_un_all == 0) return hipSuccess;
-    PlanArgs a = {};
-    a.frames = d_frames; a.car = d_car; a.out = d_out;
-    a.fw = p.fw; a.fh = p.fh; a.bw = p.bw; a.bh = p.bh; a.pitch = p.pitch;
-    a.tiles_x = p.tiles_x; a.ntiles = p.ntiles; a.ncams = p.ncams;
-    a.un_desc = static_cast<const UnitDesc *>(p.un_desc);
-    a.un_entries = static_cast<const uint4 *>(p.un_entries);
-    a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc);
-    a.un_skew = p.un_skew;
-    a.batch = batch;
-    int nb = tune.nb > 0 ? tune.nb : (batch >= 128 ? 16 : (batch >= 32 ? 8 : (batch >= 8 ? batch / 8 : 1)));   // as plan_stitch_impl
-    if (nb > batch) nb = batch;
-    a.nb = nb;
-    a.nchunks = (batch + nb - 1) / nb;
-    a.xcd_affine = (a.nchunks >= 8 && tune.xcd_map) ? tune.xcd_map : 0;
+    PlanArgs a = plan_args(p, d_frames, batch, d_car, d_out, tune);
     a.tile_list = static_cast<const uint32_t *>(p.list_un_all); a.nlist = p.n_un_all; a.ngroups = p.n_un_all;
-    const unsigned grid = a.xcd_affine ? (unsigned)(a.ngroups * (((a.nchunks + 7) / 8) * 8)) : (unsigned)(a.ngroups * a.nchunks);
-    if (blend) hipLaunchKernelGGL((k_plan_unit_wide<true>), dim3(grid), dim3(kUnitThreads), 0, st, a);
-    else hipLaunchKernelGGL((k_plan_unit_wide<false>), dim3(grid), dim3(kUnitThreads), 0, st, a);
+    with_flags([&](auto bl) { hipLaunchKernelGGL((k_plan_unit_wide<bl>), dim3(plan_grid(a)), dim3(kUnitThreads), 0, st, a); }, blend);
     return hipGetLastError();
 }
 
@@ -748,13 +731,12 @@ static inline hipError_t plan_lum_band(const Plan &p, hipStream_t st, const uint
 {
     if (p.n_groups == 0 || p.compact_stride == 0) return hipSuccess;
     const size_t set_bytes = (size_t)p.fw * p.fh * 3 * p.ncams;
-    for (int b0 = 0; b0 < batch; b0 += 65535) {
-        const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
-        const unsigned bpf = (unsigned)(p.n_groups + 256 * kLumTrips - 1) / (256 * kLumTrips);
+    const unsigned bpf = (unsigned)(p.n_groups + 256 * kLumTrips - 1) / (256 * kLumTrips);
+    for_each_chunk(batch, [&](int b0, int nb) {
         hipLaunchKernelGGL(k_lum_groups, dim3(xcd_frame_grid(bpf, (unsigned)nb)), dim3(256), 0, st, d_frames + (size_t)b0 * set_bytes,
                            d_scratch + (size_t)b0 * p.compact_stride, set_bytes, p.compact_stride, (uint32_t)p.fw * p.fh * 3,
                            static_cast<const uint32_t *>(p.groups), p.n_groups, d_deltas + (size_t)b0 * 4, d_tab, bpf, (uint32_t)nb);
-    }
+    });
     return hipGetLastError();
 }
 

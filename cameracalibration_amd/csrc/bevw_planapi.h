@@ -21,7 +21,7 @@ struct Plan {
     void *hdr = nullptr;         // uint32[ntiles]
     void *psums = nullptr;       // uint32[batch][ntiles][3]  (balance: per-tile channel sums)
     size_t psums_cap = 0;
-    int psums_layout = -1;       // entries per frame the zeros of psums were laid out for (plan_stitch_impl)
+    int psums_layout = -1;       // entries per frame of the layout the last plan_stitch call with sums wrote (plan_sum_entries)
     // destination widths that are not a multiple of 4 pixels: the kernels' 12-byte stores need dword-aligned pixel quads,
     // so they write rows of `pitch` = bw rounded up to 4 pixels into pad_out and k_plan_unpad compacts them (one more
     // pass over the output instead of the per-pixel schedule)
@@ -72,8 +72,6 @@ int plan_pad_image(hipStream_t st, const uint8_t *d_src, int bw, int pitch, int 
 int plan_build_wide(Plan &p, const std::vector<int16_t> sxy[4], const std::vector<uint32_t> frac[4], const std::vector<uint8_t> mask[4], int fw, int fh,
                     int bw, int bh, bool blend);
 int plan_stitch_wide(const Plan &p, hipStream_t st, const uint8_t *d_frames, int batch, bool blend, const uint8_t *d_car, uint8_t *d_out);
-
-bool plan_units_enabled();   // BEVW_PLAN_UNITS (default 1)
 
 // frees the plan's device buffers and leaves an empty Plan
 void plan_release(Plan &p);

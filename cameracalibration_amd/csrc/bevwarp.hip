@@ -216,7 +216,6 @@ static int build_fisheye_maps(hipStream_t st, const double K[9], const double D[
     hipLaunchKernelGGL(k_fisheye_map, grid, dim3(256), 0, st, p, dxs.as<double>(), w, h, d_map1, d_map2);
     BEVW_TRY(launch_check("k_fisheye_map"));
     HIP_TRY(hipStreamSynchronize(st));
-    dxs.release();
     return BEVW_OK;
 }
 
@@ -242,7 +241,6 @@ static int build_pinhole_maps(hipStream_t st, const double K[9], const double D[
     hipLaunchKernelGGL(k_pinhole_map, dim3((w + 255) / 256, h), dim3(256), 0, st, p, dxs.as<double>(), w, h, d_map1, d_map2);
     BEVW_TRY(launch_check("k_pinhole_map"));
     HIP_TRY(hipStreamSynchronize(st));
-    dxs.release();
     return BEVW_OK;
 }
 
@@ -313,12 +311,10 @@ static int remapper_alloc(int device, int sw, int sh, int dw, int dh, bevw_remap
 static int remap_launch(hipStream_t st, const uint8_t *d_src, int sw, int sh, const int16_t *m1, const uint16_t *m2,
                         int dw, int dh, int batch, uint8_t *d_dst, int ties_even = 0)
 {
-    for (int b0 = 0; b0 < batch; b0 += 65535) {
-        const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
-        dim3 grid((dw + 255) / 256, dh, nb);
-        hipLaunchKernelGGL(k_remap_lut, grid, dim3(256), 0, st, d_src + (size_t)b0 * sw * sh * 3, sw, sh, m1, m2, dw, dh,
-                           d_dst + (size_t)b0 * dw * dh * 3, ties_even);
-    }
+    for_each_chunk(batch, [&](int b0, int nb) {
+        hipLaunchKernelGGL(k_remap_lut, dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, d_src + (size_t)b0 * sw * sh * 3, sw, sh, m1, m2,
+                           dw, dh, d_dst + (size_t)b0 * dw * dh * 3, ties_even);
+    });
     return launch_check("k_remap_lut");
 }
 
@@ -406,32 +402,30 @@ int bevw_device_copy_rate(int device, size_t nbytes, int reps, int streaming, do
     if (!gb_per_s_moved || reps <= 0 || nbytes < 16) return fail(BEVW_E_INVALID, "bad argument");
     BEVW_TRY(use_device(device));
     DevBuf a, b;
-    int s = a.reserve(nbytes);
-    if (s == BEVW_OK) s = b.reserve(nbytes);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (s == BEVW_OK && (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)) s = fail(BEVW_E_HIP, "event creation failed");
-    if (s == BEVW_OK && hipMemset(a.p, 0x5a, nbytes) != hipSuccess) s = fail(BEVW_E_HIP, "memset failed");
-    if (s == BEVW_OK) {
-        const size_t n = nbytes / 16;
-        const dim3 grid(256 * 32), block(256);
-        auto launch = [&] {
-            if (streaming) hipLaunchKernelGGL(k_copy16<1>, grid, block, 0, nullptr, a.as<copy_u32x4>(), b.as<copy_u32x4>(), n);
-            else hipLaunchKernelGGL(k_copy16<0>, grid, block, 0, nullptr, a.as<copy_u32x4>(), b.as<copy_u32x4>(), n);
-        };
-        launch();   // warm-up
-        (void)hipEventRecord(e0, nullptr);
-        for (int r = 0; r < reps; ++r) launch();
-        (void)hipEventRecord(e1, nullptr);
-        s = launch_check("k_copy16");
-        float ms = 0.f;
-        if (s == BEVW_OK && (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || !(ms > 0.f)))
-            s = fail(BEVW_E_HIP, "timing the copy failed");
-        if (s == BEVW_OK) *gb_per_s_moved = 2.0 * (double)(n * 16) * reps / ((double)ms * 1e-3) / 1e9;   // bytes read + bytes written
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    a.release(); b.release();
-    return s;
+    BEVW_TRY(a.reserve(nbytes));
+    BEVW_TRY(b.reserve(nbytes));
+    struct Events {   // destroyed on every exit path
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    } ev;
+    if (hipEventCreate(&ev.e0) != hipSuccess || hipEventCreate(&ev.e1) != hipSuccess) return fail(BEVW_E_HIP, "event creation failed");
+    if (hipMemset(a.p, 0x5a, nbytes) != hipSuccess) return fail(BEVW_E_HIP, "memset failed");
+    const size_t n = nbytes / 16;
+    const dim3 grid(256 * 32), block(256);
+    auto launch = [&] {
+        if (streaming) hipLaunchKernelGGL(k_copy16<1>, grid, block, 0, nullptr, a.as<copy_u32x4>(), b.as<copy_u32x4>(), n);
+        else hipLaunchKernelGGL(k_copy16<0>, grid, block, 0, nullptr, a.as<copy_u32x4>(), b.as<copy_u32x4>(), n);
+    };
+    launch();   // warm-up
+    (void)hipEventRecord(ev.e0, nullptr);
+    for (int r = 0; r < reps; ++r) launch();
+    (void)hipEventRecord(ev.e1, nullptr);
+    BEVW_TRY(launch_check("k_copy16"));
+    float ms = 0.f;
+    if (hipEventSynchronize(ev.e1) != hipSuccess || hipEventElapsedTime(&ms, ev.e0, ev.e1) != hipSuccess || !(ms > 0.f))
+        return fail(BEVW_E_HIP, "timing the copy failed");
+    *gb_per_s_moved = 2.0 * (double)(n * 16) * reps / ((double)ms * 1e-3) / 1e9;   // bytes read + bytes written
+    return BEVW_OK;
 }
 
 // ---- remapper -------------------------------------------------------------------------------------------------
@@ -591,23 +585,17 @@ int bevw_warp_perspective_u8c3(int device, const uint8_t *src, int src_w, int sr
     invert3x3(H, Minv.m);
     DevBuf in, out;
     const size_t nin = (size_t)batch * src_w * src_h * 3, nout = (size_t)batch * dst_w * dst_h * 3;
-    int s = in.reserve(nin);
-    if (s == BEVW_OK) s = out.reserve(nout);
-    if (s == BEVW_OK && hipMemcpy(in.p, src, nin, hipMemcpyHostToDevice) != hipSuccess) s = fail(BEVW_E_HIP, "H2D failed");
-    if (s == BEVW_OK) {
-        for (int b0 = 0; b0 < batch; b0 += 65535) {
-            const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
-            dim3 grid((dst_w + 255) / 256, dst_h, nb);
-            hipLaunchKernelGGL(k_warp_perspective, grid, dim3(256), 0, 0, in.as<uint8_t>() + (size_t)b0 * src_w * src_h * 3,
-                               src_w, src_h, Minv, persp_block_width(dst_w, dst_h), dst_w, dst_h,
-                               out.as<uint8_t>() + (size_t)b0 * dst_w * dst_h * 3, g_compat[BEVW_COMPAT_WARP].load());
-        }
-        s = launch_check("k_warp_perspective");
-    }
-    if (s == BEVW_OK && hipMemcpy(dst, out.p, nout, hipMemcpyDeviceToHost) != hipSuccess) s = fail(BEVW_E_HIP, "D2H failed");
-    in.release();
-    out.release();
-    return s;
+    BEVW_TRY(in.reserve(nin));
+    BEVW_TRY(out.reserve(nout));
+    if (hipMemcpy(in.p, src, nin, hipMemcpyHostToDevice) != hipSuccess) return fail(BEVW_E_HIP, "H2D failed");
+    for_each_chunk(batch, [&](int b0, int nb) {
+        hipLaunchKernelGGL(k_warp_perspective, dim3((dst_w + 255) / 256, dst_h, nb), dim3(256), 0, 0,
+                           in.as<uint8_t>() + (size_t)b0 * src_w * src_h * 3, src_w, src_h, Minv, persp_block_width(dst_w, dst_h), dst_w,
+                           dst_h, out.as<uint8_t>() + (size_t)b0 * dst_w * dst_h * 3, g_compat[BEVW_COMPAT_WARP].load());
+    });
+    BEVW_TRY(launch_check("k_warp_perspective"));
+    if (hipMemcpy(dst, out.p, nout, hipMemcpyDeviceToHost) != hipSuccess) return fail(BEVW_E_HIP, "D2H failed");
+    return BEVW_OK;
 }
 
 }  // extern "C"
@@ -621,17 +609,14 @@ int bevw_translate_u8c3(int device, const uint8_t *src, int width, int height, i
     BEVW_TRY(use_device(device));
     const size_t n = (size_t)batch * width * height * 3;
     DevBuf d_src, d_dst;
-    int s = d_src.reserve(n);
-    if (s == BEVW_OK) s = d_dst.reserve(n);
-    if (s == BEVW_OK && hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) s = fail(BEVW_E_HIP, "H2D copy failed");
-    if (s == BEVW_OK) {
-        hipLaunchKernelGGL(k_translate, dim3((width + 255) / 256, height, batch), dim3(256), 0, nullptr, d_src.as<uint8_t>(), width,
-                           height, shift_x, shift_y, d_dst.as<uint8_t>());
-        s = launch_check("k_translate");
-    }
-    if (s == BEVW_OK && hipMemcpy(dst, d_dst.p, n, hipMemcpyDeviceToHost) != hipSuccess) s = fail(BEVW_E_HIP, "D2H copy failed");
-    d_src.release(); d_dst.release();
-    return s;
+    BEVW_TRY(d_src.reserve(n));
+    BEVW_TRY(d_dst.reserve(n));
+    if (hipMemcpy(d_src.p, src, n, hipMemcpyHostToDevice) != hipSuccess) return fail(BEVW_E_HIP, "H2D copy failed");
+    hipLaunchKernelGGL(k_translate, dim3((width + 255) / 256, height, batch), dim3(256), 0, nullptr, d_src.as<uint8_t>(), width,
+                       height, shift_x, shift_y, d_dst.as<uint8_t>());
+    BEVW_TRY(launch_check("k_translate"));
+    if (hipMemcpy(dst, d_dst.p, n, hipMemcpyDeviceToHost) != hipSuccess) return fail(BEVW_E_HIP, "D2H copy failed");
+    return BEVW_OK;
 }
 
 // cv2.resize's output size for dsize = (0, 0): (cvRound(w * fx), cvRound(h * fy))
@@ -655,17 +640,14 @@ int bevw_resize_linear_u8c3(int device, const uint8_t *src, int src_w, int src_h
     BEVW_TRY(use_device(device));
     const size_t nin = (size_t)batch * src_w * src_h * 3, nout = (size_t)batch * ds[0] * ds[1] * 3;
     DevBuf d_src, d_dst;
-    int s = d_src.reserve(nin);
-    if (s == BEVW_OK) s = d_dst.reserve(nout);
-    if (s == BEVW_OK && hipMemcpy(d_src.p, src, nin, hipMemcpyHostToDevice) != hipSuccess) s = fail(BEVW_E_HIP, "H2D copy failed");
-    if (s == BEVW_OK) {
-        hipLaunchKernelGGL(k_resize_linear, dim3((ds[0] + 255) / 256, ds[1], batch), dim3(256), 0, nullptr, d_src.as<uint8_t>(), src_w,
-                           src_h, 1.0 / fx, 1.0 / fy, d_dst.as<uint8_t>(), ds[0], ds[1]);
-        s = launch_check("k_resize_linear");
-    }
-    if (s == BEVW_OK && hipMemcpy(dst, d_dst.p, nout, hipMemcpyDeviceToHost) != hipSuccess) s = fail(BEVW_E_HIP, "D2H copy failed");
-    d_src.release(); d_dst.release();
-    return s;
+    BEVW_TRY(d_src.reserve(nin));
+    BEVW_TRY(d_dst.reserve(nout));
+    if (hipMemcpy(d_src.p, src, nin, hipMemcpyHostToDevice) != hipSuccess) return fail(BEVW_E_HIP, "H2D copy failed");
+    hipLaunchKernelGGL(k_resize_linear, dim3((ds[0] + 255) / 256, ds[1], batch), dim3(256), 0, nullptr, d_src.as<uint8_t>(), src_w,
+                       src_h, 1.0 / fx, 1.0 / fy, d_dst.as<uint8_t>(), ds[0], ds[1]);
+    BEVW_TRY(launch_check("k_resize_linear"));
+    if (hipMemcpy(dst, d_dst.p, nout, hipMemcpyDeviceToHost) != hipSuccess) return fail(BEVW_E_HIP, "D2H copy failed");
+    return BEVW_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -713,6 +695,23 @@ struct bevw_handle {
 hipStream_t bevw_internal_handle_stream(bevw_handle *h) { return h->stream; }
 int bevw_internal_handle_device(bevw_handle *h) { return h->cfg.device; }
 
+// the tables of the cameras a handle stitches, in frame-set order (a camera shard: its own cameras, the first one repeated)
+static StitchTables stitch_tables(const bevw_handle *h)
+{
+    StitchTables T;
+    const int ncams = h->shard_n ? h->shard_n : 4;
+    for (int i = 0; i < 4; ++i) {
+        const int c = h->shard_cams[i < ncams ? i : 0];
+        T.lut1[i] = h->lut1[c].as<int16_t>();
+        T.lut2[i] = h->lut2[c].as<uint16_t>();
+        T.mask[i] = h->mask[c].as<uint8_t>();
+    }
+    return T;
+}
+
+// the arithmetic of an analytic projection mode (k_stitch_analytic, k_stitch_perpixel), F32 a compile-time flag (with_flags)
+template <bool F32> using proj_real = std::conditional_t<F32, float, double>;
+
 static int fill_poly_device(hipStream_t st, const MaskGeometry &g, int cam, bool blend, uint8_t *d_mask, bool modern)
 {
     int pts[8][2];
@@ -737,30 +736,20 @@ static int ensure_stats(bevw_handle *h, int batch)
 static int stitch_per_pixel(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out)
 {
     const bevw_config &c = h->cfg;
-    StitchTables T;
-    for (int i = 0; i < 4; ++i) {
-        T.lut1[i] = h->lut1[i].as<int16_t>();
-        T.lut2[i] = h->lut2[i].as<uint16_t>();
-        T.mask[i] = h->mask[i].as<uint8_t>();
-    }
+    const StitchTables T = stitch_tables(h);
     const int *deltas = h->deltas.as<int>();
     const HsvTables *tab = h->hsv.as<HsvTables>();
     unsigned long long *chs = h->chsums.as<unsigned long long>();
-    for (int b0 = 0; b0 < batch; b0 += 65535) {
-        const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
-        dim3 grid((c.bev_width + 255) / 256, c.bev_height, nb), block(256);
+    for_each_chunk(batch, [&](int b0, int nb) {
+        const dim3 grid((c.bev_width + 255) / 256, c.bev_height, nb), block(256);
         const uint8_t *fr = d_frames + (size_t)b0 * 4 * c.frame_width * c.frame_height * 3;
         uint8_t *o = d_out + (size_t)b0 * c.bev_width * c.bev_height * 3;
-#define LAUNCH_PP(BL, BA)                                                                                         \
-        hipLaunchKernelGGL((k_stitch_pp<BL, BA>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height, T, \
-                           c.bev_width, c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car,              \
-                           chs ? chs + b0 * 3 : nullptr, o, h->compat[BEVW_COMPAT_REMAP])
-        if (c.blend && c.balance) LAUNCH_PP(true, true);
-        else if (c.blend) LAUNCH_PP(true, false);
-        else if (c.balance) LAUNCH_PP(false, true);
-        else LAUNCH_PP(false, false);
-#undef LAUNCH_PP
-    }
+        with_flags([&](auto bl, auto ba) {
+            hipLaunchKernelGGL((k_stitch_pp<bl, ba>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height, T, c.bev_width,
+                               c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car, chs ? chs + b0 * 3 : nullptr, o,
+                               h->compat[BEVW_COMPAT_REMAP]);
+        }, c.blend != 0, c.balance != 0);
+    });
     return launch_check("k_stitch_pp");
 }
 
@@ -815,12 +804,7 @@ static int stitch_analytic(bevw_handle *h, const uint8_t *d_frames, int batch, c
             n_left = h->aplan.n_slow;
         }
     }
-    StitchTables T;
-    for (int i = 0; i < 4; ++i) {
-        T.lut1[i] = h->lut1[i].as<int16_t>();
-        T.lut2[i] = h->lut2[i].as<uint16_t>();
-        T.mask[i] = h->mask[i].as<uint8_t>();
-    }
+    const StitchTables T = stitch_tables(h);
     const int *deltas = h->deltas.as<int>();
     const HsvTables *tab = h->hsv.as<HsvTables>();
     unsigned long long *chs = h->chsums.as<unsigned long long>();
@@ -828,42 +812,46 @@ static int stitch_analytic(bevw_handle *h, const uint8_t *d_frames, int batch, c
     // output pixel AND frame: bench.py's direct_stitch_analytic_perpixel_b64)
     static const int fpt_env = [] { const char *s = getenv("BEVW_ANALYTIC_FRAMES"); return s ? atoi(s) : 0; }();
     const int fpt = fpt_env >= 1 && fpt_env <= 1024 ? fpt_env : kAnalyticFrames;
-    const int per_launch = 65535 * fpt;
-    for (int b0 = 0; b0 < batch; b0 += per_launch) {
-        const int nb = batch - b0 < per_launch ? batch - b0 : per_launch;
-        dim3 grid((c.bev_width + 255) / 256, c.bev_height, (nb + fpt - 1) / fpt), block(256);
-        if (left_tiles) grid = dim3((unsigned)n_left, 1, (nb + fpt - 1) / fpt);
-        const int tiles_x = h->aplan.tiles_x;
+    const bool f32 = h->projection == BEVW_PROJ_ANALYTIC_F32;
+    const int tiles_x = h->aplan.tiles_x;
+    const dim3 block(256);
+    for_each_chunk(batch, [&](int b0, int nb) {
         const uint8_t *fr = d_frames + (size_t)b0 * 4 * c.frame_width * c.frame_height * 3;
         uint8_t *o = d_out + (size_t)b0 * c.bev_width * c.bev_height * 3;
         if (fpt == 1 && !c.balance && left_tiles == nullptr) {
             // one thread per pixel AND frame: the fused per-output-pixel kernel of its own (bevw_kernels.h: k_stitch_perpixel)
-            const dim3 g1((c.bev_width + 255) / 256, c.bev_height, nb);
-            if (h->projection == BEVW_PROJ_ANALYTIC_F32) {
-                if (c.blend) hipLaunchKernelGGL((k_stitch_perpixel<true, float>), g1, block, 0, h->stream, fr, c.frame_width, c.frame_height, h->arig, T, c.bev_width, c.bev_height, d_car, o);
-                else hipLaunchKernelGGL((k_stitch_perpixel<false, float>), g1, block, 0, h->stream, fr, c.frame_width, c.frame_height, h->arig, T, c.bev_width, c.bev_height, d_car, o);
-            } else {
-                if (c.blend) hipLaunchKernelGGL((k_stitch_perpixel<true, double>), g1, block, 0, h->stream, fr, c.frame_width, c.frame_height, h->arig, T, c.bev_width, c.bev_height, d_car, o);
-                else hipLaunchKernelGGL((k_stitch_perpixel<false, double>), g1, block, 0, h->stream, fr, c.frame_width, c.frame_height, h->arig, T, c.bev_width, c.bev_height, d_car, o);
-            }
-            continue;
+            const dim3 grid((c.bev_width + 255) / 256, c.bev_height, nb);
+            with_flags([&](auto bl, auto fl) {
+                hipLaunchKernelGGL((k_stitch_perpixel<bl, proj_real<fl>>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height,
+                                   h->arig, T, c.bev_width, c.bev_height, d_car, o);
+            }, c.blend != 0, f32);
+            return;
         }
-#define LAUNCH_AN(BL, BA)                                                                                                   \
-        do {                                                                                                                 \
-            if (h->projection == BEVW_PROJ_ANALYTIC_F32)                                                                     \
-                hipLaunchKernelGGL((k_stitch_analytic<BL, BA, float>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height, h->arig, T, \
-                                   c.bev_width, c.bev_height, nb, deltas ? deltas + b0 * 4 : nullptr, tab, d_car, chs ? chs + b0 * 3 : nullptr, o, left_tiles, tiles_x, fpt); \
-            else                                                                                                             \
-                hipLaunchKernelGGL((k_stitch_analytic<BL, BA, double>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height, h->arig, T, \
-                                   c.bev_width, c.bev_height, nb, deltas ? deltas + b0 * 4 : nullptr, tab, d_car, chs ? chs + b0 * 3 : nullptr, o, left_tiles, tiles_x, fpt); \
-        } while (0)
-        if (c.blend && c.balance) LAUNCH_AN(true, true);
-        else if (c.blend) LAUNCH_AN(true, false);
-        else if (c.balance) LAUNCH_AN(false, true);
-        else LAUNCH_AN(false, false);
-#undef LAUNCH_AN
-    }
+        const unsigned z = (nb + fpt - 1) / fpt;
+        const dim3 grid = left_tiles ? dim3((unsigned)n_left, 1, z) : dim3((c.bev_width + 255) / 256, c.bev_height, z);
+        with_flags([&](auto bl, auto ba, auto fl) {
+            hipLaunchKernelGGL((k_stitch_analytic<bl, ba, proj_real<fl>>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height,
+                               h->arig, T, c.bev_width, c.bev_height, nb, deltas ? deltas + b0 * 4 : nullptr, tab, d_car,
+                               chs ? chs + b0 * 3 : nullptr, o, left_tiles, tiles_x, fpt);
+        }, c.blend != 0, c.balance != 0, f32);
+    }, 65535 * fpt);
     return launch_check("k_stitch_analytic");
+}
+
+// k_vsum over `nframes` frames on `st`; returns its blocks per frame.  part_stride > 0: every block stores its partial sum, part_stride entries
+// per frame; 0: the blocks of a frame add into its one entry (zeroed by the caller)
+static int vsum_launch(hipStream_t st, const uint8_t *d_frames, int nframes, size_t frame_bytes, unsigned long long *d_vsums, int part_stride)
+{
+    const int vec_ok = (frame_bytes % 4 == 0 && ((uintptr_t)d_frames & 3u) == 0) ? 1 : 0;   // k_vsum's 12-byte loads
+    int bpf = 2048 / (nframes > 0 ? nframes : 1);
+    if (bpf < 8) bpf = 8;
+    if (bpf > 256) bpf = 256;
+    const size_t per_frame = part_stride > 0 ? (size_t)part_stride : 1;
+    for_each_chunk(nframes, [&](int f0, int nf) {
+        hipLaunchKernelGGL(k_vsum, dim3(bpf, nf), dim3(256), 0, st, d_frames + (size_t)f0 * frame_bytes, frame_bytes, vec_ok,
+                           d_vsums + (size_t)f0 * per_frame, part_stride);
+    });
+    return bpf;
 }
 
 // luminance statistics of a batch of 4-camera sets -> deltas[batch][4].  d_vsums: kVsumParts entries per frame (ensure_stats): every block
@@ -871,17 +859,7 @@ static int stitch_analytic(bevw_handle *h, const uint8_t *d_frames, int batch, c
 // front of every slice's k_vsum cost 20 us of stream time, twice per config-4 step).
 static int luminance_stats(hipStream_t st, const uint8_t *d_frames, int nsets, int fw, int fh, unsigned long long *d_vsums, int *d_deltas)
 {
-    const size_t frame_bytes = (size_t)fw * fh * 3;
-    const int nframes = nsets * 4;
-    const int vec_ok = (frame_bytes % 4 == 0 && ((uintptr_t)d_frames & 3u) == 0) ? 1 : 0;   // k_vsum's 12-byte loads
-    int bpf = 2048 / (nframes > 0 ? nframes : 1);
-    if (bpf < 8) bpf = 8;
-    if (bpf > 256) bpf = 256;
-    for (int f0 = 0; f0 < nframes; f0 += 65535) {
-        const int nf = nframes - f0 < 65535 ? nframes - f0 : 65535;
-        hipLaunchKernelGGL(k_vsum, dim3(bpf, nf), dim3(256), 0, st, d_frames + (size_t)f0 * frame_bytes, frame_bytes, vec_ok,
-                           d_vsums + (size_t)f0 * kVsumParts, kVsumParts);
-    }
+    const int bpf = vsum_launch(st, d_frames, nsets * 4, (size_t)fw * fh * 3, d_vsums, kVsumParts);
     hipLaunchKernelGGL(k_lum_delta, dim3((nsets + 63) / 64), dim3(64), 0, st, d_vsums, (double)fw * (double)fh, nsets,
                        d_deltas, bpf, kVsumParts);
     return launch_check("k_vsum/k_lum_delta");
@@ -895,8 +873,8 @@ static int gain_pass(bevw_handle *h, hipStream_t st, const uint8_t *gain_in, con
 {
     const bevw_config &c = h->cfg;
     const size_t npx_true = (size_t)c.bev_width * c.bev_height, npx = (size_t)h->pitch_px * c.bev_height;
-    for (int k0 = b0; k0 < b0 + n; k0 += 65535) {
-        const int nb = b0 + n - k0 < 65535 ? b0 + n - k0 : 65535;
+    for_each_chunk(n, [&](int k, int nb) {
+        const int k0 = b0 + k;
         int nsum = 0;
         const uint32_t *ps = (from_plan && lut_ok) ? plan_sum_entries(h->plan, k0, nsum) : nullptr;
         if (lut_ok)
@@ -907,8 +885,33 @@ static int gain_pass(bevw_handle *h, hipStream_t st, const uint8_t *gain_in, con
             hipLaunchKernelGGL(k_gain, dim3(64, nb), dim3(256), 0, st, d_out + (size_t)k0 * npx * 3, npx,
                                h->chsums.as<unsigned long long>() + (size_t)k0 * 3, d_car, d_out + (size_t)k0 * npx * 3,
                                h->compat[BEVW_COMPAT_ADDWEIGHTED] ? 0 : 1);
-    }
+    });
     return launch_check("k_gain");
+}
+
+// color_balance + car (surroundBEV.py:43-55, 323-324) of `batch` images of npx pixels, in place on `st`: k_channel_sums into d_chsums
+// (zeroed by the caller), then the gains -- k_gain_lut when `lut` (dword-aligned images of a multiple of 4 pixels), else k_gain
+static int color_balance(hipStream_t st, uint8_t *d_img, size_t npx, int batch, unsigned long long *d_chsums, const uint8_t *d_car, bool lut, int f32)
+{
+    for_each_chunk(batch, [&](int b0, int nb) {
+        uint8_t *o = d_img + (size_t)b0 * npx * 3;
+        unsigned long long *chs = d_chsums + (size_t)b0 * 3;
+        hipLaunchKernelGGL(k_channel_sums, dim3(64, nb), dim3(256), 0, st, o, npx, chs);
+        if (lut) hipLaunchKernelGGL(k_gain_lut, dim3(xcd_frame_grid(32, (unsigned)nb)), dim3(256), 0, st, o, npx, chs, d_car, o, 32u, (uint32_t)nb, f32);
+        else hipLaunchKernelGGL(k_gain, dim3(64, nb), dim3(256), 0, st, o, npx, chs, d_car, o, f32);
+    });
+    return launch_check("k_channel_sums/k_gain");
+}
+
+// the car sprite as the gain pass reads it: the pass walks the image as a flat array, so a pitched handle's sprite needs the same row pitch
+static int gain_car(bevw_handle *h, const uint8_t *d_car, const uint8_t *&car)
+{
+    car = d_car;
+    if (!d_car || h->pitch_px == h->cfg.bev_width) return BEVW_OK;
+    BEVW_TRY(h->car_pitched.reserve((size_t)h->pitch_px * h->cfg.bev_height * 3));
+    BEVW_TRY(plan_pad_image(h->stream, d_car, h->cfg.bev_width, h->pitch_px, h->cfg.bev_height, h->car_pitched.as<uint8_t>()));
+    car = h->car_pitched.as<uint8_t>();
+    return BEVW_OK;
 }
 
 // blend + balance on the tile plan (BASELINE config 4), `parts` slices of the batch alternating over the handle's two streams.
@@ -923,7 +926,6 @@ static int gain_pass(bevw_handle *h, hipStream_t st, const uint8_t *gain_in, con
 static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out)
 {
     const bevw_config &c = h->cfg;
-    const bool pitched = h->pitch_px != c.bev_width;
     const size_t npx = (size_t)h->pitch_px * c.bev_height;
     const size_t set_bytes = (size_t)c.frame_width * c.frame_height * 12;
     BEVW_TRY(ensure_stats(h, batch));
@@ -954,12 +956,8 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
     uint8_t *gain_in = d_out;
     if (oop && npx % 4 == 0 && h->pre.reserve(npx * 3 * slots) == BEVW_OK) gain_in = h->pre.as<uint8_t>();
     const bool pre_ring = ring && gain_in != d_out;
-    const uint8_t *gain_car = d_car;
-    if (pitched && d_car) {   // the gain pass walks the image as a flat array: the sprite needs the same row pitch
-        BEVW_TRY(h->car_pitched.reserve(npx * 3));
-        BEVW_TRY(plan_pad_image(h->stream, d_car, c.bev_width, h->pitch_px, c.bev_height, h->car_pitched.as<uint8_t>()));
-        gain_car = h->car_pitched.as<uint8_t>();
-    }
+    const uint8_t *car = nullptr;
+    BEVW_TRY(gain_car(h, d_car, car));
     if (parts > 1) {
         HIP_TRY(hipEventRecord(h->ev_fork, h->stream));          // the caller's uploads (and the padded sprite) were enqueued on stream
         HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
@@ -984,7 +982,7 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
         const bool lut_ok = npx % 4 == 0;   // (odd image sizes: the byte-wise gain kernel, in place, from k_reduce_psums' sums)
         BEVW_TRY(plan_stitch(h->plan, st, fr, n, c.blend != 0, false, h->deltas.as<int>() + (size_t)b0 * 4, h->hsv.as<HsvTables>(), nullptr,
                              lut_ok ? nullptr : h->chsums.as<unsigned long long>() + (size_t)b0 * 3, pre, true, batch, b0, shifted));
-        BEVW_TRY(gain_pass(h, st, pre, gain_car, d_car, d_out, b0, n, lut_ok, true));
+        BEVW_TRY(gain_pass(h, st, pre, car, d_car, d_out, b0, n, lut_ok, true));
     }
     if (parts > 1) {   // everything the caller enqueues on the handle's stream afterwards sees the whole batch
         HIP_TRY(hipEventRecord(h->ev_join, h->stream2));
@@ -1022,13 +1020,9 @@ static int run_device(bevw_handle *h, const uint8_t *d_frames, int batch, const 
         BEVW_TRY(stitch_per_pixel(h, d_frames, batch, d_car, d_out));
     }
     if (c.balance) {
-        const uint8_t *gain_car = d_car;
-        if (pitched && d_car) {   // the gain pass walks the image as a flat array: the sprite needs the same row pitch
-            BEVW_TRY(h->car_pitched.reserve(npx * 3));
-            BEVW_TRY(plan_pad_image(h->stream, d_car, c.bev_width, h->pitch_px, c.bev_height, h->car_pitched.as<uint8_t>()));
-            gain_car = h->car_pitched.as<uint8_t>();
-        }
-        BEVW_TRY(gain_pass(h, h->stream, d_out, gain_car, d_car, d_out, 0, batch, npx % 4 == 0 && aligned4));
+        const uint8_t *car = nullptr;
+        BEVW_TRY(gain_car(h, d_car, car));
+        BEVW_TRY(gain_pass(h, h->stream, d_out, car, d_car, d_out, 0, batch, npx % 4 == 0 && aligned4));
     }
     return BEVW_OK;
 }
@@ -1128,10 +1122,9 @@ int bevw_build(bevw_handle *h)
         for (int c = 0; c < 4; ++c) BEVW_TRY(fill_poly_device(st, g, c, false, h->mask[c].as<uint8_t>(), h->compat[BEVW_COMPAT_FILLPOLY] != 0));
     } else {
         DevBuf fresh[4];
-        int s = BEVW_OK;
-        for (int c = 0; c < 4 && s == BEVW_OK; ++c) {
-            s = fresh[c].reserve(bpx);
-            if (s == BEVW_OK) s = fill_poly_device(st, g, c, true, fresh[c].as<uint8_t>(), h->compat[BEVW_COMPAT_FILLPOLY] != 0);
+        for (int c = 0; c < 4; ++c) {
+            BEVW_TRY(fresh[c].reserve(bpx));
+            BEVW_TRY(fill_poly_device(st, g, c, true, fresh[c].as<uint8_t>(), h->compat[BEVW_COMPAT_FILLPOLY] != 0));
         }
         // BlendMask.__init__ (:165-186): (own mask, other mask, own seam, other seam), two steps per camera
         struct Step { int other; const char *a0, *a1, *b0, *b1; };
@@ -1141,19 +1134,17 @@ int bevw_build(bevw_handle *h)
             {{BEVW_FRONT, "tL", "cTL", "lT", "cTL"}, {BEVW_BACK, "bL", "cBL", "lB", "cBL"}},    // left:  LF/FL, LB/BL
             {{BEVW_FRONT, "tR", "cTR", "rT", "cTR"}, {BEVW_BACK, "bR", "cBR", "rB", "cBR"}},    // right: RF/FR, RB/BR
         };
-        for (int c = 0; c < 4 && s == BEVW_OK; ++c) {
+        for (int c = 0; c < 4; ++c) {
             if (hipMemcpyAsync(h->mask[c].p, fresh[c].p, bpx, hipMemcpyDeviceToDevice, st) != hipSuccess)
-                s = fail(BEVW_E_HIP, "mask copy failed");
-            for (int k = 0; k < 2 && s == BEVW_OK; ++k) {
+                return fail(BEVW_E_HIP, "mask copy failed");
+            for (int k = 0; k < 2; ++k) {
                 const Step &sp = steps[c][k];
                 hipLaunchKernelGGL(k_blend_weights, dim3((bw + 255) / 256, bh), dim3(256), 0, st, h->mask[c].as<uint8_t>(),
                                    fresh[sp.other].as<uint8_t>(), bw, bh, g.seam(sp.a0, sp.a1), g.seam(sp.b0, sp.b1));
-                s = launch_check("k_blend_weights");
+                BEVW_TRY(launch_check("k_blend_weights"));
             }
         }
-        if (s == BEVW_OK && hipStreamSynchronize(st) != hipSuccess) s = fail(BEVW_E_HIP, "mask build failed");
-        for (int c = 0; c < 4; ++c) fresh[c].release();
-        BEVW_TRY(s);
+        if (hipStreamSynchronize(st) != hipSuccess) return fail(BEVW_E_HIP, "mask build failed");
     }
 
     // HSV divisor tables
@@ -1163,14 +1154,8 @@ int bevw_build(bevw_handle *h)
     HIP_TRY(hipStreamSynchronize(st));
 
     // contributor plan for the tile schedule
-    StitchTables T;
+    const StitchTables T = stitch_tables(h);
     const int ncams = h->shard_n ? h->shard_n : 4;
-    for (int i = 0; i < 4; ++i) {
-        const int c = h->shard_cams[i < ncams ? i : 0];
-        T.lut1[i] = h->lut1[c].as<int16_t>();
-        T.lut2[i] = h->lut2[c].as<uint16_t>();
-        T.mask[i] = h->mask[c].as<uint8_t>();
-    }
     // (seam block tiles: measured +0.7 % slower under the per-tile channel sums of the balance path, -1.4 .. -1.8 % without: sweeps.log)
     h->pitch_px = h->pitch_request == BEVW_PITCH_DENSE ? bw : (h->pitch_request == BEVW_PITCH_ALIGNED ? (bw + 63) / 64 * 64 : h->pitch_request);
     BEVW_TRY(plan_build(h->plan, st, T, cfg.frame_width, cfg.frame_height, bw, bh, ncams, h->pitch_px != bw ? h->pitch_px : 0, cfg.blend != 0));
@@ -1470,15 +1455,7 @@ int bevw_shard_vsums_device(bevw_handle *h, const void *d_frames, int batch, voi
     const size_t frame_bytes = (size_t)c.frame_width * c.frame_height * 3;
     const int nframes = batch * h->shard_n;
     HIP_TRY(hipMemsetAsync(d_vsums, 0, sizeof(unsigned long long) * (size_t)nframes, h->stream));
-    const int vec_ok = (frame_bytes % 4 == 0 && ((uintptr_t)d_frames & 3u) == 0) ? 1 : 0;
-    int bpf = 2048 / nframes;
-    if (bpf < 8) bpf = 8;
-    if (bpf > 256) bpf = 256;
-    for (int f0 = 0; f0 < nframes; f0 += 65535) {
-        const int nf = nframes - f0 < 65535 ? nframes - f0 : 65535;
-        hipLaunchKernelGGL(k_vsum, dim3(bpf, nf), dim3(256), 0, h->stream, (const uint8_t *)d_frames + (size_t)f0 * frame_bytes,
-                           frame_bytes, vec_ok, (unsigned long long *)d_vsums + f0);
-    }
+    vsum_launch(h->stream, (const uint8_t *)d_frames, nframes, frame_bytes, (unsigned long long *)d_vsums, 0);   // one entry per frame
     return launch_check("k_vsum");
 }
 
@@ -1634,8 +1611,7 @@ int bevw_shard_pack_device(bevw_handle *h, const void *d_full, int batch, void *
     const int rows = bx[3] - bx[1], row_bytes = (bx[2] - bx[0]) * 3;
     const bool dwords = c.bev_width % 4 == 0 && bx[0] % 4 == 0 && (bx[2] - bx[0]) % 4 == 0 &&
                         (((uintptr_t)d_full | (uintptr_t)d_packed) & 3u) == 0;
-    for (int b0 = 0; b0 < batch; b0 += 65535) {
-        const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
+    for_each_chunk(batch, [&](int b0, int nb) {
         const uint8_t *src = (const uint8_t *)d_full + (size_t)b0 * c.bev_width * c.bev_height * 3;
         uint8_t *dst = (uint8_t *)d_packed + (size_t)b0 * rows * row_bytes;
         if (dwords)
@@ -1644,7 +1620,7 @@ int bevw_shard_pack_device(bevw_handle *h, const void *d_full, int batch, void *
         else
             hipLaunchKernelGGL((k_pack_box<uint8_t>), dim3((row_bytes + 255) / 256, rows, nb), dim3(256), 0, h->stream, src,
                                c.bev_width, c.bev_height, bx[0], bx[1], bx[2], bx[3], dst);
-    }
+    });
     return launch_check("k_pack_box");
 }
 
@@ -1672,33 +1648,20 @@ int bevw_combine_device(bevw_handle *h, const void *const *d_parts, const int32_
     const size_t npx = (size_t)bw * bh;
     // balance: the car is added after the white balance (surroundBEV.py:321-324), so the sum goes out bare first
     const uint8_t *car_now = c.balance ? nullptr : (const uint8_t *)d_car;
-    for (int b0 = 0; b0 < batch; b0 += 65535) {
-        const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
+    for_each_chunk(batch, [&](int b0, int nb) {
         CombineParts pb = parts;
         for (int k = 0; k < nparts; ++k)
             pb.p[k] += (size_t)b0 * (size_t)(pb.box[k][2] - pb.box[k][0]) * (size_t)(pb.box[k][3] - pb.box[k][1]) * 3;
         uint8_t *o = (uint8_t *)d_out + (size_t)b0 * npx * 3;
         if (dwords) hipLaunchKernelGGL((k_combine<4>), dim3((bw / 4 + 255) / 256, bh, nb), dim3(256), 0, h->stream, pb, bw, bh, car_now, o);
         else hipLaunchKernelGGL((k_combine<1>), dim3((bw + 255) / 256, bh, nb), dim3(256), 0, h->stream, pb, bw, bh, car_now, o);
-    }
+    });
     BEVW_TRY(launch_check("k_combine"));
-    if (c.balance) {
-        BEVW_TRY(ensure_stats(h, batch));
-        HIP_TRY(hipMemsetAsync(h->chsums.p, 0, sizeof(unsigned long long) * 3 * (size_t)batch, h->stream));
-        for (int b0 = 0; b0 < batch; b0 += 65535) {
-            const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
-            uint8_t *o = (uint8_t *)d_out + (size_t)b0 * npx * 3;
-            unsigned long long *chs = h->chsums.as<unsigned long long>() + (size_t)b0 * 3;
-            hipLaunchKernelGGL(k_channel_sums, dim3(64, nb), dim3(256), 0, h->stream, o, npx, chs);
-            if (npx % 4 == 0 && dwords)
-                hipLaunchKernelGGL(k_gain_lut, dim3(xcd_frame_grid(32, (unsigned)nb)), dim3(256), 0, h->stream, o, npx, chs, (const uint8_t *)d_car, o,
-                                   32u, (uint32_t)nb, h->compat[BEVW_COMPAT_ADDWEIGHTED] ? 0 : 1);
-            else hipLaunchKernelGGL(k_gain, dim3(64, nb), dim3(256), 0, h->stream, o, npx, chs, (const uint8_t *)d_car, o,
-                                    h->compat[BEVW_COMPAT_ADDWEIGHTED] ? 0 : 1);
-        }
-        BEVW_TRY(launch_check("k_channel_sums/k_gain"));
-    }
-    return BEVW_OK;
+    if (!c.balance) return BEVW_OK;
+    BEVW_TRY(ensure_stats(h, batch));
+    HIP_TRY(hipMemsetAsync(h->chsums.p, 0, sizeof(unsigned long long) * 3 * (size_t)batch, h->stream));
+    return color_balance(h->stream, (uint8_t *)d_out, npx, batch, h->chsums.as<unsigned long long>(), (const uint8_t *)d_car,
+                         npx % 4 == 0 && dwords, h->compat[BEVW_COMPAT_ADDWEIGHTED] ? 0 : 1);
 }
 
 int bevw_apply_mask(bevw_handle *h, int cam, const uint8_t *img, int batch, uint8_t *out)
@@ -1711,11 +1674,10 @@ int bevw_apply_mask(bevw_handle *h, int cam, const uint8_t *img, int batch, uint
     BEVW_TRY(h->in.reserve(n));
     BEVW_TRY(h->out.reserve(n));
     HIP_TRY(hipMemcpyAsync(h->in.p, img, n, hipMemcpyHostToDevice, h->stream));
-    for (int b0 = 0; b0 < batch; b0 += 65535) {
-        const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
+    for_each_chunk(batch, [&](int b0, int nb) {
         hipLaunchKernelGGL(k_apply_mask, dim3(256, nb), dim3(256), 0, h->stream, h->in.as<uint8_t>() + (size_t)b0 * npx * 3,
                            h->mask[cam].as<uint8_t>(), npx, h->cfg.blend, h->out.as<uint8_t>() + (size_t)b0 * npx * 3);
-    }
+    });
     BEVW_TRY(launch_check("k_apply_mask"));
     HIP_TRY(hipMemcpyAsync(out, h->out.p, n, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1729,28 +1691,22 @@ int bevw_luminance_balance(int device, const uint8_t *frames, int batch, int wid
     BEVW_TRY(use_device(device));
     const size_t fpx = (size_t)width * height, n = (size_t)batch * 4 * fpx * 3;
     DevBuf in, o, vs, dl, tb;
-    int s = in.reserve(n);
-    if (s == BEVW_OK) s = o.reserve(n);
-    if (s == BEVW_OK) s = vs.reserve(sizeof(unsigned long long) * 4 * (size_t)batch * kVsumParts);
-    if (s == BEVW_OK) s = dl.reserve(sizeof(int) * 4 * (size_t)batch);
-    if (s == BEVW_OK) s = tb.reserve(sizeof(HsvTables));
+    BEVW_TRY(in.reserve(n));
+    BEVW_TRY(o.reserve(n));
+    BEVW_TRY(vs.reserve(sizeof(unsigned long long) * 4 * (size_t)batch * kVsumParts));
+    BEVW_TRY(dl.reserve(sizeof(int) * 4 * (size_t)batch));
+    BEVW_TRY(tb.reserve(sizeof(HsvTables)));
     HsvTables tab = make_hsv_tables();
-    if (s == BEVW_OK && (hipMemcpy(in.p, frames, n, hipMemcpyHostToDevice) != hipSuccess ||
-                         hipMemcpy(tb.p, &tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess))
-        s = fail(BEVW_E_HIP, "H2D failed");
-    if (s == BEVW_OK) s = luminance_stats(0, in.as<uint8_t>(), batch, width, height, vs.as<unsigned long long>(), dl.as<int>());
-    if (s == BEVW_OK) {
-        const int nframes = batch * 4;
-        for (int f0 = 0; f0 < nframes; f0 += 65535) {
-            const int nf = nframes - f0 < 65535 ? nframes - f0 : 65535;
-            hipLaunchKernelGGL(k_lum_shift, dim3(64, nf), dim3(256), 0, 0, in.as<uint8_t>() + (size_t)f0 * fpx * 3, fpx,
-                               dl.as<int>() + f0, tb.as<HsvTables>(), o.as<uint8_t>() + (size_t)f0 * fpx * 3);
-        }
-        s = launch_check("k_lum_shift");
-    }
-    if (s == BEVW_OK && hipMemcpy(out, o.p, n, hipMemcpyDeviceToHost) != hipSuccess) s = fail(BEVW_E_HIP, "D2H failed");
-    in.release(); o.release(); vs.release(); dl.release(); tb.release();
-    return s;
+    if (hipMemcpy(in.p, frames, n, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(tb.p, &tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(BEVW_E_HIP, "H2D failed");
+    BEVW_TRY(luminance_stats(0, in.as<uint8_t>(), batch, width, height, vs.as<unsigned long long>(), dl.as<int>()));
+    for_each_chunk(batch * 4, [&](int f0, int nf) {
+        hipLaunchKernelGGL(k_lum_shift, dim3(64, nf), dim3(256), 0, 0, in.as<uint8_t>() + (size_t)f0 * fpx * 3, fpx,
+                           dl.as<int>() + f0, tb.as<HsvTables>(), o.as<uint8_t>() + (size_t)f0 * fpx * 3);
+    });
+    BEVW_TRY(launch_check("k_lum_shift"));
+    if (hipMemcpy(out, o.p, n, hipMemcpyDeviceToHost) != hipSuccess) return fail(BEVW_E_HIP, "D2H failed");
+    return BEVW_OK;
 }
 
 int bevw_color_balance(int device, const uint8_t *images, int batch, int width, int height, uint8_t *out)
@@ -1760,25 +1716,14 @@ int bevw_color_balance(int device, const uint8_t *images, int batch, int width, 
     BEVW_TRY(use_device(device));
     const size_t npx = (size_t)width * height, n = (size_t)batch * npx * 3;
     DevBuf in, cs;
-    int s = in.reserve(n);
-    if (s == BEVW_OK) s = cs.reserve(sizeof(unsigned long long) * 3 * (size_t)batch);
-    if (s == BEVW_OK && hipMemcpy(in.p, images, n, hipMemcpyHostToDevice) != hipSuccess) s = fail(BEVW_E_HIP, "H2D failed");
-    if (s == BEVW_OK && hipMemset(cs.p, 0, sizeof(unsigned long long) * 3 * (size_t)batch) != hipSuccess)
-        s = fail(BEVW_E_HIP, "memset failed");
-    if (s == BEVW_OK) {
-        for (int b0 = 0; b0 < batch; b0 += 65535) {
-            const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
-            hipLaunchKernelGGL(k_channel_sums, dim3(64, nb), dim3(256), 0, 0, in.as<uint8_t>() + (size_t)b0 * npx * 3, npx,
-                               cs.as<unsigned long long>() + (size_t)b0 * 3);
-            hipLaunchKernelGGL(k_gain, dim3(64, nb), dim3(256), 0, 0, in.as<uint8_t>() + (size_t)b0 * npx * 3, npx,
-                               cs.as<unsigned long long>() + (size_t)b0 * 3, (const uint8_t *)nullptr,
-                               in.as<uint8_t>() + (size_t)b0 * npx * 3, g_compat[BEVW_COMPAT_ADDWEIGHTED].load() ? 0 : 1);
-        }
-        s = launch_check("k_channel_sums/k_gain");
-    }
-    if (s == BEVW_OK && hipMemcpy(out, in.p, n, hipMemcpyDeviceToHost) != hipSuccess) s = fail(BEVW_E_HIP, "D2H failed");
-    in.release(); cs.release();
-    return s;
+    BEVW_TRY(in.reserve(n));
+    BEVW_TRY(cs.reserve(sizeof(unsigned long long) * 3 * (size_t)batch));
+    if (hipMemcpy(in.p, images, n, hipMemcpyHostToDevice) != hipSuccess) return fail(BEVW_E_HIP, "H2D failed");
+    if (hipMemset(cs.p, 0, sizeof(unsigned long long) * 3 * (size_t)batch) != hipSuccess) return fail(BEVW_E_HIP, "memset failed");
+    BEVW_TRY(color_balance(nullptr, in.as<uint8_t>(), npx, batch, cs.as<unsigned long long>(), nullptr, false,
+                           g_compat[BEVW_COMPAT_ADDWEIGHTED].load() ? 0 : 1));
+    if (hipMemcpy(out, in.p, n, hipMemcpyDeviceToHost) != hipSuccess) return fail(BEVW_E_HIP, "D2H failed");
+    return BEVW_OK;
 }
 
 int bevw_sync(bevw_handle *h)

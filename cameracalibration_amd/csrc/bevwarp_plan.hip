@@ -53,8 +53,6 @@ static const PlanTuning &plan_tuning()
     return tune;
 }
 
-bool plan_units_enabled() { return plan_tuning().units != 0; }
-
 int plan_build(Plan &p, hipStream_t st, const StitchTables &T, int fw, int fh, int bw, int bh, int ncams, int out_pitch, bool blend)
 {
     static const UnitTuning unit_tune = unit_tuning_env();
