@@ -104,7 +104,7 @@ def _snapshot_config(blend=False, balance=False, device=0, schedule=_ffi.SCHED_A
 class _Engine:
     """Owns one bevw_handle (4 cameras + masks on the device)."""
 
-    def __init__(self, rig, blend, balance, device, schedule, output_pitch=0):
+    def __init__(self, rig, blend, balance, device, schedule, output_pitch=0, input_format=_ffi.INPUT_BGR):
         _ffi.require_device()
         self.cfg = _snapshot_config(blend, balance, device, schedule)
         h = C.c_void_p()
@@ -115,6 +115,8 @@ class _Engine:
                 check(lib().bevw_set_camera(self.h, i, ptr(f64(K, 9)), ptr(f64(D, 4)), ptr(f64(H, 9))))
             if output_pitch:
                 check(lib().bevw_set_output_pitch(self.h, int(output_pitch)))
+            if input_format != _ffi.INPUT_BGR:
+                check(lib().bevw_set_input_format(self.h, int(input_format)))
             check(lib().bevw_build(self.h))
         except Exception:
             self.close()
@@ -291,7 +293,7 @@ class BevGenerator:
     """
 
     def __init__(self, blend=args.BLEND_FLAG, balance=args.BALANCE_FLAG, *, rig=None, device=0,
-                 schedule=_ffi.SCHED_AUTO, projection='lut', output_pitch='auto'):
+                 schedule=_ffi.SCHED_AUTO, projection='lut', output_pitch='auto', input_format='bgr'):
         """blend / balance: as in the reference (surroundBEV.py:283).  Additive keywords: rig ({name: (K, D, H)} instead of the
         data directory), device, schedule, and projection -- 'lut' (default: the reference's table-driven path, bit-exact against
         the oracle) 'analytic' (inverse homography + fisheye model evaluated per frame and pixel in fp64, no tables; not the
@@ -299,7 +301,11 @@ class BevGenerator:
         output_pitch -- the row pitch of the DEVICE-side BEV images: 'auto' (default: 'aligned' wherever the tile plan with the table
         projection serves the handle, 'dense' otherwise), 'aligned' (rows of whole 64-byte sectors, cv::cuda::GpuMat style: see
         bevw_set_output_pitch in include/bevwarp.h), 'dense' (the reference's host layout) or a number of pixels.  Arrays returned to
-        the host are dense either way; only run_device() callers see the pitch (``out_pitch`` pixels per row of their output buffer)."""
+        the host are dense either way; only run_device() callers see the pitch (``out_pitch`` pixels per row of their output buffer).
+        input_format -- 'bgr' (default: camera frames [FH, FW, 3], as cv2.imread hands them over) or 'nv12' (what a video decoder hands
+        over: [FH*3//2, FW] uint8, the Y plane followed by the interleaved U / V plane).  An 'nv12' generator returns, byte for byte, what
+        a 'bgr' one returns for the frames cv2.cvtColor(f, cv2.COLOR_YUV2BGR_NV12) makes: the conversion is fused into the stitch (see
+        bevw_set_input_format in include/bevwarp.h).  Needs even FW and FH and the 'lut' projection; jpeg() / jpeg_stream() take BGR only."""
         self.init_args()
         if rig is None:
             self.cameras = [Camera('front'), Camera('back'), Camera('left'), Camera('right')]
@@ -314,13 +320,17 @@ class BevGenerator:
         pitch = {'dense': _ffi.PITCH_DENSE, 'aligned': _ffi.PITCH_ALIGNED}.get(output_pitch, output_pitch)
         if not isinstance(pitch, int):
             raise Exception("output_pitch should be auto/dense/aligned or a number of pixels")
+        formats = {'bgr': _ffi.INPUT_BGR, 'nv12': _ffi.INPUT_NV12}
+        if input_format not in formats:
+            raise Exception("input_format should be bgr/nv12")
+        self.input_format = input_format
         rig_kdh = [(c.camera_mat, c.dist_coeff, c.homography) for c in self.cameras]
         try:
-            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, pitch)
+            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, pitch, formats[input_format])
         except _ffi.BevwError:
             if not (auto and pitch != _ffi.PITCH_DENSE):
                 raise
-            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, _ffi.PITCH_DENSE)   # a rig the tile plan cannot serve
+            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, _ffi.PITCH_DENSE, formats[input_format])   # a rig the tile plan cannot serve
         self.out_pitch = int(lib().bevw_output_pitch(self._engine.h))   # pixels per row of run_device()'s output images
         modes = {'lut': _ffi.PROJ_LUT, 'analytic': _ffi.PROJ_ANALYTIC, 'analytic_f32': _ffi.PROJ_ANALYTIC_F32}
         if projection not in modes:
@@ -349,12 +359,26 @@ class BevGenerator:
         FOCAL_SCALE = args.FOCAL_SCALE
         SIZE_SCALE = args.SIZE_SCALE
 
+    def _frame_shape(self):
+        """Shape of one camera frame this generator takes: (FH, FW, 3) for 'bgr', (FH*3//2, FW) for 'nv12'."""
+        c = self._engine.cfg
+        if self.input_format == 'nv12':
+            return (c.frame_height * 3 // 2, c.frame_width)
+        return (c.frame_height, c.frame_width, 3)
+
     # ---- reference call ------------------------------------------------------------------------------------
     def __call__(self, front, back, left, right, car=None):
         c = self._engine.cfg
-        images = [_ffi.as_u8_image(i, "camera frame") for i in (front, back, left, right)]
+        if self.input_format == 'nv12':
+            images = [np.ascontiguousarray(i) for i in (front, back, left, right)]
+            for img in images:
+                if img.dtype != np.uint8 or img.shape != self._frame_shape():
+                    raise Exception("NV12 camera frame must be uint8 {} (FH*3//2, FW), got {} {}".format(self._frame_shape(), img.dtype,
+                                                                                                         img.shape))
+        else:
+            images = [_ffi.as_u8_image(i, "camera frame") for i in (front, back, left, right)]
         for img in images:
-            if img.shape[:2] != (c.frame_height, c.frame_width):
+            if img.shape[:2] != self._frame_shape()[:2]:
                 raise Exception("camera frame is {}x{}, FRAME is {}x{}".format(img.shape[1], img.shape[0],
                                                                                c.frame_width, c.frame_height))
         car_p = None
@@ -370,11 +394,13 @@ class BevGenerator:
 
     # ---- additive: batches ---------------------------------------------------------------------------------
     def batch(self, frames, car=None):
-        """frames uint8 [B, 4, FH, FW, 3] (front, back, left, right) -> uint8 [B, BH, BW, 3]."""
+        """frames uint8 [B, 4, FH, FW, 3] (front, back, left, right) -> uint8 [B, BH, BW, 3].  An 'nv12' generator takes
+        [B, 4, FH*3//2, FW]."""
         c = self._engine.cfg
         frames = np.ascontiguousarray(frames)
-        if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[1:] != (4, c.frame_height, c.frame_width, 3):
-            raise Exception("frames must be uint8 [B, 4, {}, {}, 3]".format(c.frame_height, c.frame_width))
+        want = (4,) + self._frame_shape()
+        if frames.dtype != np.uint8 or frames.ndim != len(want) + 1 or frames.shape[1:] != want:
+            raise Exception("frames must be uint8 [B, {}]".format(", ".join(str(n) for n in want)))
         car_p = None
         if car is not None:
             car = _ffi.as_u8_image(car, "car")
@@ -460,11 +486,16 @@ class BevGenerator:
                                  "data)".format(short, 4 * slot.batch))
         return files
 
+    def _jpeg_needs_bgr(self):
+        if self.input_format != 'bgr':
+            raise Exception("jpeg() / jpeg_stream() decode camera files to BGR: use a BevGenerator with input_format='bgr'")
+
     def jpeg(self, files, car=None, quality=95):
         """main.py:74-84 + surroundBEV.py:340 with the pixels resident in HBM: ``files`` is a sequence of frame sets, each the four camera FILES' bytes
         (front, back, left, right: what main.py hands to cv2.imread); the result is one complete ``.jpg`` file per set -- the bytes
         cv2.imwrite(path, bev(front, back, left, right, car)) would write (libjpeg at quality 95, 4:2:0).  Decode, stitch and
         encode all run on the GPU (imgcodecs.JpegCodec); only compressed bytes cross PCIe.  Truncated or corrupt camera files raise."""
+        self._jpeg_needs_bgr()
         sets = self._jpeg_sets(files)
         if getattr(self, "_jpeg_slots", None) is None:
             self._jpeg_slots = [BevGenerator._JpegSlot(self, self._imgcodecs())]
@@ -484,6 +515,7 @@ class BevGenerator:
         Throughput note: the pipeline keeps seven HIP streams busy and the runtime multiplexes them onto 4 hardware queues by default; the
         published figure is with 8 -- call ``cameracalibration_amd._ffi.prefer_hw_queues()`` before the first use of
         the package in the process (importing the package does not change the environment)."""
+        self._jpeg_needs_bgr()
         from concurrent.futures import ThreadPoolExecutor
 
         imgcodecs = self._imgcodecs()
@@ -548,8 +580,14 @@ class BevGenerator:
         """Bytes of ONE device-side BEV image as run_device() writes it: rows of ``out_pitch`` pixels (padding columns included)."""
         return self.out_pitch * self._engine.cfg.bev_height * 3
 
+    @property
+    def in_set_bytes(self) -> int:
+        """Bytes of ONE camera frame set as run_device() reads it: 4 frames of FH x FW x 3 ('bgr') or FH x FW x 3 / 2 ('nv12')."""
+        return 4 * int(np.prod(self._frame_shape()))
+
     def run_device(self, d_frames: int, batch: int, d_car, d_out: int, out_bytes: int = None) -> None:
-        """Asynchronous launch on device-resident buffers (raw pointers from DeviceBuffer).
+        """Asynchronous launch on device-resident buffers (raw pointers from DeviceBuffer).  ``d_frames`` holds ``batch`` frame sets of
+        ``in_set_bytes`` each (BGR or NV12 as the generator's input_format says).
 
         out_bytes: the size of the buffer behind ``d_out``.  The library sees raw pointers and cannot check it, so a handle whose
         device images are pitched (``out_pitch != BEV_WIDTH``: the 'auto' / 'aligned' layouts) REQUIRES it -- a caller that sized its

@@ -48,14 +48,27 @@ DEFAULT_D = np.array([[-0.03367245449576437], [0.015380779195912842], [-0.018654
 class Undistorter:
     """The map set of one (K, D, size, scales, offsets) on the device."""
 
-    def __init__(self, K, D, width, height, focalscale=1.0, sizescale=1.0, offset_h=0.0, offset_v=0.0, device=0):
+    def __init__(self, K, D, width, height, focalscale=1.0, sizescale=1.0, offset_h=0.0, offset_v=0.0, device=0, input_format='bgr'):
+        """input_format: 'bgr' (images [height, width, 3]) or 'nv12' ([height*3//2, width]: Y plane, then the interleaved U / V plane; the
+        result is what cv2.remap gives for cv2.cvtColor(img, cv2.COLOR_YUV2BGR_NV12) -- bevw_remapper_set_input_format in include/bevwarp.h)."""
+        self._r = None
+        formats = {'bgr': _ffi.INPUT_BGR, 'nv12': _ffi.INPUT_NV12}
+        if input_format not in formats:
+            raise Exception("input_format should be bgr/nv12")
         _ffi.require_device()
         self.width, self.height = int(width), int(height)
+        self.input_format = input_format
         r = C.c_void_p()
         check(lib().bevw_fisheye_remapper_create(device, self.width, self.height, ptr(f64(K, 9)), ptr(f64(D, 4)),
                                                  float(focalscale), float(sizescale), float(offset_h), float(offset_v),
                                                  C.byref(r)))
         self._r = r
+        if input_format != 'bgr':
+            try:
+                check(lib().bevw_remapper_set_input_format(r, formats[input_format]))
+            except Exception:
+                self.close()
+                raise
         dims = np.zeros(4, np.int32)
         check(lib().bevw_remapper_dims(r, ptr(dims)))
         self.out_w, self.out_h = int(dims[2]), int(dims[3])
@@ -67,13 +80,15 @@ class Undistorter:
         return m1, m2
 
     def __call__(self, images):
-        """uint8 [B, height, width, 3] (or one [height, width, 3]) -> undistorted images of the map size."""
+        """uint8 [B, height, width, 3] (or one [height, width, 3]) -> undistorted images of the map size.  'nv12': [B, height*3//2, width]
+        (or one [height*3//2, width])."""
         imgs = np.ascontiguousarray(images)
-        single = imgs.ndim == 3
+        frame = (self.height * 3 // 2, self.width) if self.input_format == 'nv12' else (self.height, self.width, 3)
+        single = imgs.ndim == len(frame)
         if single:
             imgs = imgs[np.newaxis]
-        if imgs.dtype != np.uint8 or imgs.shape[1:] != (self.height, self.width, 3):
-            raise Exception("images must be uint8 [B, {}, {}, 3]".format(self.height, self.width))
+        if imgs.dtype != np.uint8 or imgs.shape[1:] != frame:
+            raise Exception("images must be uint8 [B, {}]".format(", ".join(str(n) for n in frame)))
         out = np.empty((imgs.shape[0], self.out_h, self.out_w, 3), np.uint8)
         check(lib().bevw_remap(self._r, ptr(imgs), imgs.shape[0], ptr(out)))
         return out[0] if single else out

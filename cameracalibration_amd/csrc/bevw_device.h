@@ -229,6 +229,60 @@ __host__ __device__ __forceinline__ void luminance_shift_px(int &b, int &g, int 
     r = (int)((o >> 16) & 255u);
 }
 
+// ---- NV12 camera frames (bevw_set_input_format) ---------------------------------------------------------
+// An NV12 frame of fw x fh texels (both even) is fw * fh bytes of Y rows followed by fw * fh / 2 bytes of interleaved U / V rows at half
+// resolution: texel (x, y) has Y = Y[y][x], U = UV[y >> 1][x & ~1], V = UV[y >> 1][(x & ~1) + 1] -- chroma replicated over each 2 x 2 block.
+// Every kernel that reads camera frames converts a fetched NV12 texel to BGR with cv2.cvtColor(COLOR_YUV2BGR_NV12)'s arithmetic (OpenCV's
+// YUV420sp -> RGB: ITU-R BT.601 limited range, 20-bit fixed point), so interpolation and both balance steps see exactly cvtColor's texels:
+//   yy = max(0, Y - 16) * 1220542
+//   B = sat_u8((yy + (1 << 19) + 2116026 (U - 128)) >> 20)
+//   G = sat_u8((yy + (1 << 19) - 852492 (V - 128) - 409993 (U - 128)) >> 20)
+//   R = sat_u8((yy + (1 << 19) + 1673527 (V - 128)) >> 20)
+// The -128 / -16 offsets are folded into the addends (max(0, Y - 16) c == max(0, Y c - 16 c) for c > 0): every product is a byte times a
+// coefficient below 2^23, one v_mad_i32_i24, every clamp one v_med3_i32, and no sum leaves int32.
+// Checked exhaustively (all 2^24 Y, U, V) against the NumPy statement of the arithmetic: tests/native/nv12_exhaustive.cpp.
+constexpr int kNv12Y = 1220542, kNv12Y0 = -16 * kNv12Y;
+constexpr int kNv12BU = 2116026, kNv12B0 = (1 << 19) - 128 * kNv12BU;
+constexpr int kNv12GU = -409993, kNv12GV = -852492, kNv12G0 = (1 << 19) + 128 * (409993 + 852492);
+constexpr int kNv12RV = 1673527, kNv12R0 = (1 << 19) - 128 * kNv12RV;
+
+struct Nv12Chroma { int b, g, r; };   // the chroma addends of one U / V pair (shared by the texels of a 2 x 2 block)
+__host__ __device__ __forceinline__ Nv12Chroma nv12_chroma(uint32_t u, uint32_t v)
+{
+    return {(int)u * kNv12BU + kNv12B0, (int)v * kNv12GV + ((int)u * kNv12GU + kNv12G0), (int)v * kNv12RV + kNv12R0};
+}
+__host__ __device__ __forceinline__ uint32_t nv12_sat(int s)
+{
+    s >>= 20;   // arithmetic shift
+    return (uint32_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
+}
+// one texel: B | G << 8 | R << 16
+__host__ __device__ __forceinline__ uint32_t nv12_bgr(uint32_t y, const Nv12Chroma &c)
+{
+    const int yy0 = (int)y * kNv12Y + kNv12Y0, yy = yy0 > 0 ? yy0 : 0;
+    return nv12_sat(yy + c.b) | (nv12_sat(yy + c.g) << 8) | (nv12_sat(yy + c.r) << 16);
+}
+// texels x .. x + N - 1 of one row (x even) from the Y bytes and the U / V bytes that start at x (byte k of yb: Y of texel x + k; bytes
+// 2j, 2j + 1 of uvb: U, V of texels x + 2j, x + 2j + 1)
+template <int N>
+__host__ __device__ __forceinline__ void nv12_row_bgr(uint64_t yb, uint64_t uvb, uint32_t P[N])
+{
+#pragma unroll
+    for (int k = 0; k < N; k += 2) {
+        const Nv12Chroma c = nv12_chroma((uint32_t)(uvb >> (8 * k)) & 255u, (uint32_t)(uvb >> (8 * k + 8)) & 255u);
+        P[k] = nv12_bgr((uint32_t)(yb >> (8 * k)) & 255u, c);
+        if (k + 1 < N) P[k + 1] = nv12_bgr((uint32_t)(yb >> (8 * k + 8)) & 255u, c);
+    }
+}
+// texel (x, y), inside the frame, of the NV12 frame at `src` as B | G << 8 | R << 16 (the per-tap kernels)
+__device__ __forceinline__ uint32_t nv12_texel(const uint8_t *__restrict__ src, int fw, int fh, int x, int y)
+{
+    const uint8_t *uv = src + (size_t)fw * fh + (size_t)(y >> 1) * fw + (x & ~1);
+    return nv12_bgr(src[(size_t)y * fw + x], nv12_chroma(uv[0], uv[1]));
+}
+// bytes of one frame set: BGR 3 per texel, NV12 1.5
+__host__ __device__ __forceinline__ size_t frame_bytes_of(int fw, int fh, bool nv12) { return nv12 ? (size_t)fw * fh * 3 / 2 : (size_t)fw * fh * 3; }
+
 // Linear block id of a 1-D grid -> (frame, block inside the frame) such that XCD id % 8 owns WHOLE frames: the rows a kernel
 // writes are then completed inside one L2 (tools/store_pattern.hip: 4.7 TB/s with such a map, 2.9 TB/s when the blocks of a
 // frame are dealt round-robin to the XCDs).  Grid = blocks_per_frame * 8 * ceil(nframes / 8) blocks.
@@ -253,7 +307,8 @@ __device__ __forceinline__ int remap_round10(int S, int ties_even)
     if (ties_even && (S & 1023) == 512 && (r & 1)) --r;
     return r;
 }
-template <bool LUM>
+// NV12: `src` is an NV12 frame (nv12_texel), the texels are converted before the balance step
+template <bool LUM, bool NV12 = false>
 __device__ __forceinline__ void remap_u8c3_px(const uint8_t *__restrict__ src, int sw, int sh, int sx, int sy,
                                               unsigned code, int out[3], int delta, const HsvTables *hsv, int ties_even = 0)
 {
@@ -261,6 +316,26 @@ __device__ __forceinline__ void remap_u8c3_px(const uint8_t *__restrict__ src, i
     const int ax = kQOne - fx, ay = kQOne - fy;
     const int w00 = ax * ay, w01 = fx * ay, w10 = ax * fy, w11 = fx * fy;
     const unsigned xlim = sw > 1 ? sw - 1 : 0, ylim = sh > 1 ? sh - 1 : 0;
+    if constexpr (NV12) {
+        // one path for interior and border footprints: a tap outside the frame is 0 (BORDER_CONSTANT, after the balance step)
+        if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) { out[0] = out[1] = out[2] = 0; return; }
+        int t[4][3];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int x = sx + (q & 1), y = sy + (q >> 1);
+            if ((unsigned)x < (unsigned)sw && (unsigned)y < (unsigned)sh) {
+                const uint32_t p = nv12_texel(src, sw, sh, x, y);
+                t[q][0] = (int)(p & 255u); t[q][1] = (int)((p >> 8) & 255u); t[q][2] = (int)(p >> 16);
+                if (LUM) luminance_shift_px(t[q][0], t[q][1], t[q][2], delta, *hsv);
+            } else {
+                t[q][0] = t[q][1] = t[q][2] = 0;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            out[k] = remap_round10(t[0][k] * w00 + t[1][k] * w01 + t[2][k] * w10 + t[3][k] * w11, ties_even);
+        return;
+    }
     if ((unsigned)sx < xlim && (unsigned)sy < ylim) {
         const uint8_t *p0 = src + ((size_t)sy * sw + sx) * 3;
         const uint8_t *p1 = p0 + (size_t)sw * 3;

@@ -252,7 +252,8 @@ static __global__ void k_blend_weights(uint8_t *__restrict__ maskA, const uint8_
 // =============================================================================================================
 
 // cv2.remap(src, map1, map2, INTER_LINEAR) for a batch: one thread per destination pixel.
-// grid = (ceil(dw / 256), dh, batch)
+// grid = (ceil(dw / 256), dh, batch).  NV12: the sources are NV12 frames (bevw_remapper_set_input_format), converted per tap.
+template <bool NV12 = false>
 static __global__ void k_remap_lut(const uint8_t *__restrict__ src, int sw, int sh, const int16_t *__restrict__ map1,
                             const uint16_t *__restrict__ map2, int dw, int dh, uint8_t *__restrict__ dst, int ties_even = 0)
 {
@@ -260,11 +261,11 @@ static __global__ void k_remap_lut(const uint8_t *__restrict__ src, int sw, int 
     const int y = blockIdx.y;
     if (x >= dw) return;
     const size_t o = (size_t)y * dw + x;
-    const uint8_t *s = src + (size_t)blockIdx.z * sw * sh * 3;
+    const uint8_t *s = src + (NV12 ? (size_t)blockIdx.z * frame_bytes_of(sw, sh, true) : (size_t)blockIdx.z * sw * sh * 3);
     uint8_t *d = dst + ((size_t)blockIdx.z * dw * dh + o) * 3;
     const int sx = map1[o * 2], sy = map1[o * 2 + 1];
     int out[3];
-    remap_u8c3_px<false>(s, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even);
+    remap_u8c3_px<false, NV12>(s, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even);
     d[0] = (uint8_t)out[0]; d[1] = (uint8_t)out[1]; d[2] = (uint8_t)out[2];
 }
 
@@ -305,14 +306,29 @@ __device__ __forceinline__ unsigned vsum_piece(const VsumPiece &p)
 }
 // part_stride 0: the blocks of a frame add their sums atomically into sums[frame] (zeroed by the caller); > 0: block x of frame y stores
 // its sum at sums[y * part_stride + x] -- no atomics, no zeroing pass in front of the kernel; k_lum_delta adds the parts.
+// NV12: NV12 frames of fw texels per row (frame_bytes = fw * fh * 3 / 2), V of the converted texels: the blocks of a frame take its rows
+// round-robin, a lane a horizontal texel pair (two Y bytes and the U / V pair they share) per trip.
+template <bool NV12 = false>
 static __global__ void k_vsum(const uint8_t *__restrict__ frames, size_t frame_bytes, int vec_ok,
-                       unsigned long long *__restrict__ sums, int part_stride = 0)
+                       unsigned long long *__restrict__ sums, int part_stride = 0, int fw = 0)
 {
     const uint8_t *f = frames + (size_t)blockIdx.y * frame_bytes;
-    const size_t npieces = vec_ok ? frame_bytes / 12 : 0;
+    const size_t npieces = (vec_ok && !NV12) ? frame_bytes / 12 : 0;
     const VsumPiece *fp = reinterpret_cast<const VsumPiece *>(f);
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (size_t)gridDim.x * blockDim.x;
     unsigned acc = 0;
+    if (NV12) {
+        auto v = [](uint32_t t) { return max(t & 255u, max((t >> 8) & 255u, t >> 16)); };
+        const int fh = (int)(frame_bytes / 3 * 2 / (size_t)fw), npairs = fw / 2;
+        const uint8_t *uvp = f + (size_t)fw * fh;
+        for (int y = blockIdx.x; y < fh; y += gridDim.x) {
+            const uint8_t *yr = f + (size_t)y * fw, *cr = uvp + (size_t)(y >> 1) * fw;
+            for (int k = threadIdx.x; k < npairs; k += blockDim.x) {
+                const Nv12Chroma c = nv12_chroma(cr[2 * k], cr[2 * k + 1]);
+                acc += v(nv12_bgr(yr[2 * k], c)) + v(nv12_bgr(yr[2 * k + 1], c));
+            }
+        }
+    }
     size_t i = tid;
     for (; i + 3 * nthreads < npieces; i += 4 * nthreads) {
 #if BEVW_VSUM_NT   // (bevw_device.h: the frames pass once)
@@ -328,7 +344,7 @@ static __global__ void k_vsum(const uint8_t *__restrict__ frames, size_t frame_b
     }
     for (; i < npieces; i += nthreads) acc += vsum_piece(fp[i]);
     // texels not covered by whole pieces
-    for (size_t t = npieces * 4 + tid; t * 3 + 2 < frame_bytes; t += nthreads)
+    for (size_t t = npieces * 4 + tid; !NV12 && t * 3 + 2 < frame_bytes; t += nthreads)
         acc += max((unsigned)f[t * 3], max((unsigned)f[t * 3 + 1], (unsigned)f[t * 3 + 2]));
     __shared__ unsigned long long part[16];
     unsigned long long s = wave_sum_u64(acc);
@@ -384,7 +400,8 @@ static __global__ void k_lum_shift(const uint8_t *__restrict__ frames, size_t fr
 // sprite is added here; with balance the pre-gain value is stored and per-frame channel sums are accumulated
 // (integer, so the result does not depend on the order of the atomics).
 // grid = (ceil(bw / 256), bh, batch)
-template <bool BLEND, bool BAL>
+// NV12: NV12 frame sets (bevw_set_input_format), every tap converted where it is fetched (remap_u8c3_px)
+template <bool BLEND, bool BAL, bool NV12 = false>
 static __global__ void k_stitch_pp(const uint8_t *__restrict__ frames, int fw, int fh, StitchTables T, int bw, int bh,
                             const int *__restrict__ deltas, const HsvTables *__restrict__ tab,
                             const uint8_t *__restrict__ car, unsigned long long *__restrict__ chsums,
@@ -399,7 +416,7 @@ static __global__ void k_stitch_pp(const uint8_t *__restrict__ frames, int fw, i
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
     const int b = blockIdx.z;
-    const size_t frame_bytes = (size_t)fw * fh * 3;
+    const size_t frame_bytes = NV12 ? frame_bytes_of(fw, fh, true) : (size_t)fw * fh * 3;
     int acc[3] = {0, 0, 0};
     if (x < bw) {
         const size_t o = (size_t)y * bw + x;
@@ -410,7 +427,7 @@ static __global__ void k_stitch_pp(const uint8_t *__restrict__ frames, int fw, i
             const uint8_t *src = frames + ((size_t)b * 4 + c) * frame_bytes;
             const int sx = T.lut1[c][o * 2], sy = T.lut1[c][o * 2 + 1];
             int v[3];
-            remap_u8c3_px<BAL>(src, fw, fh, sx, sy, T.lut2[c][o] & (kQTab2 - 1), v, BAL ? deltas[b * 4 + c] : 0, &hsv, ties_even);
+            remap_u8c3_px<BAL, NV12>(src, fw, fh, sx, sy, T.lut2[c][o] & (kQTab2 - 1), v, BAL ? deltas[b * 4 + c] : 0, &hsv, ties_even);
             if (BLEND) {
                 const float wgt = blend_weight_f32(m);
                 v[0] = blend_mul(v[0], wgt); v[1] = blend_mul(v[1], wgt); v[2] = blend_mul(v[2], wgt);

@@ -34,6 +34,7 @@ constexpr int kPairLoadAux = BEVW_LOAD_AUX, kPairStoreAux = BEVW_STORE_AUX, kPai
 
 typedef uint32_t pair_u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t pair_u32x3 __attribute__((ext_vector_type(3)));
+typedef uint32_t pair_u32x2 __attribute__((ext_vector_type(2)));
 
 // 16 source bytes (texels 4g .. 4g+4 of one row) -> the four pair entries: A = pairs 0, 1, B = pairs 2, 3
 __host__ __device__ __forceinline__ void pair_convert(uint32_t dx, uint32_t dy, uint32_t dz, uint32_t dw, uint4 &A, uint4 &B)
@@ -46,6 +47,19 @@ __host__ __device__ __forceinline__ void pair_convert(uint32_t dx, uint32_t dy, 
     B.y = px_perm(dz, dz, 0x0c0c0300u);   //         8 11
     B.z = px_perm(dw, dz, 0x05020401u);   // pair 3: bytes 9 12 10 13
     B.w = px_perm(dw, dz, 0x0c0c0603u);   //         11 14
+}
+
+// NV12 frames (bevw_set_input_format): the same group from two 8-byte loads -- y0 y1 = Y bytes x .. x+7 of the texel row, c0 c1 = U / V
+// bytes x .. x+7 of its chroma row (x = the group's first texel, a multiple of 4) -- converted to BGR (nv12_row_bgr, bevw_device.h: texels
+// x .. x+4; texel x+4 takes U / V bytes x+4, x+5), packed into the 15 bytes pair_convert reads and turned into the same four pair entries.
+// `has` = the lane holds a group: a lane without one lands ZERO entries (its masked loads return zeros, and the conversion of Y = U = V = 0
+// is (B, G, R) = (0, 154, 0), not the BORDER_CONSTANT 0 a missing texel must be).
+__host__ __device__ __forceinline__ void pair_convert_nv12(uint32_t y0, uint32_t y1, uint32_t c0, uint32_t c1, bool has, uint4 &A, uint4 &B)
+{
+    uint32_t P[5], d0, d1, d2;
+    nv12_row_bgr<5>(y0 | ((uint64_t)y1 << 32), c0 | ((uint64_t)c1 << 32), P);
+    pack_pixels(P, d0, d1, d2);
+    pair_convert(has ? d0 : 0u, has ? d1 : 0u, has ? d2 : 0u, has ? P[4] : 0u, A, B);
 }
 
 // one pixel from its two pair entries: accumulators with the result byte in bits 16..23.  The y weights come pre-scaled by 64:

@@ -161,7 +161,11 @@ static __global__ void k_plan_touch(const uint2 *__restrict__ plan, int ntiles, 
 // sector, and the units then re-read that sparse layout.)  A block takes kLumTrips x 256 consecutive groups of one frame set (the 4 KB of
 // tables in LDS are paid once per block); the offsets and the texels of all its trips are requested before the first one is converted.
 // grid = xcd_frame_grid(ceil(ngroups / (256 kLumTrips)), batch); block = 256.
+// NV12: the raw frames are NV12 frame sets (bevw_set_input_format), `groups` holds two offsets per group (Y, U / V: unit_gsrc_nv12, in the
+// same order) and frame_bytes is an NV12 frame's; a lane loads 4 Y and 4 U / V bytes and converts its texels (nv12_row_bgr) before the shift.
+// The scratch is BGR either way.
 constexpr int kLumTrips = 8;
+template <bool NV12 = false>
 static __global__ void __launch_bounds__(256) k_lum_groups(const uint8_t *__restrict__ frames, uint8_t *__restrict__ scratch, size_t set_bytes,
                                                             size_t scratch_stride, uint32_t frame_bytes, const uint32_t *__restrict__ groups, int ngroups,
                                                             const int *__restrict__ deltas, const HsvTables *__restrict__ tab,
@@ -176,12 +180,27 @@ static __global__ void __launch_bounds__(256) k_lum_groups(const uint8_t *__rest
     const uint8_t *fin = frames + (size_t)frame * set_bytes;
     uint8_t *fout = scratch + (size_t)frame * scratch_stride;
     const int g0 = (int)blk * (kLumTrips * 256) + (int)threadIdx.x;
-    uint32_t goff[kLumTrips];
+    uint32_t goff[kLumTrips], coff[kLumTrips];
     AlignedU3 v[kLumTrips];
+    if (NV12) {
 #pragma unroll
-    for (int t = 0; t < kLumTrips; ++t) goff[t] = g0 + t * 256 < ngroups ? groups[g0 + t * 256] : 0u;
+        for (int t = 0; t < kLumTrips; ++t) {
+            const bool in = g0 + t * 256 < ngroups;
+            goff[t] = in ? groups[2 * (g0 + t * 256)] : 0u;
+            coff[t] = in ? groups[2 * (g0 + t * 256) + 1] : 0u;
+        }
 #pragma unroll
-    for (int t = 0; t < kLumTrips; ++t) v[t] = *reinterpret_cast<const AlignedU3 *>(fin + goff[t]);   // (past the list: group 0 once more, not stored)
+        for (int t = 0; t < kLumTrips; ++t) {   // v.x = Y bytes, v.y = U / V bytes of texels x .. x+3
+            v[t].x = *reinterpret_cast<const uint32_t *>(fin + goff[t]);
+            v[t].y = *reinterpret_cast<const uint32_t *>(fin + coff[t]);
+            v[t].z = 0u;
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < kLumTrips; ++t) goff[t] = g0 + t * 256 < ngroups ? groups[g0 + t * 256] : 0u;
+#pragma unroll
+        for (int t = 0; t < kLumTrips; ++t) v[t] = *reinterpret_cast<const AlignedU3 *>(fin + goff[t]);   // (past the list: group 0 once more, not stored)
+    }
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < kLumTrips; ++t) {
@@ -192,6 +211,7 @@ static __global__ void __launch_bounds__(256) k_lum_groups(const uint8_t *__rest
         const int delta = cam_delta[cam];
         // the 4 texels of the group as dwords (byte 3 is ignored), shifted, and packed back into the 12 bytes
         uint32_t P[4] = {w[0], __builtin_amdgcn_alignbyte(w[1], w[0], 3), __builtin_amdgcn_alignbyte(w[2], w[1], 2), w[2] >> 8};
+        if (NV12) nv12_row_bgr<4>(w[0], w[1], P);
 #pragma unroll
         for (int k = 0; k < 4; ++k) P[k] = luminance_shift_bgr(P[k], delta, hsv);
         uint32_t o[3];
@@ -244,13 +264,33 @@ __device__ __forceinline__ void bilinear_rows(uint2 r0, uint2 r1, uint32_t wx, u
     v[2] = (int)(__builtin_amdgcn_udot2(pr.v, w.v, 512u, false) >> 10);
 }
 
-template <bool BLEND, bool BAL>
+// NV12 frames: the plan's interior entries hold BGR frame-set offsets -> their footprint as sx | sy << 16 (once per entry, outside the frame
+// loop), and every valid entry is evaluated per tap (eval_entry)
+__device__ __forceinline__ void entry_to_taps(EntryRegs &e, int fw, uint32_t frame_bytes)
+{
+    if ((e.meta & kMetaValid) && !(e.meta & kMetaSlow)) {
+        const uint32_t t = e.off - ((e.meta >> 18) & 3u) * frame_bytes, row = (uint32_t)fw * 3;
+        e.off = (t % row / 3) | ((t / row) << 16);
+        e.meta |= kMetaSlow;
+    }
+}
+
+// NV12: `fb` is an NV12 frame set, frame_bytes an NV12 frame's, every valid entry on the per-tap path (entry_to_taps) with the conversion per
+// fetched texel (remap_u8c3_px); an entry without a contributor adds 0
+template <bool BLEND, bool BAL, bool NV12 = false>
 __device__ __forceinline__ void eval_entry(const uint8_t *__restrict__ fb, const EntryRegs &e, uint32_t row_bytes, int fw,
                                            int fh, uint32_t frame_bytes, bool tile_slow, const int *__restrict__ fdeltas,
                                            const HsvTables &hsv, int v[3])
 {
     const int cam = (e.meta >> 18) & 3;
-    if (tile_slow && (e.meta & kMetaSlow)) {
+    if (NV12) {
+        if (e.meta & kMetaValid) {
+            const int sx = (int)(int16_t)(e.off & 0xffffu), sy = (int)(int16_t)(e.off >> 16);
+            remap_u8c3_px<BAL, true>(fb + (size_t)cam * frame_bytes, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv);
+        } else {
+            v[0] = v[1] = v[2] = 0;
+        }
+    } else if (tile_slow && (e.meta & kMetaSlow)) {
         const int sx = (int)(int16_t)(e.off & 0xffffu), sy = (int)(int16_t)(e.off >> 16);
         remap_u8c3_px<BAL>(fb + (size_t)cam * frame_bytes, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv);
     } else if (!BAL) {
@@ -330,7 +370,8 @@ __device__ __forceinline__ bool plan_block_map(const PlanArgs &a, uint32_t id, u
 // The per-tap tile kernel.  grid: blocks of 4 waves = 4 base tiles of the list; one tile per wave.
 // LUM: luminance round trip per fetched texel (raw frames); SUMS: emit per-tile channel sums and leave the car to the gain pass
 // (two waves per SIMD: the 128-VGPR budget of rounds 1 - 3 spilled 0.5 - 1.2 KB per lane to scratch -- tools/kernel_resources.sh)
-template <bool BLEND, bool LUM, bool SUMS = LUM>
+// NV12: NV12 frame sets (bevw_set_input_format), every tap converted where it is fetched (eval_entry)
+template <bool BLEND, bool LUM, bool SUMS = LUM, bool NV12 = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) k_stitch_plan(PlanArgs a)
 {
     constexpr bool BAL = LUM;
@@ -353,7 +394,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
     const int x0 = (tx * kPlanLX + lane % kPlanLX) * 4, y = ty * kPlanLY + lane / kPlanLX;
     const bool inimg = x0 < a.bw && y < a.bh;
     const uint32_t frame_bytes = (uint32_t)a.fw * a.fh * 3, row_bytes = (uint32_t)a.fw * 3;
-    const size_t set_bytes = (size_t)frame_bytes * a.ncams, img_bytes = (size_t)a.pitch * a.bh * 3;
+    const uint32_t src_frame = NV12 ? frame_bytes / 2 : frame_bytes;   // bytes of one camera frame as the kernel reads it (NV12: fw even)
+    const size_t set_bytes = (size_t)src_frame * a.ncams, img_bytes = (size_t)a.pitch * a.bh * 3;
     const uint32_t ooff = ((uint32_t)y * a.pitch + x0) * 3;
 
     EntryRegs e0[4], e1[4];
@@ -361,6 +403,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
     for (int j = 0; j < 4; ++j) {
         e0[j] = decode_entry(a.plan[((size_t)tile * 8 + j) * 64 + lane], BLEND);
         e1[j] = decode_entry(second ? a.plan[((size_t)tile * 8 + 4 + j) * 64 + lane] : make_uint2(0, 0), BLEND);
+        if (NV12) { entry_to_taps(e0[j], a.fw, frame_bytes); entry_to_taps(e1[j], a.fw, frame_bytes); }
     }
     uint32_t car0 = 0, car1 = 0, car2 = 0;
     if (!SUMS && a.car != nullptr && inimg) {
@@ -381,13 +424,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                eval_entry<BLEND, BAL>(fb, e0[j], row_bytes, a.fw, a.fh, frame_bytes, tile_slow, fdeltas, hsv, px[j]);
+                eval_entry<BLEND, BAL, NV12>(fb, e0[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, px[j]);
             }
             if (second) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     int w[3];
-                    eval_entry<BLEND, BAL>(fb, e1[j], row_bytes, a.fw, a.fh, frame_bytes, tile_slow, fdeltas, hsv, w);
+                    eval_entry<BLEND, BAL, NV12>(fb, e1[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, w);
                     px[j][0] = min(255, px[j][0] + w[0]); px[j][1] = min(255, px[j][1] + w[1]); px[j][2] = min(255, px[j][2] + w[2]);
                 }
             }
@@ -539,6 +582,11 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
         }
         p.n_groups = (int)list.size();
         if ((e = plan_upload_list(list, &p.groups)) != hipSuccess) return e;
+        if (fh % 2 == 0) {   // the same groups in NV12 frame sets (k_lum_groups<true>)
+            std::vector<uint32_t> nv;
+            unit_gsrc_nv12(list, fw, fh, nv);
+            if ((e = plan_upload_list(nv, &p.groups_nv12)) != hipSuccess) return e;
+        }
         p.band_ok = true;
         groups_host.swap(list);
     }
@@ -564,6 +612,11 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
         if (!up.desc.empty()) {
             hdr.swap(hdr_un);
             if ((e = plan_upload_units(p, up)) != hipSuccess) return e;
+            if (fh % 2 == 0) {   // the units' group lists for NV12 frame sets (k_plan_units<.., true>)
+                std::vector<uint32_t> nv;
+                unit_gsrc_nv12(up.gsrc, fw, fh, nv);
+                if ((e = plan_upload_list(nv, &p.un_gsrc_nv12)) != hipSuccess) return e;
+            }
             std::vector<uint32_t> gc;
             if (p.band_ok && unit_gsrc_compact(up.gsrc, groups_host, gc) && unit_compact_stride(groups_host.size()) < (1ull << 31)) {
                 if ((e = plan_upload_list(gc, &p.un_gsrc_compact)) != hipSuccess) return e;
@@ -656,8 +709,11 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
     }
     // the units need 4-byte aligned frame sets (dword-addressed group loads) and are not combined with the per-tap luminance kernel
     const bool compact = d_scratch != nullptr;
+    // p.nv12: d_frames are NV12 frame sets -- the units read them through the NV12 group lists unless they read the compact scratch (BGR)
+    const bool nv12_units = p.nv12 && !compact;
     const bool use_units = !balance && tune.units && p.n_un_all > 0 && (((uintptr_t)d_frames) & 3u) == 0 &&
-                           (!compact || (p.un_gsrc_compact != nullptr && (((uintptr_t)d_scratch) & 3u) == 0));
+                           (!compact || (p.un_gsrc_compact != nullptr && (((uintptr_t)d_scratch) & 3u) == 0)) &&
+                           (!nv12_units || (p.un_gsrc_nv12 != nullptr && !sums));
     const bool with_sums = balance || sums;
     // channel-sum entries per frame: one per unit + one per base tile left to the per-tap kernel (or one per tile without units).  Every
     // entry has exactly one writer per frame (no atomics, round 5: 2.4 M atomic adds per config-4 step cost 58 us of the 600), and every writer
@@ -683,7 +739,13 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         if (sums) a.car = nullptr;   // the car is added behind the gains
         a.tile_list = static_cast<const uint32_t *>(p.list_un_all); a.nlist = p.n_un_all; a.ngroups = p.n_un_all;
         if (compact) { a.frames = d_scratch; a.set_stride = (uint32_t)p.compact_stride; a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_compact); }
-        with_flags([&](auto bl, auto sm) { hipLaunchKernelGGL((k_plan_units<bl, sm>), dim3(plan_grid(a)), block, 0, st, a); }, blend, sums);
+        if (nv12_units) {
+            a.set_stride = (uint32_t)(frame_bytes_of(p.fw, p.fh, true) * p.ncams);
+            a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_nv12);
+            with_flags([&](auto bl) { hipLaunchKernelGGL((k_units_nv12<bl>), dim3(plan_grid(a)), block, 0, st, a); }, blend);
+        } else {
+            with_flags([&](auto bl, auto sm) { hipLaunchKernelGGL((k_plan_units<bl, sm>), dim3(plan_grid(a)), block, 0, st, a); }, blend, sums);
+        }
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const int n_tap = use_units ? p.n_slow : p.ntiles;
@@ -694,8 +756,12 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         a.frames = d_frames; a.set_stride = 0;   // the per-tap kernel reads whole frames: RAW ones in the balance modes
         // LUM: luminance round trip per tap (the RAW frames of balance, or the tiles no unit owns beside the compact scratch); compact
         // without sums: camera-per-GPU shards, whose stitch rank balances the colours
-        with_flags([&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm>), dim3(plan_grid(a)), block, 0, st, a); },
-                   blend, balance || compact, balance || sums);
+        if (p.nv12)
+            with_flags([&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm, true>), dim3(plan_grid(a)), block, 0, st, a); },
+                       blend, balance || compact, balance || sums);
+        else
+            with_flags([&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm>), dim3(plan_grid(a)), block, 0, st, a); },
+                       blend, balance || compact, balance || sums);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (with_sums && d_chsums != nullptr) {   // (nullptr: the caller's gain pass adds the partial sums itself: plan_sum_entries)
@@ -730,12 +796,15 @@ static inline hipError_t plan_lum_band(const Plan &p, hipStream_t st, const uint
                                        const int *d_deltas, const HsvTables *d_tab)
 {
     if (p.n_groups == 0 || p.compact_stride == 0) return hipSuccess;
-    const size_t set_bytes = (size_t)p.fw * p.fh * 3 * p.ncams;
+    if (p.nv12 && !p.groups_nv12) return hipErrorInvalidValue;
+    const size_t frame_bytes = frame_bytes_of(p.fw, p.fh, p.nv12), set_bytes = frame_bytes * p.ncams;
     const unsigned bpf = (unsigned)(p.n_groups + 256 * kLumTrips - 1) / (256 * kLumTrips);
     for_each_chunk(batch, [&](int b0, int nb) {
-        hipLaunchKernelGGL(k_lum_groups, dim3(xcd_frame_grid(bpf, (unsigned)nb)), dim3(256), 0, st, d_frames + (size_t)b0 * set_bytes,
-                           d_scratch + (size_t)b0 * p.compact_stride, set_bytes, p.compact_stride, (uint32_t)p.fw * p.fh * 3,
-                           static_cast<const uint32_t *>(p.groups), p.n_groups, d_deltas + (size_t)b0 * 4, d_tab, bpf, (uint32_t)nb);
+        with_flags([&](auto nv) {
+            hipLaunchKernelGGL((k_lum_groups<nv>), dim3(xcd_frame_grid(bpf, (unsigned)nb)), dim3(256), 0, st, d_frames + (size_t)b0 * set_bytes,
+                               d_scratch + (size_t)b0 * p.compact_stride, set_bytes, p.compact_stride, (uint32_t)frame_bytes,
+                               static_cast<const uint32_t *>(nv ? p.groups_nv12 : p.groups), p.n_groups, d_deltas + (size_t)b0 * 4, d_tab, bpf, (uint32_t)nb);
+        }, p.nv12);
     });
     return hipGetLastError();
 }

@@ -34,6 +34,7 @@ struct Plan {
     int tiles_x = 0, tiles_y = 0, ntiles = 0;
     int ncams = 4;
     void *groups = nullptr;      // uint32[n_groups]: byte offsets (inside the frame set) of the sampled 4-texel groups
+    void *groups_nv12 = nullptr; // uint32[n_groups][2]: the same groups in an NV12 frame set (Y, U / V offsets; even frame heights)
     int n_groups = 0;
     bool band_ok = false;        // the sampled-group list exists (balance schedule 1)
     int max_contrib = 0;
@@ -43,6 +44,7 @@ struct Plan {
     // unit schedule (bevw_unit.h): k-d partition compiled on the host
     void *un_desc = nullptr, *un_entries = nullptr, *un_gsrc = nullptr;
     void *un_gsrc_compact = nullptr;         // the units' group lists for the compact scratch of the balance schedule (unit_gsrc_compact); nullptr: not usable
+    void *un_gsrc_nv12 = nullptr;            // the units' group lists for NV12 frame sets, two offsets per slot (unit_gsrc_nv12); nullptr: odd frame height
     size_t compact_stride = 0;               // bytes between the compact scratch copies of consecutive frame sets
     void *list_un_all = nullptr;             // every unit in partition order, class in bits 28..31
     int n_un_all = 0;
@@ -50,6 +52,8 @@ struct Plan {
     int n_unit_tiles = 0;                    // base tiles the units own
     size_t un_lines = 0, un_sectors = 0;     // request arithmetic of the partition (per frame)
     int un_skew = 0;
+    // the per-frame kernels read NV12 frame sets (bevw_set_input_format): set by the plan's owner after plan_build, which resets it
+    bool nv12 = false;
 };
 
 // compile LUT + masks into a plan (table kernels, unit compiler on the host).  out_pitch: pixels per output row when the caller's images

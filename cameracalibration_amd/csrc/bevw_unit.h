@@ -527,6 +527,21 @@ static inline bool unit_gsrc_compact(const std::vector<uint32_t> &gsrc, const st
     }
     return true;
 }
+// NV12 frame sets (bevw_set_input_format): a list of groups as BGR frame-set offsets (12 k for group k: a unit's group list, Plan::groups)
+// translated into the byte offsets of the group's Y bytes and U / V bytes inside an NV12 frame set (fw * fh * 3 / 2 bytes per camera):
+// out[2 i] = Y of texel (x, y), out[2 i + 1] = U of texel (x, y) in row y / 2 of the chroma plane.  The plan compiler is the same for
+// both formats; the NV12 instantiation of the unit kernel reads this list instead of the BGR one.  fw % 4 == 0, fh even.
+static inline void unit_gsrc_nv12(const std::vector<uint32_t> &gsrc, int fw, int fh, std::vector<uint32_t> &out)
+{
+    out.assign(gsrc.size() * 2, kPairNoGroup);
+    const uint32_t frame_bytes = (uint32_t)fw * fh * 3, row_bytes = (uint32_t)fw * 3, y_bytes = (uint32_t)fw * fh, nv_frame = y_bytes / 2 * 3;
+    for (size_t i = 0; i < gsrc.size(); ++i) {
+        if (gsrc[i] == kPairNoGroup) continue;
+        const uint32_t cam = gsrc[i] / frame_bytes, t = gsrc[i] % frame_bytes, y = t / row_bytes, x = t % row_bytes / 3;
+        out[2 * i] = cam * nv_frame + y * (uint32_t)fw + x;
+        out[2 * i + 1] = cam * nv_frame + y_bytes + (y >> 1) * (uint32_t)fw + x;
+    }
+}
 // bytes between the compact scratch copies of consecutive frame sets: the groups + the 4 bytes the last slot's load reaches beyond them,
 // rounded to whole 64-byte sectors
 static inline size_t unit_compact_stride(size_t ngroups) { return (ngroups * 12 + 16 + 63) / 64 * 64; }
@@ -724,11 +739,15 @@ __device__ __forceinline__ void unit_store_quad16(uint32_t d0, uint32_t d1, uint
     if (streaming) __builtin_amdgcn_raw_buffer_store_b128(v, ro, off16, 0, kPairStreamAux);
     else __builtin_amdgcn_raw_buffer_store_b128(v, ro, off16, 0, kPairStoreAux);
 }
-template <bool BLEND, bool SUMS, int NQ, int GR, int NCON, bool WIDE = false>
+// NV12: the frames are NV12 frame sets (bevw_set_input_format) and a.un_gsrc holds two offsets per group slot (unit_gsrc_nv12); the group
+// is fetched as two 8-byte loads and converted to BGR where it lands (pair_convert_nv12).  The patch, the plan entries, the interpolation and
+// the stores are the BGR kernel's.  (The balance schedule's units read the compact scratch, which is BGR: no NV12 variant with SUMS.)
+template <bool BLEND, bool SUMS, int NQ, int GR, int NCON, bool WIDE = false, bool NV12 = false>
 __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk, uint32_t unit, uint8_t *lds, uint4 *wave_sums = nullptr)
 {
     static_assert(NQ >= 1 && NQ <= kUnitMaxNQ && GR >= 1 && GR <= kUnitMaxGR && (NCON == 1 || NCON == 2), "unit class");
     static_assert(!(WIDE && SUMS), "wide plans carry no channel sums");
+    static_assert(!(NV12 && (SUMS || WIDE)), "NV12 units: table projection, raw frames");
     constexpr int kFPart = NCON == 2 ? 3 : 1;          // narrow part: the entries of each contributor (+ the blend weights)
     constexpr int kParts = kFPart + (WIDE ? NCON : 0); // uint4 per lane and quad slot in the plan
     constexpr bool kWeights = BLEND && NCON == 2;
@@ -746,7 +765,7 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
     constexpr int kPatch = GR * kUnitThreads * 32;              // one frame's pair entries
     constexpr bool DB = 2 * kPatch <= kUnitMaxGroups * 32;      // both halves fit the block's 32 KB
 
-    uint32_t i0[NQ][NCON][4], i1[NQ][NCON][4], wxa[NQ][NCON][4], wy[NQ][NCON][4], gs[GR], ooff_masked[NQ];
+    uint32_t i0[NQ][NCON][4], i1[NQ][NCON][4], wxa[NQ][NCON][4], wy[NQ][NCON][4], gs[GR], gc[GR], ooff_masked[NQ];   // NV12: gs = Y, gc = U / V offsets
     // 16-byte store format (unit_store_quad16): the lane's offset of its 16-byte piece (lanes q < 3 of whole lane quads; out of range otherwise);
     // bit j of part_bits = slot j of this lane stores 12 bytes after all (its lane quad is not whole); part_any: some lane of the wave does
     const bool store16 = BEVW_UNIT_STORE16 == 2 || (BEVW_UNIT_STORE16 == 1 && streaming);
@@ -831,7 +850,15 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
         return;
     }
 #pragma unroll
-    for (int r = 0; r < GR; ++r) gs[r] = once_load<BEVW_PLAN_NT>(a.un_gsrc + ((size_t)gs_off + r) * kUnitThreads + threadIdx.x);
+    for (int r = 0; r < GR; ++r) {
+        if (NV12) {
+            const pair_u32x2 g = once_load<BEVW_PLAN_NT>(reinterpret_cast<const pair_u32x2 *>(a.un_gsrc) + ((size_t)gs_off + r) * kUnitThreads + threadIdx.x);
+            gs[r] = g.x;
+            gc[r] = g.y;
+        } else {
+            gs[r] = once_load<BEVW_PLAN_NT>(a.un_gsrc + ((size_t)gs_off + r) * kUnitThreads + threadIdx.x);
+        }
+    }
 
     // (Dealing the frames of a chunk strided over the batch, or rotating the class lists per XCD, changes nothing: profiles/r03/placement.md)
     auto frame_of = [&](int b) { return min(b, b_end - 1); };   // past the chunk: the last frame once more
@@ -844,13 +871,26 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
         const uint8_t *src = a.frames + (size_t)frame_of(b) * set_bytes;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), 0, (uint32_t)set_bytes, kBufferWord3);
 #pragma unroll
-        for (int r = 0; r < GR; ++r) pf[ring][r] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)gs[r], 0, kPairLoadAux);
+        for (int r = 0; r < GR; ++r) {
+            if (NV12) {
+                // Y bytes x .. x+7 and U / V bytes x .. x+7 of the group (x .. x+4 / x+5 are used).  The last group of a frame's last chroma
+                // row reaches 4 bytes past the frame, and for the last camera past the frame set: those bytes are never used (texel x+4 lies
+                // outside the frame, so no unit pixel samples it: such footprints are frame-border tiles of the per-tap kernel), and the
+                // buffer's range check (num_records = the frame set's bytes) returns zeros for them instead of touching memory.
+                const pair_u32x2 yv = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)gs[r], 0, kPairLoadAux);
+                const pair_u32x2 cv = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)gc[r], 0, kPairLoadAux);
+                pf[ring][r] = pair_u32x4{yv.x, yv.y, cv.x, cv.y};
+            } else {
+                pf[ring][r] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)gs[r], 0, kPairLoadAux);
+            }
+        }
     };
     auto land = [&](int ring) {   // the groups of ring slot `ring` -> the patch half of that frame: 32 bytes per group slot
 #pragma unroll
         for (int r = 0; r < GR; ++r) {
             uint4 A, B;
-            pair_convert(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, A, B);
+            if (NV12) pair_convert_nv12(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, gs[r] != kPairNoGroup, A, B);
+            else pair_convert(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, A, B);
             uint4 *sp = reinterpret_cast<uint4 *>(lds + (DB ? (ring & 1) * kPatch : 0)) + (r * kUnitThreads + (int)threadIdx.x) * 2;
             sp[0] = A;
             sp[1] = B;
@@ -978,14 +1018,14 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
 
 // block -> (chunk, unit) of the list of ALL units in the partition's own (spatial) order, class in bits 28..31: neighbouring units run
 // at the same time on the same XCD, whatever their class, so the two halves of a sector that two units share meet in the L2
-template <bool BLEND, bool SUMS>
+template <bool BLEND, bool SUMS, bool NV12>
 __device__ __forceinline__ void plan_unit_any(const PlanArgs &a, uint32_t block_id, uint8_t *lds, uint4 *wave_sums)
 {
     uint32_t chunk, group;
     if (!plan_block_map(a, block_id, chunk, group)) return;
     if ((int)group >= a.nlist) return;
     const uint32_t e = __builtin_amdgcn_readfirstlane(a.tile_list[group]), unit = e & 0x0fffffffu;
-#define BEVW_UNIT_CASE(C) case C: plan_unit_run<BLEND, SUMS, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C]>(a, chunk, unit, lds, wave_sums); break;
+#define BEVW_UNIT_CASE(C) case C: plan_unit_run<BLEND, SUMS, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C], false, NV12>(a, chunk, unit, lds, wave_sums); break;
     switch (e >> 28) {
         BEVW_UNIT_CASE(0) BEVW_UNIT_CASE(1) BEVW_UNIT_CASE(2) BEVW_UNIT_CASE(3)
         // class 4 (two quads per lane, two contributors): with float blend weights (rounds 3 - 5) its blend variant needed 177 .. 197 VGPRs and
@@ -995,7 +1035,7 @@ __device__ __forceinline__ void plan_unit_any(const PlanArgs &a, uint32_t block_
 #if !BEVW_UNIT_NO_BIG   // (experiment builds without the (4, 4) class: every other class fits 128 VGPRs = 4 waves per SIMD; plans then need BEVW_UNIT_BIG=0)
         BEVW_UNIT_CASE(7)
 #endif
-        default: plan_unit_run<BLEND, SUMS, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6]>(a, chunk, unit, lds, wave_sums); break;
+        default: plan_unit_run<BLEND, SUMS, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6], false, NV12>(a, chunk, unit, lds, wave_sums); break;
     }
 #undef BEVW_UNIT_CASE
 }
@@ -1012,10 +1052,19 @@ __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_
 #ifdef BEVW_EXPERIMENT_TRACE_BEGIN
     BEVW_EXPERIMENT_TRACE_BEGIN();
 #endif
-    plan_unit_any<BLEND, SUMS>(a, blockIdx.x, patch, wave_sums);
+    plan_unit_any<BLEND, SUMS, false>(a, blockIdx.x, patch, wave_sums);
 #ifdef BEVW_EXPERIMENT_TRACE_END
     BEVW_EXPERIMENT_TRACE_END(a)
 #endif
+}
+
+// NV12 frame sets (bevw_set_input_format): the same launch over the NV12 instantiation of plan_unit_run -- no channel sums (the balance
+// schedule's units read the BGR compact scratch).  A kernel name of its own keeps k_plan_units the four BGR instantiations.
+template <bool BLEND>
+__global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_nv12(PlanArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
+    plan_unit_any<BLEND, false, true>(a, blockIdx.x, patch, nullptr);
 }
 
 // wide plans (analytic projection): every unit class in one launch, partition order, as plan_unit_any

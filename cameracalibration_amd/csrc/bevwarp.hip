@@ -267,6 +267,7 @@ struct bevw_remapper {
     Plan plan;            // single-image contributor plan (same kernels as the BEV stitch, ncams = 1)
     bool plan_ready = false;
     int ties_even = 0;    // BEVW_COMPAT_REMAP at creation: half-to-even ties -> the per-pixel kernel (the plan's arithmetic rounds half up)
+    int input_format = BEVW_INPUT_BGR;   // bevw_remapper_set_input_format
 };
 
 // cv2.remap as a 1-camera stitch: every destination pixel has exactly one contributor with mask 255.
@@ -308,12 +309,15 @@ static int remapper_alloc(int device, int sw, int sh, int dw, int dh, bevw_remap
     return BEVW_OK;
 }
 
+// nv12: the sources are NV12 frames (bevw_remapper_set_input_format)
 static int remap_launch(hipStream_t st, const uint8_t *d_src, int sw, int sh, const int16_t *m1, const uint16_t *m2,
-                        int dw, int dh, int batch, uint8_t *d_dst, int ties_even = 0)
+                        int dw, int dh, int batch, uint8_t *d_dst, int ties_even = 0, bool nv12 = false)
 {
     for_each_chunk(batch, [&](int b0, int nb) {
-        hipLaunchKernelGGL(k_remap_lut, dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, d_src + (size_t)b0 * sw * sh * 3, sw, sh, m1, m2,
-                           dw, dh, d_dst + (size_t)b0 * dw * dh * 3, ties_even);
+        with_flags([&](auto nv) {
+            hipLaunchKernelGGL((k_remap_lut<nv>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, d_src + (size_t)b0 * frame_bytes_of(sw, sh, nv),
+                               sw, sh, m1, m2, dw, dh, d_dst + (size_t)b0 * dw * dh * 3, ties_even);
+        }, nv12);
     });
     return launch_check("k_remap_lut");
 }
@@ -505,7 +509,20 @@ int bevw_remap_device(bevw_remapper *r, const void *d_src, int batch, void *d_ds
         return plan_stitch(r->plan, r->stream, (const uint8_t *)d_src, batch, false, false, nullptr, nullptr, nullptr, nullptr,
                            (uint8_t *)d_dst);
     return remap_launch(r->stream, (const uint8_t *)d_src, r->sw, r->sh, r->map1.as<int16_t>(), r->map2.as<uint16_t>(),
-                        r->dw, r->dh, batch, (uint8_t *)d_dst, r->ties_even);
+                        r->dw, r->dh, batch, (uint8_t *)d_dst, r->ties_even, r->input_format == BEVW_INPUT_NV12);
+}
+
+int bevw_remapper_set_input_format(bevw_remapper *r, int format)
+{
+    if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    if (format != BEVW_INPUT_BGR && format != BEVW_INPUT_NV12) return fail(BEVW_E_INVALID, "unknown input format %d", format);
+    if (format == BEVW_INPUT_NV12 && (r->sw % 2 || r->sh % 2))
+        return fail(BEVW_E_INVALID, "NV12 needs an even source width and height, got %dx%d", r->sw, r->sh);
+    BEVW_TRY(use_device(r->device));
+    HIP_TRY(hipStreamSynchronize(r->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
+    r->input_format = format;
+    r->plan.nv12 = format == BEVW_INPUT_NV12;
+    return BEVW_OK;
 }
 
 int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst)
@@ -513,7 +530,7 @@ int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst)
     if (!r || !src || !dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
-    const size_t nin = (size_t)batch * r->sw * r->sh * 3, nout = (size_t)batch * r->dw * r->dh * 3;
+    const size_t nin = (size_t)batch * frame_bytes_of(r->sw, r->sh, r->input_format == BEVW_INPUT_NV12), nout = (size_t)batch * r->dw * r->dh * 3;
     BEVW_TRY(r->in.reserve(nin));
     BEVW_TRY(r->out.reserve(nout));
     HIP_TRY(hipMemcpyAsync(r->in.p, src, nin, hipMemcpyHostToDevice, r->stream));
@@ -671,6 +688,9 @@ struct bevw_handle {
     Plan plan;
     int schedule_in_use = BEVW_SCHED_PER_PIXEL;
     int projection = BEVW_PROJ_LUT;   // bevw_set_projection
+    int input_format = BEVW_INPUT_BGR;   // bevw_set_input_format
+    bool nv12() const { return input_format == BEVW_INPUT_NV12; }
+    size_t set_bytes() const { return frame_bytes_of(cfg.frame_width, cfg.frame_height, nv12()) * 4; }   // one camera frame set as the handle reads it
     int compat[BEVW_COMPAT_KEYS] = {1, 1, 0, 0};   // bevw_set_compat values at bevw_build: a handle keeps the arithmetic it was built with
     int pitch_request = BEVW_PITCH_DENSE;   // bevw_set_output_pitch
     int pitch_px = 0;                 // pixels per row of the device-side BEV images (== bev_width unless a pitch was requested)
@@ -742,13 +762,13 @@ static int stitch_per_pixel(bevw_handle *h, const uint8_t *d_frames, int batch, 
     unsigned long long *chs = h->chsums.as<unsigned long long>();
     for_each_chunk(batch, [&](int b0, int nb) {
         const dim3 grid((c.bev_width + 255) / 256, c.bev_height, nb), block(256);
-        const uint8_t *fr = d_frames + (size_t)b0 * 4 * c.frame_width * c.frame_height * 3;
+        const uint8_t *fr = d_frames + (size_t)b0 * h->set_bytes();
         uint8_t *o = d_out + (size_t)b0 * c.bev_width * c.bev_height * 3;
-        with_flags([&](auto bl, auto ba) {
-            hipLaunchKernelGGL((k_stitch_pp<bl, ba>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height, T, c.bev_width,
+        with_flags([&](auto bl, auto ba, auto nv) {
+            hipLaunchKernelGGL((k_stitch_pp<bl, ba, nv>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height, T, c.bev_width,
                                c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car, chs ? chs + b0 * 3 : nullptr, o,
                                h->compat[BEVW_COMPAT_REMAP]);
-        }, c.blend != 0, c.balance != 0);
+        }, c.blend != 0, c.balance != 0, h->nv12());
     });
     return launch_check("k_stitch_pp");
 }
@@ -839,8 +859,9 @@ static int stitch_analytic(bevw_handle *h, const uint8_t *d_frames, int batch, c
 }
 
 // k_vsum over `nframes` frames on `st`; returns its blocks per frame.  part_stride > 0: every block stores its partial sum, part_stride entries
-// per frame; 0: the blocks of a frame add into its one entry (zeroed by the caller)
-static int vsum_launch(hipStream_t st, const uint8_t *d_frames, int nframes, size_t frame_bytes, unsigned long long *d_vsums, int part_stride)
+// per frame; 0: the blocks of a frame add into its one entry (zeroed by the caller).  nv12_width > 0: NV12 frames of that width
+static int vsum_launch(hipStream_t st, const uint8_t *d_frames, int nframes, size_t frame_bytes, unsigned long long *d_vsums, int part_stride,
+                       int nv12_width = 0)
 {
     const int vec_ok = (frame_bytes % 4 == 0 && ((uintptr_t)d_frames & 3u) == 0) ? 1 : 0;   // k_vsum's 12-byte loads
     int bpf = 2048 / (nframes > 0 ? nframes : 1);
@@ -848,8 +869,10 @@ static int vsum_launch(hipStream_t st, const uint8_t *d_frames, int nframes, siz
     if (bpf > 256) bpf = 256;
     const size_t per_frame = part_stride > 0 ? (size_t)part_stride : 1;
     for_each_chunk(nframes, [&](int f0, int nf) {
-        hipLaunchKernelGGL(k_vsum, dim3(bpf, nf), dim3(256), 0, st, d_frames + (size_t)f0 * frame_bytes, frame_bytes, vec_ok,
-                           d_vsums + (size_t)f0 * per_frame, part_stride);
+        with_flags([&](auto nv) {
+            hipLaunchKernelGGL((k_vsum<nv>), dim3(bpf, nf), dim3(256), 0, st, d_frames + (size_t)f0 * frame_bytes, frame_bytes, vec_ok,
+                               d_vsums + (size_t)f0 * per_frame, part_stride, nv12_width);
+        }, nv12_width > 0);
     });
     return bpf;
 }
@@ -857,9 +880,10 @@ static int vsum_launch(hipStream_t st, const uint8_t *d_frames, int nframes, siz
 // luminance statistics of a batch of 4-camera sets -> deltas[batch][4].  d_vsums: kVsumParts entries per frame (ensure_stats): every block
 // of k_vsum stores its partial sum, k_lum_delta adds them -- no atomics and no zeroing pass per step (round 5: the 4 KB hipMemsetAsync in
 // front of every slice's k_vsum cost 20 us of stream time, twice per config-4 step).
-static int luminance_stats(hipStream_t st, const uint8_t *d_frames, int nsets, int fw, int fh, unsigned long long *d_vsums, int *d_deltas)
+static int luminance_stats(hipStream_t st, const uint8_t *d_frames, int nsets, int fw, int fh, unsigned long long *d_vsums, int *d_deltas,
+                           bool nv12 = false)
 {
-    const int bpf = vsum_launch(st, d_frames, nsets * 4, (size_t)fw * fh * 3, d_vsums, kVsumParts);
+    const int bpf = vsum_launch(st, d_frames, nsets * 4, frame_bytes_of(fw, fh, nv12), d_vsums, kVsumParts, nv12 ? fw : 0);
     hipLaunchKernelGGL(k_lum_delta, dim3((nsets + 63) / 64), dim3(64), 0, st, d_vsums, (double)fw * (double)fh, nsets,
                        d_deltas, bpf, kVsumParts);
     return launch_check("k_vsum/k_lum_delta");
@@ -927,7 +951,7 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
 {
     const bevw_config &c = h->cfg;
     const size_t npx = (size_t)h->pitch_px * c.bev_height;
-    const size_t set_bytes = (size_t)c.frame_width * c.frame_height * 12;
+    const size_t set_bytes = h->set_bytes();
     BEVW_TRY(ensure_stats(h, batch));
     const size_t cstride = h->plan.compact_stride;   // the compact scratch: only the sampled texel groups of a frame set (bevw_unit.h: unit_gsrc_compact)
     static const int parts_env = [] { const char *s = getenv("BEVW_BAL_PARTS"); return s ? atoi(s) : 0; }();
@@ -970,7 +994,7 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
         // (Deriving the deltas inside k_lum_groups instead of by k_lum_delta, a kernel of its own in between, measured SLOWER: 1.669 against
         // 1.660 ms, profiles/r05/ab_call17...: 22 k blocks repeat four fp64 divisions.  The switch is gone.)
         BEVW_TRY(luminance_stats(st, fr, n, c.frame_width, c.frame_height, h->vsums.as<unsigned long long>() + (size_t)b0 * 4 * kVsumParts,
-                                 h->deltas.as<int>() + (size_t)b0 * 4));
+                                 h->deltas.as<int>() + (size_t)b0 * 4, h->nv12()));
         if (part == 0 && parts > 1 && skew_env) {   // the other stream's first slice starts when this one's V sums are done
             HIP_TRY(hipEventRecord(h->ev_skew, h->stream));
             HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_skew, 0));
@@ -1008,7 +1032,7 @@ static int run_device(bevw_handle *h, const uint8_t *d_frames, int batch, const 
     if (c.balance) {
         BEVW_TRY(ensure_stats(h, batch));
         BEVW_TRY(luminance_stats(h->stream, d_frames, batch, c.frame_width, c.frame_height,
-                                 h->vsums.as<unsigned long long>(), h->deltas.as<int>()));
+                                 h->vsums.as<unsigned long long>(), h->deltas.as<int>(), h->nv12()));
         HIP_TRY(hipMemsetAsync(h->chsums.p, 0, sizeof(unsigned long long) * 3 * (size_t)batch, h->stream));
     }
     if (h->projection != BEVW_PROJ_LUT) {
@@ -1159,6 +1183,7 @@ int bevw_build(bevw_handle *h)
     // (seam block tiles: measured +0.7 % slower under the per-tile channel sums of the balance path, -1.4 .. -1.8 % without: sweeps.log)
     h->pitch_px = h->pitch_request == BEVW_PITCH_DENSE ? bw : (h->pitch_request == BEVW_PITCH_ALIGNED ? (bw + 63) / 64 * 64 : h->pitch_request);
     BEVW_TRY(plan_build(h->plan, st, T, cfg.frame_width, cfg.frame_height, bw, bh, ncams, h->pitch_px != bw ? h->pitch_px : 0, cfg.blend != 0));
+    h->plan.nv12 = h->nv12();
     if (h->shard_n) {
         if (!h->plan.usable) return fail(BEVW_E_INVALID, "camera shard needs the tile plan: %d contributors on some pixel", h->plan.max_contrib);
         // bounding box of the owned masks, widened to multiples of 4 pixels in x so that packed rows stay dword aligned
@@ -1266,6 +1291,7 @@ int bevw_set_projection(bevw_handle *h, int mode)
     if (!h) return fail(BEVW_E_INVALID, "null handle");
     if (mode != BEVW_PROJ_LUT && mode != BEVW_PROJ_ANALYTIC && mode != BEVW_PROJ_ANALYTIC_F32) return fail(BEVW_E_INVALID, "unknown projection mode %d", mode);
     if (mode != BEVW_PROJ_LUT && h->shard_n) return fail(BEVW_E_INVALID, "analytic projection is not available on camera-shard handles");
+    if (mode != BEVW_PROJ_LUT && h->nv12()) return fail(BEVW_E_INVALID, "analytic projection is not available with NV12 input");
     h->projection = mode;
     return BEVW_OK;
 }
@@ -1304,6 +1330,31 @@ int bevw_output_pitch(bevw_handle *h)
     return h->pitch_px;
 }
 
+int bevw_set_input_format(bevw_handle *h, int format)
+{
+    if (!h) return fail(BEVW_E_INVALID, "null handle");
+    if (format != BEVW_INPUT_BGR && format != BEVW_INPUT_NV12) return fail(BEVW_E_INVALID, "unknown input format %d", format);
+    if (format == BEVW_INPUT_NV12) {
+        const bevw_config &c = h->cfg;
+        if (c.frame_width % 2 || c.frame_height % 2)
+            return fail(BEVW_E_INVALID, "NV12 needs an even frame width and height, got %dx%d", c.frame_width, c.frame_height);
+        if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "NV12 input is not available with the analytic projection");
+        if (h->shard_n) return fail(BEVW_E_INVALID, "NV12 input is not available on camera-shard handles");
+    }
+    BEVW_TRY(use_device(h->cfg.device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
+    if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
+    h->input_format = format;
+    h->plan.nv12 = h->nv12();
+    return BEVW_OK;
+}
+
+int bevw_input_format(bevw_handle *h)
+{
+    if (!h) return fail(BEVW_E_INVALID, "null handle");
+    return h->input_format;
+}
+
 // [batch * rows][pitch_px][3] on the device -> dense [batch * rows][bw][3] on the host (rows compacted inside the copy)
 static int download_images(bevw_handle *h, uint8_t *out, const void *d_src, size_t rows)
 {
@@ -1329,7 +1380,7 @@ int bevw_run(bevw_handle *h, const uint8_t *frames, int batch, const uint8_t *ca
     if (!frames || !out || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
     if (batch == 0) return BEVW_OK;
     const bevw_config &c = h->cfg;
-    const size_t nin = (size_t)batch * 4 * c.frame_width * c.frame_height * 3;
+    const size_t nin = (size_t)batch * h->set_bytes();
     const size_t bev = (size_t)c.bev_width * c.bev_height * 3, dbev = (size_t)h->pitch_px * c.bev_height * 3;
     BEVW_TRY(h->in.reserve(nin));
     BEVW_TRY(h->out.reserve(dbev * batch));
@@ -1354,7 +1405,7 @@ int bevw_run_cameras(bevw_handle *h, const uint8_t *front, const uint8_t *back, 
     if (h->shard_n) return fail(BEVW_E_INVALID, "handle is a camera shard: use bevw_shard_run_device + bevw_combine_device");
     if (!front || !back || !left || !right || !out) return fail(BEVW_E_INVALID, "bad argument");
     const bevw_config &c = h->cfg;
-    const size_t frame = (size_t)c.frame_width * c.frame_height * 3, bev = (size_t)c.bev_width * c.bev_height * 3;
+    const size_t frame = h->set_bytes() / 4, bev = (size_t)c.bev_width * c.bev_height * 3;
     BEVW_TRY(h->in.reserve(frame * 4));
     BEVW_TRY(h->out.reserve((size_t)h->pitch_px * c.bev_height * 3));
     const uint8_t *src[4] = {front, back, left, right};
@@ -1425,6 +1476,7 @@ int bevw_set_camera_shard(bevw_handle *h, const int32_t *cams, int ncams)
         if (cams[k] < 0 || cams[k] > 3) return fail(BEVW_E_INVALID, "name should be front/back/left/right");
         if (k && cams[k] <= cams[k - 1]) return fail(BEVW_E_INVALID, "shard cameras must be distinct and ascending");
     }
+    if (h->nv12()) return fail(BEVW_E_INVALID, "camera-shard handles take BGR frames only (NV12 input is set)");
     h->shard_n = ncams;
     for (int k = 0; k < 4; ++k) h->shard_cams[k] = k < ncams ? cams[k] : cams[0];
     h->built = false;

@@ -7,7 +7,7 @@ namespace bevw {
 
 void plan_release(Plan &p)
 {
-    void *ptrs[] = {p.un_desc, p.un_entries, p.un_gsrc, p.un_gsrc_compact, p.list_un_all, p.entries, p.hdr, p.groups, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
+    void *ptrs[] = {p.un_desc, p.un_entries, p.un_gsrc, p.un_gsrc_compact, p.un_gsrc_nv12, p.list_un_all, p.entries, p.hdr, p.groups, p.groups_nv12, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     p = Plan();

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define BEVW_ABI_VERSION 5
+#define BEVW_ABI_VERSION 6
 
 typedef enum bevw_status {
     BEVW_OK = 0,
@@ -158,6 +158,23 @@ int bevw_run_device(bevw_handle *h, const void *d_frames, int batch, const void 
 #define BEVW_PITCH_ALIGNED (-1)
 int bevw_set_output_pitch(bevw_handle *h, int pitch_pixels);
 int bevw_output_pitch(bevw_handle *h);   /* pixels per row of the handle's device images */
+/* Camera frames as NV12 (what a hardware video decoder hands over; the reference reads mp4 through cv2.VideoCapture, calibrate.py
+ * CalibMode): a Y plane of FH rows of FW bytes followed by one interleaved U / V plane of FH/2 rows of FW bytes (U first), dense --
+ * FW * FH * 3 / 2 bytes per frame, a host array of shape (FH*3//2, FW).  A frame set is the four frames back to back (front, back,
+ * left, right) and a batch frame sets back to back, as for BGR.  With BEVW_INPUT_NV12, bevw_run, bevw_run_device and bevw_run_cameras
+ * read NV12 frames and return, byte for byte, what the BGR handle returns for [cv2.cvtColor(f, cv2.COLOR_YUV2BGR_NV12) for f in frames]:
+ * every fetched texel is converted with OpenCV's YUV420sp arithmetic (BT.601 limited range, 20-bit fixed point; chroma replicated over
+ * each 2 x 2 block) where the kernels stage it, so interpolation, luminance balance and colour balance see cvtColor's texels.  Taps outside
+ * the frame stay 0 (BORDER_CONSTANT).  Call before or after bevw_build.  Refused with BEVW_E_INVALID:
+ *   - an odd FW or FH;
+ *   - together with BEVW_PROJ_ANALYTIC / BEVW_PROJ_ANALYTIC_F32 (in either order);
+ *   - on camera-shard handles (in either order with bevw_set_camera_shard).
+ * Not provided: BT.709 or full-range matrices, NV21, I420, YUYV / UYVY, a row pitch or separate plane pointers, a standalone converter.
+ * The per-camera tools (bevw_camera_undistort, ...) and the JPEG entry points keep taking BGR. */
+#define BEVW_INPUT_BGR 0
+#define BEVW_INPUT_NV12 1
+int bevw_set_input_format(bevw_handle *h, int format);
+int bevw_input_format(bevw_handle *h);   /* BEVW_INPUT_BGR or BEVW_INPUT_NV12 */
 /* The reference's own call shape, bev(front, back, left, right, car) (surroundBEV.py:312, main.py:84): four separate
  * [FH][FW][3] host arrays (no packing copy on the host), one frame set, out [BH][BW][3]. */
 int bevw_run_cameras(bevw_handle *h, const uint8_t *front, const uint8_t *back, const uint8_t *left, const uint8_t *right,
@@ -262,6 +279,10 @@ int bevw_remapper_get_maps(bevw_remapper *r, int16_t *map1, uint16_t *map2);
 /* src [batch][src_h][src_w][3] -> dst [batch][dst_h][dst_w][3]; INTER_LINEAR, BORDER_CONSTANT 0 */
 int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst);
 int bevw_remap_device(bevw_remapper *r, const void *d_src, int batch, void *d_dst);
+/* BEVW_INPUT_NV12 (bevw_set_input_format has the layout and the arithmetic): bevw_remap and bevw_remap_device read src as
+ * [batch][src_h*3/2][src_w] NV12 frames and write what cv2.remap writes for cv2.cvtColor(src, cv2.COLOR_YUV2BGR_NV12), in either
+ * BEVW_COMPAT_REMAP mode.  Refused (BEVW_E_INVALID) for an odd src_w or src_h. */
+int bevw_remapper_set_input_format(bevw_remapper *r, int format);
 int bevw_remapper_sync(bevw_remapper *r);
 int bevw_remapper_timer_start(bevw_remapper *r);
 int bevw_remapper_timer_stop(bevw_remapper *r, float *elapsed_ms);
