@@ -104,7 +104,7 @@ def _snapshot_config(blend=False, balance=False, device=0, schedule=_ffi.SCHED_A
 class _Engine:
     """Owns one bevw_handle (4 cameras + masks on the device)."""
 
-    def __init__(self, rig, blend, balance, device, schedule, output_pitch=0, input_format=_ffi.INPUT_BGR):
+    def __init__(self, rig, blend, balance, device, schedule, output_pitch=0, input_format=_ffi.INPUT_BGR, output_format=_ffi.OUTPUT_BGR):
         _ffi.require_device()
         self.cfg = _snapshot_config(blend, balance, device, schedule)
         h = C.c_void_p()
@@ -117,6 +117,8 @@ class _Engine:
                 check(lib().bevw_set_output_pitch(self.h, int(output_pitch)))
             if input_format != _ffi.INPUT_BGR:
                 check(lib().bevw_set_input_format(self.h, int(input_format)))
+            if output_format != _ffi.OUTPUT_BGR:
+                check(lib().bevw_set_output_format(self.h, int(output_format)))
             check(lib().bevw_build(self.h))
         except Exception:
             self.close()
@@ -293,7 +295,7 @@ class BevGenerator:
     """
 
     def __init__(self, blend=args.BLEND_FLAG, balance=args.BALANCE_FLAG, *, rig=None, device=0,
-                 schedule=_ffi.SCHED_AUTO, projection='lut', output_pitch='auto', input_format='bgr'):
+                 schedule=_ffi.SCHED_AUTO, projection='lut', output_pitch='auto', input_format='bgr', output_format='bgr'):
         """blend / balance: as in the reference (surroundBEV.py:283).  Additive keywords: rig ({name: (K, D, H)} instead of the
         data directory), device, schedule, and projection -- 'lut' (default: the reference's table-driven path, bit-exact against
         the oracle) 'analytic' (inverse homography + fisheye model evaluated per frame and pixel in fp64, no tables; not the
@@ -305,7 +307,12 @@ class BevGenerator:
         input_format -- 'bgr' (default: camera frames [FH, FW, 3], as cv2.imread hands them over) or 'nv12' (what a video decoder hands
         over: [FH*3//2, FW] uint8, the Y plane followed by the interleaved U / V plane).  An 'nv12' generator returns, byte for byte, what
         a 'bgr' one returns for the frames cv2.cvtColor(f, cv2.COLOR_YUV2BGR_NV12) makes: the conversion is fused into the stitch (see
-        bevw_set_input_format in include/bevwarp.h).  Needs even FW and FH and the 'lut' projection; jpeg() / jpeg_stream() take BGR only."""
+        bevw_set_input_format in include/bevwarp.h).  Needs even FW and FH and the 'lut' projection; jpeg() / jpeg_stream() take BGR only.
+        output_format -- 'bgr' (default: BEV images [BH, BW, 3]) or 'nv12' (what a video encoder takes: [BH*3//2, BW] uint8 per image, the
+        Y plane followed by the interleaved U / V plane; on the device rows of ``out_pitch`` bytes for both planes).  An 'nv12' generator
+        returns, byte for byte, the NV12 form of what a 'bgr' one returns: cv2.cvtColor(bev, cv2.COLOR_BGR2YUV_I420) with U and V
+        interleaved, the chroma of each 2 x 2 block from its top-left pixel (see bevw_set_output_format in include/bevwarp.h).  Needs even
+        BW and BH and the 'lut' projection; combines with either input_format; jpeg() / jpeg_stream() need BGR output."""
         self.init_args()
         if rig is None:
             self.cameras = [Camera('front'), Camera('back'), Camera('left'), Camera('right')]
@@ -323,14 +330,19 @@ class BevGenerator:
         formats = {'bgr': _ffi.INPUT_BGR, 'nv12': _ffi.INPUT_NV12}
         if input_format not in formats:
             raise Exception("input_format should be bgr/nv12")
+        out_formats = {'bgr': _ffi.OUTPUT_BGR, 'nv12': _ffi.OUTPUT_NV12}
+        if output_format not in out_formats:
+            raise Exception("output_format should be bgr/nv12")
         self.input_format = input_format
+        self.output_format = output_format
         rig_kdh = [(c.camera_mat, c.dist_coeff, c.homography) for c in self.cameras]
+        fmts = (formats[input_format], out_formats[output_format])
         try:
-            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, pitch, formats[input_format])
+            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, pitch, *fmts)
         except _ffi.BevwError:
             if not (auto and pitch != _ffi.PITCH_DENSE):
                 raise
-            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, _ffi.PITCH_DENSE, formats[input_format])   # a rig the tile plan cannot serve
+            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, _ffi.PITCH_DENSE, *fmts)   # a rig the tile plan cannot serve
         self.out_pitch = int(lib().bevw_output_pitch(self._engine.h))   # pixels per row of run_device()'s output images
         modes = {'lut': _ffi.PROJ_LUT, 'analytic': _ffi.PROJ_ANALYTIC, 'analytic_f32': _ffi.PROJ_ANALYTIC_F32}
         if projection not in modes:
@@ -366,6 +378,13 @@ class BevGenerator:
             return (c.frame_height * 3 // 2, c.frame_width)
         return (c.frame_height, c.frame_width, 3)
 
+    def _image_shape(self):
+        """Shape of one host-side BEV image this generator returns: (BH, BW, 3) for 'bgr', (BH*3//2, BW) for 'nv12'."""
+        c = self._engine.cfg
+        if self.output_format == 'nv12':
+            return (c.bev_height * 3 // 2, c.bev_width)
+        return (c.bev_height, c.bev_width, 3)
+
     # ---- reference call ------------------------------------------------------------------------------------
     def __call__(self, front, back, left, right, car=None):
         c = self._engine.cfg
@@ -387,7 +406,7 @@ class BevGenerator:
             if car.shape[:2] != (c.bev_height, c.bev_width):
                 raise Exception("car must be padded to the BEV size (padding())")
             car_p = ptr(car)
-        out = np.empty((c.bev_height, c.bev_width, 3), np.uint8)
+        out = np.empty(self._image_shape(), np.uint8)
         check(lib().bevw_run_cameras(self._engine.h, ptr(images[0]), ptr(images[1]), ptr(images[2]), ptr(images[3]), car_p,
                                      ptr(out)))
         return out
@@ -395,7 +414,7 @@ class BevGenerator:
     # ---- additive: batches ---------------------------------------------------------------------------------
     def batch(self, frames, car=None):
         """frames uint8 [B, 4, FH, FW, 3] (front, back, left, right) -> uint8 [B, BH, BW, 3].  An 'nv12' generator takes
-        [B, 4, FH*3//2, FW]."""
+        [B, 4, FH*3//2, FW]; one with output_format='nv12' returns [B, BH*3//2, BW]."""
         c = self._engine.cfg
         frames = np.ascontiguousarray(frames)
         want = (4,) + self._frame_shape()
@@ -407,7 +426,7 @@ class BevGenerator:
             if car.shape[:2] != (c.bev_height, c.bev_width):
                 raise Exception("car must be padded to the BEV size (padding())")
             car_p = ptr(car)
-        out = np.empty((frames.shape[0], c.bev_height, c.bev_width, 3), np.uint8)
+        out = np.empty((frames.shape[0],) + self._image_shape(), np.uint8)
         check(lib().bevw_run(self._engine.h, ptr(frames), frames.shape[0], car_p, ptr(out)))
         return out
 
@@ -489,6 +508,8 @@ class BevGenerator:
     def _jpeg_needs_bgr(self):
         if self.input_format != 'bgr':
             raise Exception("jpeg() / jpeg_stream() decode camera files to BGR: use a BevGenerator with input_format='bgr'")
+        if self.output_format != 'bgr':
+            raise Exception("jpeg() / jpeg_stream() encode BGR BEV images: use a BevGenerator with output_format='bgr'")
 
     def jpeg(self, files, car=None, quality=95):
         """main.py:74-84 + surroundBEV.py:340 with the pixels resident in HBM: ``files`` is a sequence of frame sets, each the four camera FILES' bytes
@@ -577,7 +598,10 @@ class BevGenerator:
 
     @property
     def out_image_bytes(self) -> int:
-        """Bytes of ONE device-side BEV image as run_device() writes it: rows of ``out_pitch`` pixels (padding columns included)."""
+        """Bytes of ONE device-side BEV image as run_device() writes it: rows of ``out_pitch`` pixels (padding columns included), 3 bytes
+        per pixel ('bgr') or a Y plane and a half-height U / V plane of ``out_pitch`` bytes per row ('nv12': out_pitch * BH * 3 // 2)."""
+        if self.output_format == 'nv12':
+            return self.out_pitch * self._engine.cfg.bev_height * 3 // 2
         return self.out_pitch * self._engine.cfg.bev_height * 3
 
     @property

@@ -48,13 +48,20 @@ DEFAULT_D = np.array([[-0.03367245449576437], [0.015380779195912842], [-0.018654
 class Undistorter:
     """The map set of one (K, D, size, scales, offsets) on the device."""
 
-    def __init__(self, K, D, width, height, focalscale=1.0, sizescale=1.0, offset_h=0.0, offset_v=0.0, device=0, input_format='bgr'):
+    def __init__(self, K, D, width, height, focalscale=1.0, sizescale=1.0, offset_h=0.0, offset_v=0.0, device=0, input_format='bgr',
+                 output_format='bgr'):
         """input_format: 'bgr' (images [height, width, 3]) or 'nv12' ([height*3//2, width]: Y plane, then the interleaved U / V plane; the
-        result is what cv2.remap gives for cv2.cvtColor(img, cv2.COLOR_YUV2BGR_NV12) -- bevw_remapper_set_input_format in include/bevwarp.h)."""
+        result is what cv2.remap gives for cv2.cvtColor(img, cv2.COLOR_YUV2BGR_NV12) -- bevw_remapper_set_input_format in include/bevwarp.h).
+        output_format: 'bgr' (results [out_h, out_w, 3]) or 'nv12' ([out_h*3//2, out_w]: the NV12 form of the BGR result, chroma of each 2 x 2
+        block from its top-left pixel -- bevw_set_output_format in include/bevwarp.h; needs an even output size)."""
         self._r = None
         formats = {'bgr': _ffi.INPUT_BGR, 'nv12': _ffi.INPUT_NV12}
         if input_format not in formats:
             raise Exception("input_format should be bgr/nv12")
+        out_formats = {'bgr': _ffi.OUTPUT_BGR, 'nv12': _ffi.OUTPUT_NV12}
+        if output_format not in out_formats:
+            raise Exception("output_format should be bgr/nv12")
+        self.output_format = output_format
         _ffi.require_device()
         self.width, self.height = int(width), int(height)
         self.input_format = input_format
@@ -63,12 +70,14 @@ class Undistorter:
                                                  float(focalscale), float(sizescale), float(offset_h), float(offset_v),
                                                  C.byref(r)))
         self._r = r
-        if input_format != 'bgr':
-            try:
+        try:
+            if input_format != 'bgr':
                 check(lib().bevw_remapper_set_input_format(r, formats[input_format]))
-            except Exception:
-                self.close()
-                raise
+            if output_format != 'bgr':
+                check(lib().bevw_remapper_set_output_format(r, out_formats[output_format]))
+        except Exception:
+            self.close()
+            raise
         dims = np.zeros(4, np.int32)
         check(lib().bevw_remapper_dims(r, ptr(dims)))
         self.out_w, self.out_h = int(dims[2]), int(dims[3])
@@ -81,7 +90,7 @@ class Undistorter:
 
     def __call__(self, images):
         """uint8 [B, height, width, 3] (or one [height, width, 3]) -> undistorted images of the map size.  'nv12': [B, height*3//2, width]
-        (or one [height*3//2, width])."""
+        (or one [height*3//2, width]).  output_format 'nv12': [B, out_h*3//2, out_w] (or one [out_h*3//2, out_w])."""
         imgs = np.ascontiguousarray(images)
         frame = (self.height * 3 // 2, self.width) if self.input_format == 'nv12' else (self.height, self.width, 3)
         single = imgs.ndim == len(frame)
@@ -89,7 +98,8 @@ class Undistorter:
             imgs = imgs[np.newaxis]
         if imgs.dtype != np.uint8 or imgs.shape[1:] != frame:
             raise Exception("images must be uint8 [B, {}]".format(", ".join(str(n) for n in frame)))
-        out = np.empty((imgs.shape[0], self.out_h, self.out_w, 3), np.uint8)
+        shape = (self.out_h * 3 // 2, self.out_w) if self.output_format == 'nv12' else (self.out_h, self.out_w, 3)
+        out = np.empty((imgs.shape[0],) + shape, np.uint8)
         check(lib().bevw_remap(self._r, ptr(imgs), imgs.shape[0], ptr(out)))
         return out[0] if single else out
 

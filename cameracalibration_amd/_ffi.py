@@ -12,12 +12,13 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BEVW_LIB_PATH") or os.path.join(_HERE, "libbevwarp.so")   # override: A/B of two builds
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 SCHED_AUTO, SCHED_PER_PIXEL, SCHED_TILE_PLAN = 0, 1, 2
 PROJ_LUT, PROJ_ANALYTIC, PROJ_ANALYTIC_F32 = 0, 1, 2   # bevw_set_projection
 PITCH_DENSE, PITCH_ALIGNED = 0, -1                    # bevw_set_output_pitch
 INPUT_BGR, INPUT_NV12 = 0, 1                         # bevw_set_input_format, bevw_remapper_set_input_format
+OUTPUT_BGR, OUTPUT_NV12 = 0, 1                       # bevw_set_output_format, bevw_remapper_set_output_format
 COMPAT_FILLPOLY, COMPAT_ADDWEIGHTED, COMPAT_WARP, COMPAT_REMAP = 0, 1, 2, 3   # bevw_set_compat keys (include/bevwarp.h)
 
 
@@ -63,6 +64,8 @@ SIGNATURES = {
     "bevw_output_pitch": (_i, [_vp]),
     "bevw_set_input_format": (_i, [_vp, _i]),
     "bevw_input_format": (_i, [_vp]),
+    "bevw_set_output_format": (_i, [_vp, _i]),
+    "bevw_output_format": (_i, [_vp]),
     "bevw_run_cameras": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bevw_camera_undistort": (_i, [_vp, _i, _vp, _i, _vp]),
     "bevw_camera_warp_homography": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
@@ -97,6 +100,7 @@ SIGNATURES = {
     "bevw_remap_device": (_i, [_vp, _vp, _i, _vp]),
     "bevw_remapper_sync": (_i, [_vp]),
     "bevw_remapper_set_input_format": (_i, [_vp, _i]),
+    "bevw_remapper_set_output_format": (_i, [_vp, _i]),
     "bevw_remapper_timer_start": (_i, [_vp]),
     "bevw_remapper_timer_stop": (_i, [_vp, C.POINTER(C.c_float)]),
     "bevw_remapper_timer_mark": (_i, [_vp, _i]),

@@ -283,6 +283,67 @@ __device__ __forceinline__ uint32_t nv12_texel(const uint8_t *__restrict__ src, 
 // bytes of one frame set: BGR 3 per texel, NV12 1.5
 __host__ __device__ __forceinline__ size_t frame_bytes_of(int fw, int fh, bool nv12) { return nv12 ? (size_t)fw * fh * 3 / 2 : (size_t)fw * fh * 3; }
 
+// ---- NV12 BEV images (bevw_set_output_format) -------------------------------------------------------------
+// An NV12 image of BW x BH pixels (both even) with a row pitch of `pitch` bytes is a Y plane of BH rows followed by a U / V plane of BH / 2
+// rows, U first, both with the same pitch: pitch * BH * 3 / 2 bytes.  It is cv2.cvtColor(bgr, cv2.COLOR_BGR2YUV_I420) with the U and V
+// planes interleaved -- OpenCV's RGB8toYUV420pInvoker: BT.601 limited range, 20-bit fixed point, and the chroma of the 2 x 2 block (i, j)
+// taken from its top-left pixel (2j, 2i) alone (no averaging):
+//   Y = (269484 R + 528482 G + 102760 B + (16 << 20) + (1 << 19)) >> 20
+//   U = (-155188 R - 305135 G + 460324 B + (128 << 20) + (1 << 19)) >> 20
+//   V = (460324 R - 385875 G - 74448 B + (128 << 20) + (1 << 19)) >> 20
+// Every sum is positive and below 2^28, so Y lies in [16, 235] and U, V in [16, 240] without a clamp; black is (16, 128, 128).  Every
+// product is a byte times a coefficient below 2^23: one v_mad_i32_i24 each.  Checked exhaustively (all 2^24 B, G, R) against the NumPy
+// statement of the arithmetic: tests/native/nv12_out_exhaustive.cpp.
+constexpr int kBgrYR = 269484, kBgrYG = 528482, kBgrYB = 102760, kBgrY0 = (16 << 20) + (1 << 19);
+constexpr int kBgrUR = -155188, kBgrUG = -305135, kBgrUB = 460324, kBgrC0 = (128 << 20) + (1 << 19);
+constexpr int kBgrVR = 460324, kBgrVG = -385875, kBgrVB = -74448;
+// one pixel B | G << 8 | R << 16 (byte 3 ignored) -> its Y byte
+__host__ __device__ __forceinline__ uint32_t bgr_to_y(uint32_t p)
+{
+    const int b = (int)(p & 255u), g = (int)((p >> 8) & 255u), r = (int)((p >> 16) & 255u);
+    return (uint32_t)((r * kBgrYR + g * kBgrYG + b * kBgrYB + kBgrY0) >> 20);
+}
+// one pixel -> its U | V << 8
+__host__ __device__ __forceinline__ uint32_t bgr_to_uv(uint32_t p)
+{
+    const int b = (int)(p & 255u), g = (int)((p >> 8) & 255u), r = (int)((p >> 16) & 255u);
+    return (uint32_t)((r * kBgrUR + g * kBgrUG + b * kBgrUB + kBgrC0) >> 20) | ((uint32_t)((r * kBgrVR + g * kBgrVG + b * kBgrVB + kBgrC0) >> 20) << 8);
+}
+// a quad of four pixels x .. x+3 of one row (x % 4 == 0) -> its Y dword and its U / V dword (U V of pixel x, U V of pixel x+2: the chroma of
+// the two 2 x 2 blocks whose top-left pixels the quad holds when its row is even)
+__host__ __device__ __forceinline__ void nv12_quad(const uint32_t P[4], uint32_t &y, uint32_t &uv)
+{
+    y = bgr_to_y(P[0]) | (bgr_to_y(P[1]) << 8) | (bgr_to_y(P[2]) << 16) | (bgr_to_y(P[3]) << 24);
+    uv = bgr_to_uv(P[0]) | (bgr_to_uv(P[2]) << 16);
+}
+// the 12 bytes of a packed quad (pack_pixels) -> its four pixels (byte 3 of each is garbage: bgr_to_y / bgr_to_uv ignore it)
+__host__ __device__ __forceinline__ void unpack_quad(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t P[4])
+{
+    P[0] = d0;
+    P[1] = (d0 >> 24) | (d1 << 8);
+    P[2] = (d1 >> 16) | (d2 << 16);
+    P[3] = d2 >> 8;
+}
+// byte offsets inside one NV12 image of pixel (x, y)'s Y byte, and of the U / V pair of the 2 x 2 block whose top-left pixel it is (x, y even)
+__host__ __device__ __forceinline__ uint32_t nv12_y_offset(int pitch, int x, int y) { return (uint32_t)y * (uint32_t)pitch + (uint32_t)x; }
+__host__ __device__ __forceinline__ uint32_t nv12_uv_offset(int pitch, int bh, int x, int y)
+{
+    return ((uint32_t)bh + ((uint32_t)y >> 1)) * (uint32_t)pitch + (uint32_t)x;
+}
+// bytes of one BEV image with rows of `pitch` pixels: BGR 3 per pixel, NV12 1.5
+__host__ __device__ __forceinline__ size_t image_bytes_of(int pitch, int bh, bool nv12) { return nv12 ? (size_t)pitch * bh * 3 / 2 : (size_t)pitch * bh * 3; }
+// one pixel's Y, and for the top-left pixel of a block its U / V, into an NV12 image (the per-pixel kernels: one thread per pixel)
+__device__ __forceinline__ void nv12_store_px(uint8_t *img, int pitch, int bh, int x, int y, uint32_t p)
+{
+    img[nv12_y_offset(pitch, x, y)] = (uint8_t)bgr_to_y(p);
+    if (((x | y) & 1) == 0) {
+        const uint32_t uv = bgr_to_uv(p);
+        uint8_t *c = img + nv12_uv_offset(pitch, bh, x, y);
+        c[0] = (uint8_t)uv;
+        c[1] = (uint8_t)(uv >> 8);
+    }
+}
+
 // Linear block id of a 1-D grid -> (frame, block inside the frame) such that XCD id % 8 owns WHOLE frames: the rows a kernel
 // writes are then completed inside one L2 (tools/store_pattern.hip: 4.7 TB/s with such a map, 2.9 TB/s when the blocks of a
 // frame are dealt round-robin to the XCDs).  Grid = blocks_per_frame * 8 * ceil(nframes / 8) blocks.

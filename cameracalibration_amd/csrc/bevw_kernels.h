@@ -253,7 +253,8 @@ static __global__ void k_blend_weights(uint8_t *__restrict__ maskA, const uint8_
 
 // cv2.remap(src, map1, map2, INTER_LINEAR) for a batch: one thread per destination pixel.
 // grid = (ceil(dw / 256), dh, batch).  NV12: the sources are NV12 frames (bevw_remapper_set_input_format), converted per tap.
-template <bool NV12 = false>
+// OUT_NV12: dst holds dense NV12 images (bevw_remapper_set_output_format, dw and dh even): the pixel's Y, and U / V on even rows and columns
+template <bool NV12 = false, bool OUT_NV12 = false>
 static __global__ void k_remap_lut(const uint8_t *__restrict__ src, int sw, int sh, const int16_t *__restrict__ map1,
                             const uint16_t *__restrict__ map2, int dw, int dh, uint8_t *__restrict__ dst, int ties_even = 0)
 {
@@ -262,10 +263,15 @@ static __global__ void k_remap_lut(const uint8_t *__restrict__ src, int sw, int 
     if (x >= dw) return;
     const size_t o = (size_t)y * dw + x;
     const uint8_t *s = src + (NV12 ? (size_t)blockIdx.z * frame_bytes_of(sw, sh, true) : (size_t)blockIdx.z * sw * sh * 3);
-    uint8_t *d = dst + ((size_t)blockIdx.z * dw * dh + o) * 3;
     const int sx = map1[o * 2], sy = map1[o * 2 + 1];
     int out[3];
     remap_u8c3_px<false, NV12>(s, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even);
+    if (OUT_NV12) {
+        nv12_store_px(dst + (size_t)blockIdx.z * image_bytes_of(dw, dh, true), dw, dh, x, y,
+                      (uint32_t)out[0] | ((uint32_t)out[1] << 8) | ((uint32_t)out[2] << 16));
+        return;
+    }
+    uint8_t *d = dst + ((size_t)blockIdx.z * dw * dh + o) * 3;
     d[0] = (uint8_t)out[0]; d[1] = (uint8_t)out[1]; d[2] = (uint8_t)out[2];
 }
 
@@ -401,7 +407,8 @@ static __global__ void k_lum_shift(const uint8_t *__restrict__ frames, size_t fr
 // (integer, so the result does not depend on the order of the atomics).
 // grid = (ceil(bw / 256), bh, batch)
 // NV12: NV12 frame sets (bevw_set_input_format), every tap converted where it is fetched (remap_u8c3_px)
-template <bool BLEND, bool BAL, bool NV12 = false>
+// OUT_NV12 (not with BAL, whose pre-gain image is BGR): dense NV12 BEV images (bevw_set_output_format), converted after the car
+template <bool BLEND, bool BAL, bool NV12 = false, bool OUT_NV12 = false>
 static __global__ void k_stitch_pp(const uint8_t *__restrict__ frames, int fw, int fh, StitchTables T, int bw, int bh,
                             const int *__restrict__ deltas, const HsvTables *__restrict__ tab,
                             const uint8_t *__restrict__ car, unsigned long long *__restrict__ chsums,
@@ -439,7 +446,13 @@ static __global__ void k_stitch_pp(const uint8_t *__restrict__ frames, int fw, i
             acc[0] = min(255, acc[0] + car[o * 3]); acc[1] = min(255, acc[1] + car[o * 3 + 1]);
             acc[2] = min(255, acc[2] + car[o * 3 + 2]);
         }
-        d[0] = (uint8_t)acc[0]; d[1] = (uint8_t)acc[1]; d[2] = (uint8_t)acc[2];
+        if (OUT_NV12) {
+            static_assert(!(OUT_NV12 && BAL), "balance: the pre-gain image is BGR, the gain pass writes NV12");
+            nv12_store_px(out + (size_t)b * image_bytes_of(bw, bh, true), bw, bh, x, y,
+                          (uint32_t)acc[0] | ((uint32_t)acc[1] << 8) | ((uint32_t)acc[2] << 16));
+        } else {
+            d[0] = (uint8_t)acc[0]; d[1] = (uint8_t)acc[1]; d[2] = (uint8_t)acc[2];
+        }
     }
     if (BAL) {
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -851,21 +864,12 @@ static __global__ void k_apply_mask(const uint8_t *__restrict__ img, const uint8
     }
 }
 
-// k_gain with a per-frame 3 x 256 look-up table (the gain is one fp64 multiply + cvRound per byte VALUE, so 768
-// table entries per frame replace 3.5 M fp64 operations) and 12-byte vector accesses (4 pixels per lane).
-// Needs npx % 4 == 0 and 4-byte aligned images.  grid = (blocks, batch), block = 256; in place when in == out.
-// psums != nullptr: the channel sums of a frame arrive as `nsum` partial sums (one per unit / border tile of the tile plan:
-// psums[frame][nsum][3], bevw_plan.h) and every block adds them up itself -- integer sums, the same value k_reduce_psums would have left in
-// chsums, without that kernel between the stitch and this pass.
-static __global__ void __launch_bounds__(256) k_gain_lut(const uint8_t *in, size_t npx, const unsigned long long *__restrict__ chsums,
-                                                   const uint8_t *__restrict__ car, uint8_t *out, uint32_t blocks_per_frame,
-                                                   uint32_t nframes, int f32 = 0, size_t npx_mean = 0, const uint32_t *__restrict__ psums = nullptr,
-                                                   int nsum = 0)
+// the block's frame and its gain table: lut[c][v] = the gained value v of channel c (k_gain_lut, k_gain_lut_nv12).  false: no frame
+__device__ __forceinline__ bool gain_lut_prepare(uint8_t (&lut)[3][256], unsigned long long (&part)[3][4], size_t npx,
+                                                 const unsigned long long *__restrict__ chsums, uint32_t blocks_per_frame, uint32_t nframes,
+                                                 int f32, size_t npx_mean, const uint32_t *__restrict__ psums, int nsum, uint32_t &frame, uint32_t &blk)
 {
-    __shared__ uint8_t lut[3][256];
-    __shared__ unsigned long long part[3][4];
-    uint32_t frame, blk;
-    if (!xcd_frame_map(blockIdx.x, blocks_per_frame, nframes, frame, blk)) return;   // grid: xcd_frame_grid()
+    if (!xcd_frame_map(blockIdx.x, blocks_per_frame, nframes, frame, blk)) return false;   // grid: xcd_frame_grid()
     unsigned long long total[3];
     if (psums != nullptr) {
         const uint32_t *p = psums + (size_t)frame * nsum * 3;
@@ -896,6 +900,24 @@ static __global__ void __launch_bounds__(256) k_gain_lut(const uint8_t *in, size
         }
     }
     __syncthreads();
+    return true;
+}
+
+// k_gain with a per-frame 3 x 256 look-up table (the gain is one fp64 multiply + cvRound per byte VALUE, so 768
+// table entries per frame replace 3.5 M fp64 operations) and 12-byte vector accesses (4 pixels per lane).
+// Needs npx % 4 == 0 and 4-byte aligned images.  grid = (blocks, batch), block = 256; in place when in == out.
+// psums != nullptr: the channel sums of a frame arrive as `nsum` partial sums (one per unit / border tile of the tile plan:
+// psums[frame][nsum][3], bevw_plan.h) and every block adds them up itself -- integer sums, the same value k_reduce_psums would have left in
+// chsums, without that kernel between the stitch and this pass.
+static __global__ void __launch_bounds__(256) k_gain_lut(const uint8_t *in, size_t npx, const unsigned long long *__restrict__ chsums,
+                                                   const uint8_t *__restrict__ car, uint8_t *out, uint32_t blocks_per_frame,
+                                                   uint32_t nframes, int f32 = 0, size_t npx_mean = 0, const uint32_t *__restrict__ psums = nullptr,
+                                                   int nsum = 0)
+{
+    __shared__ uint8_t lut[3][256];
+    __shared__ unsigned long long part[3][4];
+    uint32_t frame, blk;
+    if (!gain_lut_prepare(lut, part, npx, chsums, blocks_per_frame, nframes, f32, npx_mean, psums, nsum, frame, blk)) return;
     const size_t base = (size_t)frame * npx * 3, nq = npx / 4;
     for (size_t q = (size_t)blk * blockDim.x + threadIdx.x; q < nq; q += (size_t)blocks_per_frame * blockDim.x) {
         const uint32_t *ip = reinterpret_cast<const uint32_t *>(in + base + q * 12);
@@ -913,6 +935,74 @@ static __global__ void __launch_bounds__(256) k_gain_lut(const uint8_t *in, size
         }
         uint32_t *op = reinterpret_cast<uint32_t *>(out + base + q * 12);
         once_store<BEVW_GAIN_NT>(op, o[0]); once_store<BEVW_GAIN_NT>(op + 1, o[1]); once_store<BEVW_GAIN_NT>(op + 2, o[2]);
+    }
+}
+
+// k_gain_lut writing NV12 (bevw_set_output_format): `in` holds the pre-gain BGR images (npx = pitch * bh pixels each, 4-byte aligned), `out`
+// NV12 images of pitch * bh * 3 / 2 bytes (pitch and bh even).  A lane gains its quad of 4 pixels, adds the car, converts (nv12_quad) and
+// stores the Y dword and, on even rows, the chroma of the blocks whose top-left pixels it holds.  Quads cross rows only when pitch % 4 == 2;
+// such pitches and unaligned output or car buffers take the byte-wise stores.  The quad's row comes from a float reciprocal of the pitch,
+// corrected by one step (the estimate is within one row for images below 2^31 pixels).
+static __global__ void __launch_bounds__(256) k_gain_lut_nv12(const uint8_t *in, size_t npx, const unsigned long long *__restrict__ chsums,
+                                                        const uint8_t *__restrict__ car, uint8_t *out, uint32_t blocks_per_frame, uint32_t nframes,
+                                                        int f32, size_t npx_mean, const uint32_t *__restrict__ psums, int nsum, int pitch, int bh)
+{
+    __shared__ uint8_t lut[3][256];
+    __shared__ unsigned long long part[3][4];
+    uint32_t frame, blk;
+    if (!gain_lut_prepare(lut, part, npx, chsums, blocks_per_frame, nframes, f32, npx_mean, psums, nsum, frame, blk)) return;
+    const size_t base = (size_t)frame * npx * 3, nq = npx / 4;
+    uint8_t *img = out + (size_t)frame * image_bytes_of(pitch, bh, true);
+    const bool al = (((uintptr_t)img | (uintptr_t)car) & 3u) == 0 && pitch % 4 == 0;   // uniform over the launch / block
+    const uint32_t uv0 = (uint32_t)bh * (uint32_t)pitch;
+    const float rcp = 1.0f / (float)pitch;
+    auto row_of = [&](uint32_t i) {
+        uint32_t r = (uint32_t)((float)i * rcp);
+        const uint32_t lo = r * (uint32_t)pitch;
+        if (lo > i) --r;
+        else if (i - lo >= (uint32_t)pitch) ++r;
+        return r;
+    };
+    for (size_t q = (size_t)blk * blockDim.x + threadIdx.x; q < nq; q += (size_t)blocks_per_frame * blockDim.x) {
+        const uint32_t *ip = reinterpret_cast<const uint32_t *>(in + base + q * 12);
+        uint32_t w[3] = {once_load<BEVW_GAIN_NT>(ip), once_load<BEVW_GAIN_NT>(ip + 1), once_load<BEVW_GAIN_NT>(ip + 2)}, cw[3] = {0, 0, 0}, o[3] = {0, 0, 0};
+        if (car != nullptr) {
+            if (al) {
+                const uint32_t *cp = reinterpret_cast<const uint32_t *>(car + q * 12);
+                cw[0] = cp[0]; cw[1] = cp[1]; cw[2] = cp[2];
+            } else {
+#pragma unroll
+                for (int k = 0; k < 12; ++k) cw[k >> 2] |= (uint32_t)car[q * 12 + k] << ((k & 3) * 8);
+            }
+        }
+#pragma unroll
+        for (int bi = 0; bi < 12; ++bi) {
+            const int c = bi % 3;
+            uint32_t v = lut[c][(w[bi >> 2] >> ((bi & 3) * 8)) & 255u];
+            v = min(255u, v + ((cw[bi >> 2] >> ((bi & 3) * 8)) & 255u));
+            o[bi >> 2] |= v << ((bi & 3) * 8);
+        }
+        uint32_t P[4], yw, uvw;
+        unpack_quad(o[0], o[1], o[2], P);
+        nv12_quad(P, yw, uvw);
+        const uint32_t i = (uint32_t)q * 4u;   // Y offset of the quad's first pixel (rows of `pitch` pixels: the Y plane IS the flat pixel index)
+        if (al) {
+            once_store<BEVW_GAIN_NT>(reinterpret_cast<uint32_t *>(img + i), yw);
+            const uint32_t y = row_of(i), x = i - y * (uint32_t)pitch;
+            if (!(y & 1u)) once_store<BEVW_GAIN_NT>(reinterpret_cast<uint32_t *>(img + uv0 + (i + x) / 2), uvw);   // nv12_uv_offset
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) img[i + k] = (uint8_t)(yw >> (8 * k));
+#pragma unroll
+            for (int k = 0; k < 4; k += 2) {   // pixels i and i + 2: even columns (pitch is even), their own rows
+                const uint32_t y = row_of(i + k), x = i + k - y * (uint32_t)pitch;
+                if (!(y & 1u)) {
+                    uint8_t *c = img + uv0 + (i + k + x) / 2;
+                    c[0] = (uint8_t)(uvw >> (8 * k));
+                    c[1] = (uint8_t)(uvw >> (8 * k + 8));
+                }
+            }
+        }
     }
 }
 

@@ -371,7 +371,9 @@ __device__ __forceinline__ bool plan_block_map(const PlanArgs &a, uint32_t id, u
 // LUM: luminance round trip per fetched texel (raw frames); SUMS: emit per-tile channel sums and leave the car to the gain pass
 // (two waves per SIMD: the 128-VGPR budget of rounds 1 - 3 spilled 0.5 - 1.2 KB per lane to scratch -- tools/kernel_resources.sh)
 // NV12: NV12 frame sets (bevw_set_input_format), every tap converted where it is fetched (eval_entry)
-template <bool BLEND, bool LUM, bool SUMS = LUM, bool NV12 = false>
+// OUT_NV12: NV12 BEV images (bevw_set_output_format; a.pitch % 4 == 0, no SUMS: the balance modes store BGR for the gain pass) -- a lane's
+// quad as one Y dword and, on even rows, one U / V dword (nv12_quad), after the car
+template <bool BLEND, bool LUM, bool SUMS = LUM, bool NV12 = false, bool OUT_NV12 = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) k_stitch_plan(PlanArgs a)
 {
     constexpr bool BAL = LUM;
@@ -451,7 +453,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
 #pragma unroll
         for (int j = 0; j < 4; ++j) P[j] = (uint32_t)px[j][0] | ((uint32_t)px[j][1] << 8) | ((uint32_t)px[j][2] << 16);
         if (!SUMS && car_any) add_car(P, car0, car1, car2);
-        if (inimg) {
+        if (OUT_NV12) {
+            static_assert(!(OUT_NV12 && SUMS), "balance: the pre-gain image is BGR, the gain pass writes NV12");
+            if (inimg) {
+                uint32_t yw, uvw;
+                nv12_quad(P, yw, uvw);
+                uint8_t *img = a.out + (size_t)b * image_bytes_of(a.pitch, a.bh, true);
+                *reinterpret_cast<uint32_t *>(img + nv12_y_offset(a.pitch, x0, y)) = yw;
+                if (!(y & 1)) *reinterpret_cast<uint32_t *>(img + nv12_uv_offset(a.pitch, a.bh, x0, y)) = uvw;
+            }
+        } else if (inimg) {
             uint32_t d0, d1, d2;
             pack_pixels(P, d0, d1, d2);
             uint32_t *op = reinterpret_cast<uint32_t *>(a.out + (size_t)b * img_bytes + ooff);
@@ -609,6 +620,10 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
         UnitPlanHost up;
         std::vector<uint32_t> hdr_un = hdr;
         unit_compile(h1, h2, hm, ncams, fw, fh, bw, bh, plan_pitch(bw, out_pitch), p.tiles_x, p.tiles_y, hdr_un, up, unit_tune);
+        // every unit quad starts at a column x % 4 == 0 (left edges and the row skew are multiples of 4): the NV12 store stage
+        // (plan_unit_run<.., OUT_NV12>) writes the chroma of the blocks whose top-left pixels the quad holds, and needs no other unit's pixels
+        for (const UnitDesc &d : up.desc)
+            if (((int)(int16_t)(d.pos & 0xffffu)) % 4 != 0 || unit_skew((uint32_t)up.skew, 1) % 4 != 0) return hipErrorInvalidValue;
         if (!up.desc.empty()) {
             hdr.swap(hdr_un);
             if ((e = plan_upload_units(p, up)) != hipSuccess) return e;
@@ -691,6 +706,9 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
     a.plan = static_cast<const uint2 *>(p.entries); a.hdr = static_cast<const uint32_t *>(p.hdr);
     a.deltas = d_deltas; a.tab = d_tab;
     const bool padded = p.pitch != p.bw, scratch = padded && !p.out_pitched;
+    // NV12 images (p.out_nv12) unless the step leaves a pre-gain BGR image for a gain pass (channel sums) or serves a shard (compact scratch)
+    const bool out_nv12 = p.out_nv12 && !balance && !sums && d_scratch == nullptr;
+    if (out_nv12 && (scratch || p.pitch % 4 != 0)) return hipErrorInvalidValue;   // (the caller runs the per-pixel kernel instead)
     if (padded) {
         const size_t img = (size_t)p.pitch * p.bh * 3, need = scratch ? img * (size_t)batch : 0;
         if (need > p.pad_cap) {
@@ -742,6 +760,10 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         if (nv12_units) {
             a.set_stride = (uint32_t)(frame_bytes_of(p.fw, p.fh, true) * p.ncams);
             a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_nv12);
+        }
+        if (out_nv12) {
+            with_flags([&](auto bl, auto nv) { hipLaunchKernelGGL((k_units_out_nv12<bl, nv>), dim3(plan_grid(a)), block, 0, st, a); }, blend, nv12_units);
+        } else if (nv12_units) {
             with_flags([&](auto bl) { hipLaunchKernelGGL((k_units_nv12<bl>), dim3(plan_grid(a)), block, 0, st, a); }, blend);
         } else {
             with_flags([&](auto bl, auto sm) { hipLaunchKernelGGL((k_plan_units<bl, sm>), dim3(plan_grid(a)), block, 0, st, a); }, blend, sums);
@@ -756,7 +778,10 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         a.frames = d_frames; a.set_stride = 0;   // the per-tap kernel reads whole frames: RAW ones in the balance modes
         // LUM: luminance round trip per tap (the RAW frames of balance, or the tiles no unit owns beside the compact scratch); compact
         // without sums: camera-per-GPU shards, whose stitch rank balances the colours
-        if (p.nv12)
+        if (out_nv12)
+            with_flags([&](auto bl, auto nv) { hipLaunchKernelGGL((k_stitch_plan<bl, false, false, nv, true>), dim3(plan_grid(a)), block, 0, st, a); },
+                       blend, p.nv12);
+        else if (p.nv12)
             with_flags([&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm, true>), dim3(plan_grid(a)), block, 0, st, a); },
                        blend, balance || compact, balance || sums);
         else

@@ -54,6 +54,9 @@ struct Plan {
     int un_skew = 0;
     // the per-frame kernels read NV12 frame sets (bevw_set_input_format): set by the plan's owner after plan_build, which resets it
     bool nv12 = false;
+    // the per-frame kernels write NV12 images of `pitch` bytes per row (bevw_set_output_format; needs pitch % 4 == 0 and no padded scratch):
+    // set by the owner after plan_build.  Steps with channel sums (balance) still write the BGR pre-gain image: their gain pass converts.
+    bool out_nv12 = false;
 };
 
 // compile LUT + masks into a plan (table kernels, unit compiler on the host).  out_pitch: pixels per output row when the caller's images

@@ -575,11 +575,20 @@ static inline std::vector<uint32_t> unit_host_headers(const std::vector<int16_t>
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // CPU emulation of one unit and one frame: the per-lane steps of plan_unit_body in program order (group loads -> pair conversion
-// -> patch -> pixel interpolation -> 12-byte stores), with the same helpers.  Test infrastructure (tests/native/unit_emulate.cpp).
+// -> patch -> pixel interpolation -> 12-byte stores), with the same helpers.  Test infrastructure (tests/native/unit_emulate.cpp,
+// tests/native/nv12_out_emulate.cpp).
 // ---------------------------------------------------------------------------------------------------------------------------------
+// the store stage of plan_unit_run<.., OUT_NV12>: NV12 image of `pitch` bytes per row and bh rows; y_written / uv_written count the stores of
+// every Y byte ([bh][pitch]) and of every U / V pair ([bh / 2][pitch / 2])
+struct UnitNv12Out {
+    uint8_t *img;
+    int bh;
+    std::vector<uint8_t> *y_written, *uv_written;
+};
 static inline void unit_emulate(const UnitPlanHost &up, uint32_t unit, int cls, const uint8_t *frame_set, size_t set_bytes, bool blend,
-                                const uint8_t *car, int pitch, uint8_t *out_img, uint32_t sums[3] = nullptr, std::vector<uint8_t> *written = nullptr)
-    // written: per PIXEL, the number of its BYTES stored (3 = every byte exactly once)
+                                const uint8_t *car, int pitch, uint8_t *out_img, uint32_t sums[3] = nullptr, std::vector<uint8_t> *written = nullptr,
+                                const UnitNv12Out *nv12 = nullptr)
+    // written: per PIXEL, the number of its BYTES stored (3 = every byte exactly once).  nv12: the NV12 store stage instead of the BGR one
 {
     const UnitDesc &d = up.desc[unit];
     const int NQ = kUnitClassNQ[cls], GR = kUnitClassGR[cls], NCON = kUnitClassCON[cls], fpart = NCON == 2 ? 3 : 1, parts = fpart + (up.wide ? NCON : 0);
@@ -601,6 +610,8 @@ static inline void unit_emulate(const UnitPlanHost &up, uint32_t unit, int cls, 
     for (int wave = 0; wave < kUnitWaves; ++wave)
         for (int j = 0; j < NQ; ++j) {
             uint32_t od[64][3];     // the wave's packed quads of this slot, the lanes' store masks and offsets: the store format needs the neighbours
+            uint32_t yq[64], uvq[64];   // nv12: the lanes' Y and U / V dwords (nv12_quad)
+            int qy[64], qxp[64];        // nv12: the lanes' quad positions
             bool st[64];
             size_t so[64];
             for (int lane = 0; lane < 64; ++lane) {
@@ -647,6 +658,22 @@ static inline void unit_emulate(const UnitPlanHost &up, uint32_t unit, int cls, 
                     add_car(P, c[0], c[1], c[2]);
                 }
                 pack_pixels(P, od[lane][0], od[lane][1], od[lane][2]);
+                nv12_quad(P, yq[lane], uvq[lane]);
+                qy[lane] = uy + row;
+                qxp[lane] = x;
+            }
+            if (nv12) {   // plan_unit_run<.., OUT_NV12>: store_nv12 -- one Y dword per quad, one U / V dword on even rows
+                for (int lane = 0; lane < 64; ++lane) {
+                    if (!st[lane]) continue;
+                    const uint32_t yo = nv12_y_offset(pitch, qxp[lane], qy[lane]);
+                    memcpy(nv12->img + yo, &yq[lane], 4);
+                    for (int k = 0; k < 4; ++k) ++(*nv12->y_written)[yo + k];
+                    if (qy[lane] & 1) continue;
+                    const uint32_t co = nv12_uv_offset(pitch, nv12->bh, qxp[lane], qy[lane]);
+                    memcpy(nv12->img + co, &uvq[lane], 4);
+                    for (int k = 0; k < 2; ++k) ++(*nv12->uv_written)[(size_t)(qy[lane] / 2) * (pitch / 2) + qxp[lane] / 2 + k];
+                }
+                continue;
             }
             // the wave-store (unit_store_quad16 / unit_store_quad): whole lane quads write 3 x 16 bytes, the other lanes 12 bytes
             for (int lane = 0; lane < 64; ++lane) {
@@ -739,15 +766,26 @@ __device__ __forceinline__ void unit_store_quad16(uint32_t d0, uint32_t d1, uint
     if (streaming) __builtin_amdgcn_raw_buffer_store_b128(v, ro, off16, 0, kPairStreamAux);
     else __builtin_amdgcn_raw_buffer_store_b128(v, ro, off16, 0, kPairStoreAux);
 }
+// one dword of an NV12 image (OUT_NV12: a quad's Y bytes, or the U / V pairs of its blocks); the policy of unit_store_quad
+__device__ __forceinline__ void unit_store_dword(uint32_t v, __amdgpu_buffer_rsrc_t ro, int off, bool streaming)
+{
+    if (streaming) __builtin_amdgcn_raw_buffer_store_b32(v, ro, off, 0, kPairStreamAux);
+    else __builtin_amdgcn_raw_buffer_store_b32(v, ro, off, 0, kPairStoreAux);
+}
 // NV12: the frames are NV12 frame sets (bevw_set_input_format) and a.un_gsrc holds two offsets per group slot (unit_gsrc_nv12); the group
 // is fetched as two 8-byte loads and converted to BGR where it lands (pair_convert_nv12).  The patch, the plan entries, the interpolation and
 // the stores are the BGR kernel's.  (The balance schedule's units read the compact scratch, which is BGR: no NV12 variant with SUMS.)
-template <bool BLEND, bool SUMS, int NQ, int GR, int NCON, bool WIDE = false, bool NV12 = false>
+// OUT_NV12: a.out holds NV12 images (bevw_set_output_format; a.pitch % 4 == 0): each lane converts its final quad (nv12_quad, after the car)
+// and stores one Y dword and, on even rows, one U / V dword -- the chroma of the two 2 x 2 blocks whose top-left pixels it holds.  Quads start
+// at x % 4 == 0 (unit left edges and the skew are multiples of 4), so no unit needs another unit's pixels and the plan is the BGR one.
+// The 16-byte store format does not apply (a quad is 4 bytes of Y).  ooff_masked holds the quad's Y offset; the car (BGR) is read at 3 times it.
+template <bool BLEND, bool SUMS, int NQ, int GR, int NCON, bool WIDE = false, bool NV12 = false, bool OUT_NV12 = false>
 __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk, uint32_t unit, uint8_t *lds, uint4 *wave_sums = nullptr)
 {
     static_assert(NQ >= 1 && NQ <= kUnitMaxNQ && GR >= 1 && GR <= kUnitMaxGR && (NCON == 1 || NCON == 2), "unit class");
     static_assert(!(WIDE && SUMS), "wide plans carry no channel sums");
     static_assert(!(NV12 && (SUMS || WIDE)), "NV12 units: table projection, raw frames");
+    static_assert(!(OUT_NV12 && (SUMS || WIDE)), "NV12 images: table projection, no channel sums (balance stores BGR for the gain pass)");
     constexpr int kFPart = NCON == 2 ? 3 : 1;          // narrow part: the entries of each contributor (+ the blend weights)
     constexpr int kParts = kFPart + (WIDE ? NCON : 0); // uint4 per lane and quad slot in the plan
     constexpr bool kWeights = BLEND && NCON == 2;
@@ -761,7 +799,8 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
     const int ux = (int)(int16_t)(pos & 0xffffu), uy = (int)(pos >> 16), uw = (int)(shape & 0xffffu), uh = (int)(shape >> 16);
     // bytes between consecutive frame sets as this kernel reads them: whole frames, or the compact scratch of the balance schedule (unit_gsrc_compact)
     const size_t set_bytes = a.set_stride ? (size_t)a.set_stride : (size_t)a.fw * a.fh * 3 * a.ncams, img_bytes = (size_t)a.pitch * a.bh * 3;
-    const bool streaming = ((uint32_t)a.pitch * 3u) % 64u == 0u;   // rows of whole sectors (see unit_store_quad)
+    const bool streaming = ((uint32_t)a.pitch * 3u) % 64u == 0u;   // rows of whole sectors (see unit_store_quad; NV12: the same condition)
+    const size_t out_bytes = OUT_NV12 ? image_bytes_of(a.pitch, a.bh, true) : img_bytes;   // one output image
     constexpr int kPatch = GR * kUnitThreads * 32;              // one frame's pair entries
     constexpr bool DB = 2 * kPatch <= kUnitMaxGroups * 32;      // both halves fit the block's 32 KB
 
@@ -770,12 +809,15 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
     // bit j of part_bits = slot j of this lane stores 12 bytes after all (its lane quad is not whole); part_any: some lane of the wave does
     const bool store16 = BEVW_UNIT_STORE16 == 2 || (BEVW_UNIT_STORE16 == 1 && streaming);
     uint32_t ooff16[NQ], part_bits = 0;
+    uint32_t coff[NQ];           // OUT_NV12: offset of the U / V dword of quad slot j (even rows; out of range otherwise)
     bool part_any[NQ];
     uint32_t wq[NQ][NCON][4];    // blend weights as 24-bit integer factors (blend_weight_q23)
     const bool with_car = !SUMS && a.car != nullptr;
     const __amdgpu_buffer_rsrc_t rcar = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(with_car ? a.car : a.out), 0,
                                                                           with_car ? (uint32_t)img_bytes : 0u, kBufferWord3);
     uint32_t car_or = 0;
+    // byte offset of quad slot j in the car sprite (BGR; OUT_NV12: 3 x the Y offset -- 3 x kPairNoGroup is kPairNoGroup modulo 2^32)
+    auto car_off = [&](int j) { return OUT_NV12 ? (int)(ooff_masked[j] * 3u) : (int)ooff_masked[j]; };
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
         const int sidx = unit_slot(wave, j);
@@ -810,18 +852,26 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
             for (int p = 0; p < 4; ++p) { wq[j][0][p] = blend_weight_q23(w[p] & 255u); wq[j][NCON - 1][p] = blend_weight_q23((w[p] >> 8) & 255u); }
         }
         const bool store = 4 * qx < uw && row < uh && x >= 0 && x < a.pitch && !(unit_no_contributor(e0) && (e0 & kUnitSkip));
-        ooff_masked[j] = store ? ooff : kPairNoGroup;   // out of range of the image's buffer descriptor: neither read (car) nor written
-        {
+        // out of range of the image's buffer descriptor: neither read (car) nor written
+        ooff_masked[j] = store ? (OUT_NV12 ? nv12_y_offset(a.pitch, x, uy + row) : ooff) : kPairNoGroup;
+        if (OUT_NV12) {
+            coff[j] = (store && !((uy + row) & 1)) ? nv12_uv_offset(a.pitch, a.bh, x, uy + row) : kPairNoGroup;
+        } else {
             const bool whole = ((__builtin_amdgcn_ballot_w64(store) >> (lane & ~3)) & 0xfull) == 0xfull;
             ooff16[j] = (store16 && whole && (lane & 3) < 3) ? ooff + 4u * (uint32_t)(lane & 3) : kPairNoGroup;
             const bool part = store && !(store16 && whole);
             part_bits |= (part ? 1u : 0u) << j;
             part_any[j] = __builtin_amdgcn_ballot_w64(part) != 0;
         }
-        const pair_u32x3 c = __builtin_amdgcn_raw_buffer_load_b96(rcar, (int)ooff_masked[j], 0, 0);
+        const pair_u32x3 c = __builtin_amdgcn_raw_buffer_load_b96(rcar, car_off(j), 0, 0);
         car_or |= c.x | c.y | c.z;
     }
     const bool car_any = __builtin_amdgcn_ballot_w64(car_or != 0) != 0;
+    // OUT_NV12: the Y dword and the U / V dword of quad slot j to image `ro` (masked slots and odd rows: out of range, not written)
+    auto store_nv12 = [&](int j, uint32_t yw, uint32_t uvw, const __amdgpu_buffer_rsrc_t ro) {
+        unit_store_dword(yw, ro, (int)ooff_masked[j], streaming);
+        unit_store_dword(uvw, ro, (int)coff[j], streaming);
+    };
     // the 12 output bytes of quad slot j to image `ro` (unit_store_quad16 / unit_store_quad)
     auto store_slot = [&](int j, uint32_t d0, uint32_t d1, uint32_t d2, const __amdgpu_buffer_rsrc_t ro) {
         if (BEVW_UNIT_STORE16 == 0) {
@@ -838,11 +888,18 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
         // (balance: zeros -- the sprite is added after the gains, as in the reference)
 #pragma unroll 1
         for (int b = b_begin; b < b_end; ++b) {
-            const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)b * img_bytes, 0, (uint32_t)img_bytes, kBufferWord3);
+            const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)b * out_bytes, 0, (uint32_t)out_bytes, kBufferWord3);
 #pragma unroll
             for (int j = 0; j < NQ; ++j) {
-                const pair_u32x3 c = __builtin_amdgcn_raw_buffer_load_b96(rcar, (int)ooff_masked[j], 0, 0);   // zeros without a sprite
-                store_slot(j, c.x, c.y, c.z, ro);
+                const pair_u32x3 c = __builtin_amdgcn_raw_buffer_load_b96(rcar, car_off(j), 0, 0);   // zeros without a sprite
+                if (OUT_NV12) {
+                    uint32_t P[4], yw, uvw;
+                    unpack_quad(c.x, c.y, c.z, P);
+                    nv12_quad(P, yw, uvw);   // zeros: (16, 128, 128)
+                    store_nv12(j, yw, uvw, ro);
+                } else {
+                    store_slot(j, c.x, c.y, c.z, ro);
+                }
             }
             // its channel sums are zero, and it says so for every frame: no entry depends on what the buffer held before (another layout's sums)
             if (SUMS && wave == 0 && lane < 3) a.psums[((size_t)b * a.nsum + unit) * 3 + lane] = 0u;
@@ -933,7 +990,7 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
                     P[p] = v;
                 }
                 if (car_any) {
-                    const pair_u32x3 c = __builtin_amdgcn_raw_buffer_load_b96(rcar, (int)ooff_masked[j], 0, 0);
+                    const pair_u32x3 c = __builtin_amdgcn_raw_buffer_load_b96(rcar, car_off(j), 0, 0);
                     add_car(P, c.x, c.y, c.z);
                 }
                 pack_pixels(P, d[j][0], d[j][1], d[j][2]);
@@ -942,7 +999,7 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
             uint32_t acc[4][3];
 #pragma unroll
             for (int p = 0; p < 4; ++p) bilinear_pairs(pw[i0[j][0][p]], pw[i1[j][0][p]], wxa[j][0][p], wxa[j][0][p] << 16, wy[j][0][p], acc[p]);
-            if (NCON == 1 && !car_any) {
+            if (NCON == 1 && !car_any && !OUT_NV12) {
                 pack_accs(acc, d[j][0], d[j][1], d[j][2]);
             } else {
                 uint32_t P[4];
@@ -965,10 +1022,11 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
                     }
                 }
                 if (car_any) {     // uniform over the wave; the sprite is not kept in registers across the frame loop
-                    const pair_u32x3 c = __builtin_amdgcn_raw_buffer_load_b96(rcar, (int)ooff_masked[j], 0, 0);
+                    const pair_u32x3 c = __builtin_amdgcn_raw_buffer_load_b96(rcar, car_off(j), 0, 0);
                     add_car(P, c.x, c.y, c.z);
                 }
-                pack_pixels(P, d[j][0], d[j][1], d[j][2]);
+                if (OUT_NV12) nv12_quad(P, d[j][0], d[j][1]);   // d[j][0] = Y, d[j][1] = U / V
+                else pack_pixels(P, d[j][0], d[j][1], d[j][2]);
             }
             if (SUMS) {
                 // the lane's own channel sums over its quad slots, from the 12 packed bytes B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3 (no sprite in
@@ -988,10 +1046,13 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
         }
         if (DB) land((ring + 1) % D);    // frame b+1 into the other half: nobody reads it before the barrier
         {
-            uint8_t *img = a.out + (size_t)frame_of(b) * img_bytes;   // past the chunk: re-writes the last frame with the same bytes
-            const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(img, 0, (uint32_t)img_bytes, kBufferWord3);
+            uint8_t *img = a.out + (size_t)frame_of(b) * out_bytes;   // past the chunk: re-writes the last frame with the same bytes
+            const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(img, 0, (uint32_t)out_bytes, kBufferWord3);
 #pragma unroll
-            for (int j = 0; j < NQ; ++j) store_slot(j, d[j][0], d[j][1], d[j][2], ro);
+            for (int j = 0; j < NQ; ++j) {
+                if (OUT_NV12) store_nv12(j, d[j][0], d[j][1], ro);
+                else store_slot(j, d[j][0], d[j][1], d[j][2], ro);
+            }
         }
         block_lds_barrier();       // DB: half[ring ^ 1] complete for everybody, half[ring] free for frame b+2; else: the patch is free
         if (SUMS && wave == 0 && lane < 3 && b < b_end) {
@@ -1018,14 +1079,14 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
 
 // block -> (chunk, unit) of the list of ALL units in the partition's own (spatial) order, class in bits 28..31: neighbouring units run
 // at the same time on the same XCD, whatever their class, so the two halves of a sector that two units share meet in the L2
-template <bool BLEND, bool SUMS, bool NV12>
+template <bool BLEND, bool SUMS, bool NV12, bool OUT_NV12 = false>
 __device__ __forceinline__ void plan_unit_any(const PlanArgs &a, uint32_t block_id, uint8_t *lds, uint4 *wave_sums)
 {
     uint32_t chunk, group;
     if (!plan_block_map(a, block_id, chunk, group)) return;
     if ((int)group >= a.nlist) return;
     const uint32_t e = __builtin_amdgcn_readfirstlane(a.tile_list[group]), unit = e & 0x0fffffffu;
-#define BEVW_UNIT_CASE(C) case C: plan_unit_run<BLEND, SUMS, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C], false, NV12>(a, chunk, unit, lds, wave_sums); break;
+#define BEVW_UNIT_CASE(C) case C: plan_unit_run<BLEND, SUMS, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C], false, NV12, OUT_NV12>(a, chunk, unit, lds, wave_sums); break;
     switch (e >> 28) {
         BEVW_UNIT_CASE(0) BEVW_UNIT_CASE(1) BEVW_UNIT_CASE(2) BEVW_UNIT_CASE(3)
         // class 4 (two quads per lane, two contributors): with float blend weights (rounds 3 - 5) its blend variant needed 177 .. 197 VGPRs and
@@ -1035,7 +1096,7 @@ __device__ __forceinline__ void plan_unit_any(const PlanArgs &a, uint32_t block_
 #if !BEVW_UNIT_NO_BIG   // (experiment builds without the (4, 4) class: every other class fits 128 VGPRs = 4 waves per SIMD; plans then need BEVW_UNIT_BIG=0)
         BEVW_UNIT_CASE(7)
 #endif
-        default: plan_unit_run<BLEND, SUMS, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6], false, NV12>(a, chunk, unit, lds, wave_sums); break;
+        default: plan_unit_run<BLEND, SUMS, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6], false, NV12, OUT_NV12>(a, chunk, unit, lds, wave_sums); break;
     }
 #undef BEVW_UNIT_CASE
 }
@@ -1065,6 +1126,16 @@ __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_
 {
     __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
     plan_unit_any<BLEND, false, true>(a, blockIdx.x, patch, nullptr);
+}
+
+// NV12 BEV images (bevw_set_output_format): the same launch over the OUT_NV12 instantiation of plan_unit_run, for BGR or NV12 frame sets
+// (IN_NV12: a.un_gsrc holds the NV12 group lists).  No channel sums: the balance modes store the BGR pre-gain image and convert in the gain
+// pass.  Named apart from k_plan_units (the four BGR instantiations) and k_units_nv12.
+template <bool BLEND, bool IN_NV12>
+__global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_out_nv12(PlanArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
+    plan_unit_any<BLEND, false, IN_NV12, true>(a, blockIdx.x, patch, nullptr);
 }
 
 // wide plans (analytic projection): every unit class in one launch, partition order, as plan_unit_any

@@ -268,6 +268,8 @@ struct bevw_remapper {
     bool plan_ready = false;
     int ties_even = 0;    // BEVW_COMPAT_REMAP at creation: half-to-even ties -> the per-pixel kernel (the plan's arithmetic rounds half up)
     int input_format = BEVW_INPUT_BGR;   // bevw_remapper_set_input_format
+    int output_format = BEVW_OUTPUT_BGR; // bevw_remapper_set_output_format
+    bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
 };
 
 // cv2.remap as a 1-camera stitch: every destination pixel has exactly one contributor with mask 255.
@@ -309,15 +311,22 @@ static int remapper_alloc(int device, int sw, int sh, int dw, int dh, bevw_remap
     return BEVW_OK;
 }
 
-// nv12: the sources are NV12 frames (bevw_remapper_set_input_format)
+// nv12: the sources are NV12 frames (bevw_remapper_set_input_format); out_nv12: the destinations are dense NV12 images
+// (bevw_remapper_set_output_format)
 static int remap_launch(hipStream_t st, const uint8_t *d_src, int sw, int sh, const int16_t *m1, const uint16_t *m2,
-                        int dw, int dh, int batch, uint8_t *d_dst, int ties_even = 0, bool nv12 = false)
+                        int dw, int dh, int batch, uint8_t *d_dst, int ties_even = 0, bool nv12 = false, bool out_nv12 = false)
 {
     for_each_chunk(batch, [&](int b0, int nb) {
-        with_flags([&](auto nv) {
-            hipLaunchKernelGGL((k_remap_lut<nv>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, d_src + (size_t)b0 * frame_bytes_of(sw, sh, nv),
-                               sw, sh, m1, m2, dw, dh, d_dst + (size_t)b0 * dw * dh * 3, ties_even);
-        }, nv12);
+        if (out_nv12)
+            with_flags([&](auto nv) {
+                hipLaunchKernelGGL((k_remap_lut<nv, true>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, d_src + (size_t)b0 * frame_bytes_of(sw, sh, nv),
+                                   sw, sh, m1, m2, dw, dh, d_dst + (size_t)b0 * image_bytes_of(dw, dh, true), ties_even);
+            }, nv12);
+        else
+            with_flags([&](auto nv) {
+                hipLaunchKernelGGL((k_remap_lut<nv>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, d_src + (size_t)b0 * frame_bytes_of(sw, sh, nv),
+                                   sw, sh, m1, m2, dw, dh, d_dst + (size_t)b0 * dw * dh * 3, ties_even);
+            }, nv12);
     });
     return launch_check("k_remap_lut");
 }
@@ -505,11 +514,25 @@ int bevw_remap_device(bevw_remapper *r, const void *d_src, int batch, void *d_ds
     if (!r || !d_src || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
-    if (r->plan_ready && ((((uintptr_t)d_src) | ((uintptr_t)d_dst)) & 3u) == 0)
+    // (NV12 images on the plan need dword-aligned quads in the caller's rows: a width that is not a multiple of 4 takes the per-pixel kernel)
+    if (r->plan_ready && ((((uintptr_t)d_src) | ((uintptr_t)d_dst)) & 3u) == 0 && (!r->out_nv12() || r->dw % 4 == 0))
         return plan_stitch(r->plan, r->stream, (const uint8_t *)d_src, batch, false, false, nullptr, nullptr, nullptr, nullptr,
                            (uint8_t *)d_dst);
     return remap_launch(r->stream, (const uint8_t *)d_src, r->sw, r->sh, r->map1.as<int16_t>(), r->map2.as<uint16_t>(),
-                        r->dw, r->dh, batch, (uint8_t *)d_dst, r->ties_even, r->input_format == BEVW_INPUT_NV12);
+                        r->dw, r->dh, batch, (uint8_t *)d_dst, r->ties_even, r->input_format == BEVW_INPUT_NV12, r->out_nv12());
+}
+
+int bevw_remapper_set_output_format(bevw_remapper *r, int format)
+{
+    if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    if (format != BEVW_OUTPUT_BGR && format != BEVW_OUTPUT_NV12) return fail(BEVW_E_INVALID, "unknown output format %d", format);
+    if (format == BEVW_OUTPUT_NV12 && (r->dw % 2 || r->dh % 2))
+        return fail(BEVW_E_INVALID, "NV12 output needs an even destination width and height, got %dx%d", r->dw, r->dh);
+    BEVW_TRY(use_device(r->device));
+    HIP_TRY(hipStreamSynchronize(r->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
+    r->output_format = format;
+    r->plan.out_nv12 = r->out_nv12();
+    return BEVW_OK;
 }
 
 int bevw_remapper_set_input_format(bevw_remapper *r, int format)
@@ -530,7 +553,7 @@ int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst)
     if (!r || !src || !dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
-    const size_t nin = (size_t)batch * frame_bytes_of(r->sw, r->sh, r->input_format == BEVW_INPUT_NV12), nout = (size_t)batch * r->dw * r->dh * 3;
+    const size_t nin = (size_t)batch * frame_bytes_of(r->sw, r->sh, r->input_format == BEVW_INPUT_NV12), nout = (size_t)batch * image_bytes_of(r->dw, r->dh, r->out_nv12());
     BEVW_TRY(r->in.reserve(nin));
     BEVW_TRY(r->out.reserve(nout));
     HIP_TRY(hipMemcpyAsync(r->in.p, src, nin, hipMemcpyHostToDevice, r->stream));
@@ -691,9 +714,12 @@ struct bevw_handle {
     int input_format = BEVW_INPUT_BGR;   // bevw_set_input_format
     bool nv12() const { return input_format == BEVW_INPUT_NV12; }
     size_t set_bytes() const { return frame_bytes_of(cfg.frame_width, cfg.frame_height, nv12()) * 4; }   // one camera frame set as the handle reads it
+    int output_format = BEVW_OUTPUT_BGR;   // bevw_set_output_format
+    bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
     int compat[BEVW_COMPAT_KEYS] = {1, 1, 0, 0};   // bevw_set_compat values at bevw_build: a handle keeps the arithmetic it was built with
     int pitch_request = BEVW_PITCH_DENSE;   // bevw_set_output_pitch
     int pitch_px = 0;                 // pixels per row of the device-side BEV images (== bev_width unless a pitch was requested)
+    size_t out_image_bytes() const { return image_bytes_of(pitch_px, cfg.bev_height, out_nv12()); }   // one device-side BEV image
     DevBuf car_pitched;               // the car sprite with rows of pitch_px pixels (gain pass of a pitched handle)
     AnalyticRig arig;                 // filled by bevw_build
     Plan aplan;                       // analytic modes: the WIDE unit schedule compiled from the projection (analytic_units_build)
@@ -763,6 +789,14 @@ static int stitch_per_pixel(bevw_handle *h, const uint8_t *d_frames, int batch, 
     for_each_chunk(batch, [&](int b0, int nb) {
         const dim3 grid((c.bev_width + 255) / 256, c.bev_height, nb), block(256);
         const uint8_t *fr = d_frames + (size_t)b0 * h->set_bytes();
+        if (h->out_nv12() && !c.balance) {   // NV12 images (the balance modes store the BGR pre-gain image: the gain pass converts)
+            uint8_t *o = d_out + (size_t)b0 * image_bytes_of(c.bev_width, c.bev_height, true);
+            with_flags([&](auto bl, auto nv) {
+                hipLaunchKernelGGL((k_stitch_pp<bl, false, nv, true>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height, T, c.bev_width,
+                                   c.bev_height, nullptr, tab, d_car, nullptr, o, h->compat[BEVW_COMPAT_REMAP]);
+            }, c.blend != 0, h->nv12());
+            return;
+        }
         uint8_t *o = d_out + (size_t)b0 * c.bev_width * c.bev_height * 3;
         with_flags([&](auto bl, auto ba, auto nv) {
             hipLaunchKernelGGL((k_stitch_pp<bl, ba, nv>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height, T, c.bev_width,
@@ -901,7 +935,11 @@ static int gain_pass(bevw_handle *h, hipStream_t st, const uint8_t *gain_in, con
         const int k0 = b0 + k;
         int nsum = 0;
         const uint32_t *ps = (from_plan && lut_ok) ? plan_sum_entries(h->plan, k0, nsum) : nullptr;
-        if (lut_ok)
+        if (h->out_nv12())   // NV12 images: gain_in is a BGR buffer of the handle's own, d_out the caller's NV12 images
+            hipLaunchKernelGGL(k_gain_lut_nv12, dim3(xcd_frame_grid(32, (unsigned)nb)), dim3(256), 0, st, gain_in + (size_t)(k0 - b0) * npx * 3, npx,
+                               h->chsums.as<unsigned long long>() + (size_t)k0 * 3, gain_car, d_out + (size_t)k0 * h->out_image_bytes(), 32u,
+                               (uint32_t)nb, h->compat[BEVW_COMPAT_ADDWEIGHTED] ? 0 : 1, npx_true, ps, nsum, h->pitch_px, c.bev_height);
+        else if (lut_ok)
             hipLaunchKernelGGL(k_gain_lut, dim3(xcd_frame_grid(32, (unsigned)nb)), dim3(256), 0, st, gain_in + (size_t)(k0 - b0) * npx * 3, npx,
                                h->chsums.as<unsigned long long>() + (size_t)k0 * 3, gain_car, d_out + (size_t)k0 * npx * 3, 32u,
                                (uint32_t)nb, h->compat[BEVW_COMPAT_ADDWEIGHTED] ? 0 : 1, npx_true, ps, nsum);
@@ -931,7 +969,8 @@ static int color_balance(hipStream_t st, uint8_t *d_img, size_t npx, int batch, 
 static int gain_car(bevw_handle *h, const uint8_t *d_car, const uint8_t *&car)
 {
     car = d_car;
-    if (!d_car || h->pitch_px == h->cfg.bev_width) return BEVW_OK;
+    // (NV12 images: the gain pass reads the sprite in dwords -- an unaligned one is copied too)
+    if (!d_car || (h->pitch_px == h->cfg.bev_width && !(h->out_nv12() && ((uintptr_t)d_car & 3u)))) return BEVW_OK;
     BEVW_TRY(h->car_pitched.reserve((size_t)h->pitch_px * h->cfg.bev_height * 3));
     BEVW_TRY(plan_pad_image(h->stream, d_car, h->cfg.bev_width, h->pitch_px, h->cfg.bev_height, h->car_pitched.as<uint8_t>()));
     car = h->car_pitched.as<uint8_t>();
@@ -978,7 +1017,12 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
     // one more BEV batch of HBM (0.9 GB at batch 256).  No room for it: the gain pass runs in place -- never an error
     static const int oop = [] { const char *s = getenv("BEVW_GAIN_OOP"); return s ? atoi(s) : 1; }();
     uint8_t *gain_in = d_out;
-    if (oop && npx % 4 == 0 && h->pre.reserve(npx * 3 * slots) == BEVW_OK) gain_in = h->pre.as<uint8_t>();
+    if (h->out_nv12()) {   // NV12 images: the BGR pre-gain image never fits the caller's buffer -- always a buffer of its own
+        BEVW_TRY(h->pre.reserve(npx * 3 * slots));
+        gain_in = h->pre.as<uint8_t>();
+    } else if (oop && npx % 4 == 0 && h->pre.reserve(npx * 3 * slots) == BEVW_OK) {
+        gain_in = h->pre.as<uint8_t>();
+    }
     const bool pre_ring = ring && gain_in != d_out;
     const uint8_t *car = nullptr;
     BEVW_TRY(gain_car(h, d_car, car));
@@ -1035,18 +1079,26 @@ static int run_device(bevw_handle *h, const uint8_t *d_frames, int batch, const 
                                  h->vsums.as<unsigned long long>(), h->deltas.as<int>(), h->nv12()));
         HIP_TRY(hipMemsetAsync(h->chsums.p, 0, sizeof(unsigned long long) * 3 * (size_t)batch, h->stream));
     }
+    // NV12 images: the balance modes stitch their BGR pre-gain image into a buffer of the handle's own (the gain pass converts); without
+    // balance the plan writes NV12 itself where its quads are whole dwords of the caller's rows (no padded scratch), else the per-pixel kernel
+    uint8_t *st_out = d_out;
+    if (h->out_nv12() && c.balance) {
+        BEVW_TRY(h->pre.reserve(npx * 3 * (size_t)batch));
+        st_out = h->pre.as<uint8_t>();
+    }
+    const bool plan_ok = !h->out_nv12() || c.balance || h->plan.pitch == h->pitch_px;
     if (h->projection != BEVW_PROJ_LUT) {
         BEVW_TRY(stitch_analytic(h, d_frames, batch, d_car, d_out));
-    } else if (h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4) {
+    } else if (h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && plan_ok) {
         BEVW_TRY(plan_stitch(h->plan, h->stream, d_frames, batch, c.blend != 0, c.balance != 0, h->deltas.as<int>(),
-                             h->hsv.as<HsvTables>(), d_car, h->chsums.as<unsigned long long>(), d_out));
+                             h->hsv.as<HsvTables>(), d_car, h->chsums.as<unsigned long long>(), st_out));
     } else {
-        BEVW_TRY(stitch_per_pixel(h, d_frames, batch, d_car, d_out));
+        BEVW_TRY(stitch_per_pixel(h, d_frames, batch, d_car, st_out));
     }
     if (c.balance) {
         const uint8_t *car = nullptr;
         BEVW_TRY(gain_car(h, d_car, car));
-        BEVW_TRY(gain_pass(h, h->stream, d_out, car, d_car, d_out, 0, batch, npx % 4 == 0 && aligned4));
+        BEVW_TRY(gain_pass(h, h->stream, st_out, car, d_car, d_out, 0, batch, npx % 4 == 0 && aligned4));
     }
     return BEVW_OK;
 }
@@ -1184,6 +1236,7 @@ int bevw_build(bevw_handle *h)
     h->pitch_px = h->pitch_request == BEVW_PITCH_DENSE ? bw : (h->pitch_request == BEVW_PITCH_ALIGNED ? (bw + 63) / 64 * 64 : h->pitch_request);
     BEVW_TRY(plan_build(h->plan, st, T, cfg.frame_width, cfg.frame_height, bw, bh, ncams, h->pitch_px != bw ? h->pitch_px : 0, cfg.blend != 0));
     h->plan.nv12 = h->nv12();
+    h->plan.out_nv12 = h->out_nv12();
     if (h->shard_n) {
         if (!h->plan.usable) return fail(BEVW_E_INVALID, "camera shard needs the tile plan: %d contributors on some pixel", h->plan.max_contrib);
         // bounding box of the owned masks, widened to multiples of 4 pixels in x so that packed rows stay dword aligned
@@ -1292,6 +1345,7 @@ int bevw_set_projection(bevw_handle *h, int mode)
     if (mode != BEVW_PROJ_LUT && mode != BEVW_PROJ_ANALYTIC && mode != BEVW_PROJ_ANALYTIC_F32) return fail(BEVW_E_INVALID, "unknown projection mode %d", mode);
     if (mode != BEVW_PROJ_LUT && h->shard_n) return fail(BEVW_E_INVALID, "analytic projection is not available on camera-shard handles");
     if (mode != BEVW_PROJ_LUT && h->nv12()) return fail(BEVW_E_INVALID, "analytic projection is not available with NV12 input");
+    if (mode != BEVW_PROJ_LUT && h->out_nv12()) return fail(BEVW_E_INVALID, "analytic projection is not available with NV12 output");
     h->projection = mode;
     return BEVW_OK;
 }
@@ -1355,9 +1409,41 @@ int bevw_input_format(bevw_handle *h)
     return h->input_format;
 }
 
-// [batch * rows][pitch_px][3] on the device -> dense [batch * rows][bw][3] on the host (rows compacted inside the copy)
+int bevw_set_output_format(bevw_handle *h, int format)
+{
+    if (!h) return fail(BEVW_E_INVALID, "null handle");
+    if (format != BEVW_OUTPUT_BGR && format != BEVW_OUTPUT_NV12) return fail(BEVW_E_INVALID, "unknown output format %d", format);
+    if (format == BEVW_OUTPUT_NV12) {
+        const bevw_config &c = h->cfg;
+        if (c.bev_width % 2 || c.bev_height % 2)
+            return fail(BEVW_E_INVALID, "NV12 output needs an even BEV width and height, got %dx%d", c.bev_width, c.bev_height);
+        if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "NV12 output is not available with the analytic projection");
+        if (h->shard_n) return fail(BEVW_E_INVALID, "NV12 output is not available on camera-shard handles");
+    }
+    BEVW_TRY(use_device(h->cfg.device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
+    if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
+    h->output_format = format;
+    h->plan.out_nv12 = h->out_nv12();
+    return BEVW_OK;
+}
+
+int bevw_output_format(bevw_handle *h)
+{
+    if (!h) return fail(BEVW_E_INVALID, "null handle");
+    return h->output_format;
+}
+
+// [batch * rows][pitch_px][3] on the device -> dense [batch * rows][bw][3] on the host (rows compacted inside the copy).  NV12 images:
+// `rows` counts BEV rows; the copy moves batch * rows * 3 / 2 rows of pitch_px -> bw bytes (the Y and U / V planes of every image)
 static int download_images(bevw_handle *h, uint8_t *out, const void *d_src, size_t rows)
 {
+    if (h->out_nv12()) {
+        const size_t row_bytes = (size_t)h->cfg.bev_width, src_pitch = (size_t)h->pitch_px, nrows = rows * 3 / 2;
+        if (src_pitch == row_bytes) HIP_TRY(hipMemcpyAsync(out, d_src, row_bytes * nrows, hipMemcpyDeviceToHost, h->stream));
+        else HIP_TRY(hipMemcpy2DAsync(out, row_bytes, d_src, src_pitch, row_bytes, nrows, hipMemcpyDeviceToHost, h->stream));
+        return BEVW_OK;
+    }
     const size_t row_bytes = (size_t)h->cfg.bev_width * 3, src_pitch = (size_t)h->pitch_px * 3;
     if (src_pitch == row_bytes) HIP_TRY(hipMemcpyAsync(out, d_src, row_bytes * rows, hipMemcpyDeviceToHost, h->stream));
     else HIP_TRY(hipMemcpy2DAsync(out, row_bytes, d_src, src_pitch, row_bytes, rows, hipMemcpyDeviceToHost, h->stream));
@@ -1381,7 +1467,7 @@ int bevw_run(bevw_handle *h, const uint8_t *frames, int batch, const uint8_t *ca
     if (batch == 0) return BEVW_OK;
     const bevw_config &c = h->cfg;
     const size_t nin = (size_t)batch * h->set_bytes();
-    const size_t bev = (size_t)c.bev_width * c.bev_height * 3, dbev = (size_t)h->pitch_px * c.bev_height * 3;
+    const size_t bev = (size_t)c.bev_width * c.bev_height * 3, dbev = h->out_image_bytes();
     BEVW_TRY(h->in.reserve(nin));
     BEVW_TRY(h->out.reserve(dbev * batch));
     HIP_TRY(hipMemcpyAsync(h->in.p, frames, nin, hipMemcpyHostToDevice, h->stream));
@@ -1407,7 +1493,7 @@ int bevw_run_cameras(bevw_handle *h, const uint8_t *front, const uint8_t *back, 
     const bevw_config &c = h->cfg;
     const size_t frame = h->set_bytes() / 4, bev = (size_t)c.bev_width * c.bev_height * 3;
     BEVW_TRY(h->in.reserve(frame * 4));
-    BEVW_TRY(h->out.reserve((size_t)h->pitch_px * c.bev_height * 3));
+    BEVW_TRY(h->out.reserve(h->out_image_bytes()));
     const uint8_t *src[4] = {front, back, left, right};
     for (int i = 0; i < 4; ++i)
         HIP_TRY(hipMemcpyAsync(h->in.as<uint8_t>() + frame * i, src[i], frame, hipMemcpyHostToDevice, h->stream));
@@ -1477,6 +1563,7 @@ int bevw_set_camera_shard(bevw_handle *h, const int32_t *cams, int ncams)
         if (k && cams[k] <= cams[k - 1]) return fail(BEVW_E_INVALID, "shard cameras must be distinct and ascending");
     }
     if (h->nv12()) return fail(BEVW_E_INVALID, "camera-shard handles take BGR frames only (NV12 input is set)");
+    if (h->out_nv12()) return fail(BEVW_E_INVALID, "camera-shard handles write BGR images only (NV12 output is set)");
     h->shard_n = ncams;
     for (int k = 0; k < 4; ++k) h->shard_cams[k] = k < ncams ? cams[k] : cams[0];
     h->built = false;
@@ -1682,6 +1769,7 @@ int bevw_combine_device(bevw_handle *h, const void *const *d_parts, const int32_
     BEVW_TRY(need_built(h));
     if (!d_parts || !boxes || !d_out || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
     if (nparts < 1 || nparts > 8) return fail(BEVW_E_INVALID, "1..8 parts");
+    if (h->out_nv12()) return fail(BEVW_E_INVALID, "bevw_combine_device writes BGR images (the handle's output format is NV12)");
     const bevw_config &c = h->cfg;
     const int bw = c.bev_width, bh = c.bev_height;
     CombineParts parts;

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define BEVW_ABI_VERSION 6
+#define BEVW_ABI_VERSION 7
 
 typedef enum bevw_status {
     BEVW_OK = 0,
@@ -175,6 +175,32 @@ int bevw_output_pitch(bevw_handle *h);   /* pixels per row of the handle's devic
 #define BEVW_INPUT_NV12 1
 int bevw_set_input_format(bevw_handle *h, int format);
 int bevw_input_format(bevw_handle *h);   /* BEVW_INPUT_BGR or BEVW_INPUT_NV12 */
+/* BEV images as NV12 (what a hardware video encoder takes).  With BEVW_OUTPUT_NV12 one device image is a Y plane of BH rows of `pitch`
+ * bytes followed by one interleaved U / V plane (U first) of BH/2 rows of `pitch` bytes, where pitch = bevw_output_pitch() (unchanged by the
+ * format: BEV_WIDTH, BEV_WIDTH rounded up to 64, or the explicit multiple of 4): pitch * BH * 3 / 2 bytes per image, images back to back.
+ * An encoder takes d_out + k * pitch * BH * 3 / 2 as an NV12 surface with one pitch for both planes.  bevw_run and bevw_run_cameras
+ * return dense host arrays of BH*3/2 rows of BW bytes per image (rows compacted inside the copy, as for BGR).  The result is, byte for
+ * byte, the NV12 form of what the same handle returns with BGR output: cv2.cvtColor(bgr, cv2.COLOR_BGR2YUV_I420) with the U and V
+ * planes interleaved -- OpenCV's RGB8toYUV420pInvoker, BT.601 limited range, 20-bit fixed point:
+ *   Y = (269484 R + 528482 G + 102760 B + (16 << 20) + (1 << 19)) >> 20
+ *   U = (-155188 R - 305135 G + 460324 B + (128 << 20) + (1 << 19)) >> 20
+ *   V = (460324 R - 385875 G - 74448 B + (128 << 20) + (1 << 19)) >> 20
+ * with the U / V of each 2 x 2 block taken from its top-left pixel alone (no averaging).  Y stays in [16, 235] and U, V in [16, 240];
+ * black -- BEV pixels no camera covers, units without a contributor when no car is given -- is (16, 128, 128).  The conversion is the
+ * last step: after interpolation, blend weights, saturating adds, the car sprite (still a BGR [BH][BW][3] input) and, in the balance
+ * modes, the gains.  The arithmetic is UNPINNED: restated from OpenCV's source and checked against a NumPy statement of it, not yet
+ * against a real cv2 (tests/golden/make_nv12_out_goldens_with_cv2.py writes the probe that would pin it).  Bytes of the padding columns
+ * are unspecified.  Combines freely with bevw_set_input_format.  Call before or after bevw_build; the tile plan is the same for both
+ * formats.  Refused with BEVW_E_INVALID:
+ *   - an odd BW or BH;
+ *   - together with BEVW_PROJ_ANALYTIC / BEVW_PROJ_ANALYTIC_F32 (in either order);
+ *   - on camera-shard handles (in either order with bevw_set_camera_shard), and by bevw_combine_device.
+ * Not provided: I420, NV21, YUYV, BT.709 or full range, averaged chroma, separate plane pointers, JPEG encoding from NV12.  The per-camera
+ * tools (bevw_camera_undistort, ...) keep writing BGR. */
+#define BEVW_OUTPUT_BGR 0
+#define BEVW_OUTPUT_NV12 1
+int bevw_set_output_format(bevw_handle *h, int format);
+int bevw_output_format(bevw_handle *h);   /* BEVW_OUTPUT_BGR or BEVW_OUTPUT_NV12 */
 /* The reference's own call shape, bev(front, back, left, right, car) (surroundBEV.py:312, main.py:84): four separate
  * [FH][FW][3] host arrays (no packing copy on the host), one frame set, out [BH][BW][3]. */
 int bevw_run_cameras(bevw_handle *h, const uint8_t *front, const uint8_t *back, const uint8_t *left, const uint8_t *right,
@@ -283,6 +309,10 @@ int bevw_remap_device(bevw_remapper *r, const void *d_src, int batch, void *d_ds
  * [batch][src_h*3/2][src_w] NV12 frames and write what cv2.remap writes for cv2.cvtColor(src, cv2.COLOR_YUV2BGR_NV12), in either
  * BEVW_COMPAT_REMAP mode.  Refused (BEVW_E_INVALID) for an odd src_w or src_h. */
 int bevw_remapper_set_input_format(bevw_remapper *r, int format);
+/* BEVW_OUTPUT_NV12 (bevw_set_output_format has the layout and the arithmetic): bevw_remap and bevw_remap_device write dst as dense NV12
+ * images [batch][dst_h*3/2][dst_w] -- the NV12 form of what the BGR remapper writes.  Combines with either input format.  Refused
+ * (BEVW_E_INVALID) for an odd dst_w or dst_h. */
+int bevw_remapper_set_output_format(bevw_remapper *r, int format);
 int bevw_remapper_sync(bevw_remapper *r);
 int bevw_remapper_timer_start(bevw_remapper *r);
 int bevw_remapper_timer_stop(bevw_remapper *r, float *elapsed_ms);
