@@ -104,7 +104,8 @@ def _snapshot_config(blend=False, balance=False, device=0, schedule=_ffi.SCHED_A
 class _Engine:
     """Owns one bevw_handle (4 cameras + masks on the device)."""
 
-    def __init__(self, rig, blend, balance, device, schedule, output_pitch=0, input_format=_ffi.INPUT_BGR, output_format=_ffi.OUTPUT_BGR):
+    def __init__(self, rig, blend, balance, device, schedule, output_pitch=0, input_format=_ffi.INPUT_BGR, output_format=_ffi.OUTPUT_BGR,
+                 input_pitch=0):
         _ffi.require_device()
         self.cfg = _snapshot_config(blend, balance, device, schedule)
         h = C.c_void_p()
@@ -117,6 +118,8 @@ class _Engine:
                 check(lib().bevw_set_output_pitch(self.h, int(output_pitch)))
             if input_format != _ffi.INPUT_BGR:
                 check(lib().bevw_set_input_format(self.h, int(input_format)))
+            if input_pitch:
+                check(lib().bevw_set_input_pitch(self.h, int(input_pitch)))
             if output_format != _ffi.OUTPUT_BGR:
                 check(lib().bevw_set_output_format(self.h, int(output_format)))
             check(lib().bevw_build(self.h))
@@ -295,7 +298,8 @@ class BevGenerator:
     """
 
     def __init__(self, blend=args.BLEND_FLAG, balance=args.BALANCE_FLAG, *, rig=None, device=0,
-                 schedule=_ffi.SCHED_AUTO, projection='lut', output_pitch='auto', input_format='bgr', output_format='bgr'):
+                 schedule=_ffi.SCHED_AUTO, projection='lut', output_pitch='auto', input_format='bgr', output_format='bgr',
+                 input_pitch=None):
         """blend / balance: as in the reference (surroundBEV.py:283).  Additive keywords: rig ({name: (K, D, H)} instead of the
         data directory), device, schedule, and projection -- 'lut' (default: the reference's table-driven path, bit-exact against
         the oracle) 'analytic' (inverse homography + fisheye model evaluated per frame and pixel in fp64, no tables; not the
@@ -312,8 +316,12 @@ class BevGenerator:
         Y plane followed by the interleaved U / V plane; on the device rows of ``out_pitch`` bytes for both planes).  An 'nv12' generator
         returns, byte for byte, the NV12 form of what a 'bgr' one returns: cv2.cvtColor(bev, cv2.COLOR_BGR2YUV_I420) with U and V
         interleaved, the chroma of each 2 x 2 block from its top-left pixel (see bevw_set_output_format in include/bevwarp.h).  Needs even
-        BW and BH and the 'lut' projection; combines with either input_format; jpeg() / jpeg_stream() need BGR output."""
+        BW and BH and the 'lut' projection; combines with either input_format; jpeg() / jpeg_stream() need BGR output.
+        input_pitch -- with input_format='nv12': bytes between the rows of the decoder surfaces run_surfaces() / run_surface_table() read in
+        place (None: FW; else a multiple of 4 >= FW; see bevw_set_input_pitch in include/bevwarp.h).  With a pitch other than FW the
+        packed entry points (__call__, batch, run_device) are refused."""
         self.init_args()
+        in_pitch = _ffi.check_input_pitch(input_pitch, args.FRAME_WIDTH, input_format == 'nv12')
         if rig is None:
             self.cameras = [Camera('front'), Camera('back'), Camera('left'), Camera('right')]
         else:
@@ -338,11 +346,12 @@ class BevGenerator:
         rig_kdh = [(c.camera_mat, c.dist_coeff, c.homography) for c in self.cameras]
         fmts = (formats[input_format], out_formats[output_format])
         try:
-            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, pitch, *fmts)
+            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, pitch, *fmts, in_pitch)
         except _ffi.BevwError:
             if not (auto and pitch != _ffi.PITCH_DENSE):
                 raise
-            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, _ffi.PITCH_DENSE, *fmts)   # a rig the tile plan cannot serve
+            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, _ffi.PITCH_DENSE, *fmts, in_pitch)   # a rig the tile plan cannot serve
+        self.in_pitch = int(lib().bevw_input_pitch(self._engine.h))   # bytes between the rows of an NV12 surface (run_surfaces)
         self.out_pitch = int(lib().bevw_output_pitch(self._engine.h))   # pixels per row of run_device()'s output images
         modes = {'lut': _ffi.PROJ_LUT, 'analytic': _ffi.PROJ_ANALYTIC, 'analytic_f32': _ffi.PROJ_ANALYTIC_F32}
         if projection not in modes:
@@ -617,6 +626,11 @@ class BevGenerator:
         device images are pitched (``out_pitch != BEV_WIDTH``: the 'auto' / 'aligned' layouts) REQUIRES it -- a caller that sized its
         buffer for dense images (batch * BEV_HEIGHT * BEV_WIDTH * 3) would otherwise be overrun silently.  Size buffers with
         ``batch * bev.out_image_bytes`` or construct with ``output_pitch='dense'``."""
+        self._check_out_bytes(batch, out_bytes)
+        check(lib().bevw_run_device(self._engine.h, d_frames, batch, d_car, d_out))
+
+    def _check_out_bytes(self, batch: int, out_bytes) -> None:
+        """run_device()'s rule for the buffer behind d_out."""
         need = int(batch) * self.out_image_bytes
         if out_bytes is None:
             if self.out_pitch != self._engine.cfg.bev_width:
@@ -624,7 +638,27 @@ class BevGenerator:
                                 "this batch) or construct it with output_pitch='dense'".format(self.out_pitch, need))
         elif int(out_bytes) < need:
             raise Exception("output buffer of {} bytes, {} images of {} bytes need {}".format(int(out_bytes), int(batch), self.out_image_bytes, need))
-        check(lib().bevw_run_device(self._engine.h, d_frames, batch, d_car, d_out))
+
+    def _need_nv12(self, what: str) -> None:
+        if self.input_format != 'nv12':
+            raise Exception("{} reads NV12 surfaces: use a BevGenerator with input_format='nv12'".format(what))
+
+    def run_surfaces(self, table, d_car, d_out: int, out_bytes: int = None) -> None:
+        """Asynchronous launch on NV12 decoder surfaces, read where they lie.  ``table``: uint64 [B, 4, 2] on the HOST -- for every frame
+        set and camera (front, back, left, right) the device addresses of the Y plane (FH rows) and of the U / V plane (FH // 2 rows), both
+        with rows of ``in_pitch`` bytes and 4-byte aligned.  The table is copied before the call returns.  d_car, d_out and out_bytes as
+        for run_device()."""
+        self._need_nv12("run_surfaces()")
+        t = _ffi.surface_table(table, 4)
+        self._check_out_bytes(t.shape[0], out_bytes)
+        check(lib().bevw_run_surfaces_device(self._engine.h, ptr(t), int(t.shape[0]), d_car, d_out))
+
+    def run_surface_table(self, d_table: int, batch: int, d_car, d_out: int, out_bytes: int = None) -> None:
+        """run_surfaces() with the table -- ``batch`` x 4 x 2 uint64 -- already in DEVICE memory at ``d_table`` (a decoder ring repeats:
+        upload the table once).  The library cannot check the plane pointers of a device table."""
+        self._need_nv12("run_surface_table()")
+        self._check_out_bytes(batch, out_bytes)
+        check(lib().bevw_run_surface_table_device(self._engine.h, d_table, int(batch), d_car, d_out))
 
     def sync(self) -> None:
         check(lib().bevw_sync(self._engine.h))

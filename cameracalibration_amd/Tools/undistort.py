@@ -49,11 +49,13 @@ class Undistorter:
     """The map set of one (K, D, size, scales, offsets) on the device."""
 
     def __init__(self, K, D, width, height, focalscale=1.0, sizescale=1.0, offset_h=0.0, offset_v=0.0, device=0, input_format='bgr',
-                 output_format='bgr'):
+                 output_format='bgr', input_pitch=None):
         """input_format: 'bgr' (images [height, width, 3]) or 'nv12' ([height*3//2, width]: Y plane, then the interleaved U / V plane; the
         result is what cv2.remap gives for cv2.cvtColor(img, cv2.COLOR_YUV2BGR_NV12) -- bevw_remapper_set_input_format in include/bevwarp.h).
         output_format: 'bgr' (results [out_h, out_w, 3]) or 'nv12' ([out_h*3//2, out_w]: the NV12 form of the BGR result, chroma of each 2 x 2
-        block from its top-left pixel -- bevw_set_output_format in include/bevwarp.h; needs an even output size)."""
+        block from its top-left pixel -- bevw_set_output_format in include/bevwarp.h; needs an even output size).
+        input_pitch: with input_format='nv12', bytes between the rows of the decoder surfaces run_surfaces() reads in place (None: width;
+        else a multiple of 4 >= width -- bevw_remapper_set_input_pitch); with a pitch other than width __call__ is refused."""
         self._r = None
         formats = {'bgr': _ffi.INPUT_BGR, 'nv12': _ffi.INPUT_NV12}
         if input_format not in formats:
@@ -62,6 +64,7 @@ class Undistorter:
         if output_format not in out_formats:
             raise Exception("output_format should be bgr/nv12")
         self.output_format = output_format
+        in_pitch = _ffi.check_input_pitch(input_pitch, width, input_format == 'nv12')
         _ffi.require_device()
         self.width, self.height = int(width), int(height)
         self.input_format = input_format
@@ -73,6 +76,8 @@ class Undistorter:
         try:
             if input_format != 'bgr':
                 check(lib().bevw_remapper_set_input_format(r, formats[input_format]))
+            if in_pitch:
+                check(lib().bevw_remapper_set_input_pitch(r, in_pitch))
             if output_format != 'bgr':
                 check(lib().bevw_remapper_set_output_format(r, out_formats[output_format]))
         except Exception:
@@ -81,6 +86,37 @@ class Undistorter:
         dims = np.zeros(4, np.int32)
         check(lib().bevw_remapper_dims(r, ptr(dims)))
         self.out_w, self.out_h = int(dims[2]), int(dims[3])
+        self.in_pitch = in_pitch or self.width   # bytes between the rows of an NV12 surface (run_surfaces)
+
+    @property
+    def out_image_bytes(self) -> int:
+        """Bytes of one dense device image as run_surfaces() writes it."""
+        return self.out_w * self.out_h * 3 // 2 if self.output_format == 'nv12' else self.out_w * self.out_h * 3
+
+    def run_surfaces(self, table, d_out: int, out_bytes: int = None) -> None:
+        """Asynchronous remap of NV12 decoder surfaces, read where they lie.  ``table``: uint64 [B, 2] on the HOST -- per image the device
+        addresses of its Y plane (height rows) and its U / V plane (height // 2 rows), rows of ``in_pitch`` bytes, 4-byte aligned; copied
+        before the call returns.  ``d_out``: B dense device images of ``out_image_bytes``; out_bytes: the size of the buffer behind it."""
+        if self.input_format != 'nv12':
+            raise Exception("run_surfaces() reads NV12 surfaces: use an Undistorter with input_format='nv12'")
+        t = _ffi.surface_table(table, 1)
+        need = int(t.shape[0]) * self.out_image_bytes
+        if out_bytes is not None and int(out_bytes) < need:
+            raise Exception("output buffer of {} bytes, {} images of {} bytes need {}".format(int(out_bytes), int(t.shape[0]), self.out_image_bytes, need))
+        check(lib().bevw_remap_surfaces_device(self._r, ptr(t), int(t.shape[0]), d_out))
+
+    def run_surface_table(self, d_table: int, batch: int, d_out: int, out_bytes: int = None) -> None:
+        """run_surfaces() with the table -- ``batch`` x 2 uint64 -- already in DEVICE memory at ``d_table`` (a decoder ring repeats: upload
+        the table once).  The library cannot check the plane pointers of a device table."""
+        if self.input_format != 'nv12':
+            raise Exception("run_surface_table() reads NV12 surfaces: use an Undistorter with input_format='nv12'")
+        need = int(batch) * self.out_image_bytes
+        if out_bytes is not None and int(out_bytes) < need:
+            raise Exception("output buffer of {} bytes, {} images of {} bytes need {}".format(int(out_bytes), int(batch), self.out_image_bytes, need))
+        check(lib().bevw_remap_surface_table_device(self._r, d_table, int(batch), d_out))
+
+    def sync(self) -> None:
+        check(lib().bevw_remapper_sync(self._r))
 
     def maps(self):
         m1 = np.empty((self.out_h, self.out_w, 2), np.int16)

@@ -12,7 +12,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BEVW_LIB_PATH") or os.path.join(_HERE, "libbevwarp.so")   # override: A/B of two builds
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 SCHED_AUTO, SCHED_PER_PIXEL, SCHED_TILE_PLAN = 0, 1, 2
 PROJ_LUT, PROJ_ANALYTIC, PROJ_ANALYTIC_F32 = 0, 1, 2   # bevw_set_projection
@@ -64,6 +64,10 @@ SIGNATURES = {
     "bevw_output_pitch": (_i, [_vp]),
     "bevw_set_input_format": (_i, [_vp, _i]),
     "bevw_input_format": (_i, [_vp]),
+    "bevw_set_input_pitch": (_i, [_vp, _i]),
+    "bevw_input_pitch": (_i, [_vp]),
+    "bevw_run_surfaces_device": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "bevw_run_surface_table_device": (_i, [_vp, _vp, _i, _vp, _vp]),
     "bevw_set_output_format": (_i, [_vp, _i]),
     "bevw_output_format": (_i, [_vp]),
     "bevw_run_cameras": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -101,6 +105,9 @@ SIGNATURES = {
     "bevw_remapper_sync": (_i, [_vp]),
     "bevw_remapper_set_input_format": (_i, [_vp, _i]),
     "bevw_remapper_set_output_format": (_i, [_vp, _i]),
+    "bevw_remapper_set_input_pitch": (_i, [_vp, _i]),
+    "bevw_remap_surfaces_device": (_i, [_vp, _vp, _i, _vp]),
+    "bevw_remap_surface_table_device": (_i, [_vp, _vp, _i, _vp]),
     "bevw_remapper_timer_start": (_i, [_vp]),
     "bevw_remapper_timer_stop": (_i, [_vp, C.POINTER(C.c_float)]),
     "bevw_remapper_timer_mark": (_i, [_vp, _i]),
@@ -194,6 +201,30 @@ def device_name(device: int = 0) -> str:
     buf = C.create_string_buffer(256)
     check(lib().bevw_device_name(device, buf, 256))
     return buf.value.decode()
+
+
+def surface_table(table, per_set: int, what: str = "table") -> np.ndarray:
+    """A host table of NV12 surfaces as the library reads it (bevw_nv12_surface: two device addresses, Y plane then U / V plane): a
+    C-contiguous uint64 array [B, per_set, 2] ([B, 2] when per_set is 1).  Raises with the expected shape otherwise."""
+    a = np.asarray(table)
+    want = "[B, {}, 2]".format(per_set) if per_set > 1 else "[B, 2]"
+    ok = a.dtype == np.uint64 and a.shape[-1:] == (2,) and (a.ndim == 3 and a.shape[1] == per_set if per_set > 1 else a.ndim == 2)
+    if not ok:
+        raise Exception("{} must be uint64 {} (device addresses of the Y and U/V planes), got {} {}".format(what, want, a.dtype, list(a.shape)))
+    return np.ascontiguousarray(a)
+
+
+def check_input_pitch(input_pitch, width: int, nv12: bool) -> int:
+    """The rules of bevw_set_input_pitch, checked before any device call: None / 0 = the frame width; else NV12 input, a multiple of 4
+    bytes >= the frame width."""
+    if input_pitch is None or int(input_pitch) == 0:
+        return 0
+    if not nv12:
+        raise Exception("input_pitch needs input_format='nv12' (BGR frames are dense)")
+    p = int(input_pitch)
+    if p < int(width) or p % 4 != 0:
+        raise Exception("input_pitch must be a multiple of 4 bytes >= the frame width {}, got {}".format(int(width), p))
+    return p
 
 
 def ptr(a: np.ndarray) -> int:

@@ -280,6 +280,19 @@ __device__ __forceinline__ uint32_t nv12_texel(const uint8_t *__restrict__ src, 
     const uint8_t *uv = src + (size_t)fw * fh + (size_t)(y >> 1) * fw + (x & ~1);
     return nv12_bgr(src[(size_t)y * fw + x], nv12_chroma(uv[0], uv[1]));
 }
+// NV12 surfaces (bevw_run_surfaces_device; DESIGN.md "NV12 surfaces"): one decoded frame as two device pointers -- FH rows of Y and FH / 2 rows
+// of interleaved U / V (U first), both with the handle's row pitch (bevw_set_input_pitch; >= FW, a multiple of 4), anywhere in memory.  The
+// layout of bevw_nv12_surface (include/bevwarp.h); a table holds one entry per (frame set, camera).
+struct Nv12Surface { const uint8_t *y, *uv; };
+// the second dword of a group of the surface group lists (bevw_unit.h: unit_gsrc_surf): U / V offset inside the plane | camera in the low bits
+__host__ __device__ __forceinline__ uint32_t unit_surf_cam(uint32_t c) { return c & 3u; }
+__host__ __device__ __forceinline__ uint32_t unit_surf_uv(uint32_t c) { return c & ~3u; }
+// texel (x, y), inside the frame, of a surface with rows of `pitch` bytes
+__device__ __forceinline__ uint32_t nv12_texel_planes(const uint8_t *__restrict__ yp, const uint8_t *__restrict__ uvp, int pitch, int x, int y)
+{
+    const uint8_t *uv = uvp + (size_t)(y >> 1) * pitch + (x & ~1);
+    return nv12_bgr(yp[(size_t)y * pitch + x], nv12_chroma(uv[0], uv[1]));
+}
 // bytes of one frame set: BGR 3 per texel, NV12 1.5
 __host__ __device__ __forceinline__ size_t frame_bytes_of(int fw, int fh, bool nv12) { return nv12 ? (size_t)fw * fh * 3 / 2 : (size_t)fw * fh * 3; }
 
@@ -369,10 +382,13 @@ __device__ __forceinline__ int remap_round10(int S, int ties_even)
     return r;
 }
 // NV12: `src` is an NV12 frame (nv12_texel), the texels are converted before the balance step
-template <bool LUM, bool NV12 = false>
+// SURF (with NV12): `src` is the Y plane and `uvp` the U / V plane of a surface with rows of `pitch` bytes (nv12_texel_planes)
+template <bool LUM, bool NV12 = false, bool SURF = false>
 __device__ __forceinline__ void remap_u8c3_px(const uint8_t *__restrict__ src, int sw, int sh, int sx, int sy,
-                                              unsigned code, int out[3], int delta, const HsvTables *hsv, int ties_even = 0)
+                                              unsigned code, int out[3], int delta, const HsvTables *hsv, int ties_even = 0,
+                                              const uint8_t *__restrict__ uvp = nullptr, int pitch = 0)
 {
+    static_assert(!SURF || NV12, "surfaces are NV12");
     const int fx = code & 31, fy = (code >> 5) & 31;
     const int ax = kQOne - fx, ay = kQOne - fy;
     const int w00 = ax * ay, w01 = fx * ay, w10 = ax * fy, w11 = fx * fy;
@@ -385,7 +401,7 @@ __device__ __forceinline__ void remap_u8c3_px(const uint8_t *__restrict__ src, i
         for (int q = 0; q < 4; ++q) {
             const int x = sx + (q & 1), y = sy + (q >> 1);
             if ((unsigned)x < (unsigned)sw && (unsigned)y < (unsigned)sh) {
-                const uint32_t p = nv12_texel(src, sw, sh, x, y);
+                const uint32_t p = SURF ? nv12_texel_planes(src, uvp, pitch, x, y) : nv12_texel(src, sw, sh, x, y);
                 t[q][0] = (int)(p & 255u); t[q][1] = (int)((p >> 8) & 255u); t[q][2] = (int)(p >> 16);
                 if (LUM) luminance_shift_px(t[q][0], t[q][1], t[q][2], delta, *hsv);
             } else {

@@ -254,9 +254,11 @@ static __global__ void k_blend_weights(uint8_t *__restrict__ maskA, const uint8_
 // cv2.remap(src, map1, map2, INTER_LINEAR) for a batch: one thread per destination pixel.
 // grid = (ceil(dw / 256), dh, batch).  NV12: the sources are NV12 frames (bevw_remapper_set_input_format), converted per tap.
 // OUT_NV12: dst holds dense NV12 images (bevw_remapper_set_output_format, dw and dh even): the pixel's Y, and U / V on even rows and columns
-template <bool NV12 = false, bool OUT_NV12 = false>
+// SURF: the sources are NV12 surfaces (bevw_remap_surfaces_device): surf[image] with rows of src_pitch bytes, `src` is not read
+template <bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
 static __global__ void k_remap_lut(const uint8_t *__restrict__ src, int sw, int sh, const int16_t *__restrict__ map1,
-                            const uint16_t *__restrict__ map2, int dw, int dh, uint8_t *__restrict__ dst, int ties_even = 0)
+                            const uint16_t *__restrict__ map2, int dw, int dh, uint8_t *__restrict__ dst, int ties_even = 0,
+                            const Nv12Surface *__restrict__ surf = nullptr, int src_pitch = 0)
 {
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
@@ -265,7 +267,12 @@ static __global__ void k_remap_lut(const uint8_t *__restrict__ src, int sw, int 
     const uint8_t *s = src + (NV12 ? (size_t)blockIdx.z * frame_bytes_of(sw, sh, true) : (size_t)blockIdx.z * sw * sh * 3);
     const int sx = map1[o * 2], sy = map1[o * 2 + 1];
     int out[3];
-    remap_u8c3_px<false, NV12>(s, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even);
+    if constexpr (SURF) {
+        const Nv12Surface sf = surf[blockIdx.z];
+        remap_u8c3_px<false, true, true>(sf.y, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even, sf.uv, src_pitch);
+    } else {
+        remap_u8c3_px<false, NV12>(s, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even);
+    }
     if (OUT_NV12) {
         nv12_store_px(dst + (size_t)blockIdx.z * image_bytes_of(dw, dh, true), dw, dh, x, y,
                       (uint32_t)out[0] | ((uint32_t)out[1] << 8) | ((uint32_t)out[2] << 16));
@@ -314,11 +321,14 @@ __device__ __forceinline__ unsigned vsum_piece(const VsumPiece &p)
 // its sum at sums[y * part_stride + x] -- no atomics, no zeroing pass in front of the kernel; k_lum_delta adds the parts.
 // NV12: NV12 frames of fw texels per row (frame_bytes = fw * fh * 3 / 2), V of the converted texels: the blocks of a frame take its rows
 // round-robin, a lane a horizontal texel pair (two Y bytes and the U / V pair they share) per trip.
-template <bool NV12 = false>
+// SURF: NV12 surfaces -- surf[frame] with rows of src_pitch bytes, of which the first fw are texels (the padding columns are not summed)
+template <bool NV12 = false, bool SURF = false>
 static __global__ void k_vsum(const uint8_t *__restrict__ frames, size_t frame_bytes, int vec_ok,
-                       unsigned long long *__restrict__ sums, int part_stride = 0, int fw = 0)
+                       unsigned long long *__restrict__ sums, int part_stride = 0, int fw = 0,
+                       const Nv12Surface *__restrict__ surf = nullptr, int src_pitch = 0)
 {
-    const uint8_t *f = frames + (size_t)blockIdx.y * frame_bytes;
+    static_assert(!SURF || NV12, "surfaces are NV12");
+    const uint8_t *f = SURF ? nullptr : frames + (size_t)blockIdx.y * frame_bytes;
     const size_t npieces = (vec_ok && !NV12) ? frame_bytes / 12 : 0;
     const VsumPiece *fp = reinterpret_cast<const VsumPiece *>(f);
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (size_t)gridDim.x * blockDim.x;
@@ -326,9 +336,14 @@ static __global__ void k_vsum(const uint8_t *__restrict__ frames, size_t frame_b
     if (NV12) {
         auto v = [](uint32_t t) { return max(t & 255u, max((t >> 8) & 255u, t >> 16)); };
         const int fh = (int)(frame_bytes / 3 * 2 / (size_t)fw), npairs = fw / 2;
-        const uint8_t *uvp = f + (size_t)fw * fh;
+        const uint8_t *yp = f, *uvp = f + (size_t)fw * fh;
+        int rb = fw;   // bytes between rows
+        if constexpr (SURF) {
+            const Nv12Surface sf = surf[blockIdx.y];
+            yp = sf.y; uvp = sf.uv; rb = src_pitch;
+        }
         for (int y = blockIdx.x; y < fh; y += gridDim.x) {
-            const uint8_t *yr = f + (size_t)y * fw, *cr = uvp + (size_t)(y >> 1) * fw;
+            const uint8_t *yr = yp + (size_t)y * rb, *cr = uvp + (size_t)(y >> 1) * rb;
             for (int k = threadIdx.x; k < npairs; k += blockDim.x) {
                 const Nv12Chroma c = nv12_chroma(cr[2 * k], cr[2 * k + 1]);
                 acc += v(nv12_bgr(yr[2 * k], c)) + v(nv12_bgr(yr[2 * k + 1], c));
@@ -408,11 +423,12 @@ static __global__ void k_lum_shift(const uint8_t *__restrict__ frames, size_t fr
 // grid = (ceil(bw / 256), bh, batch)
 // NV12: NV12 frame sets (bevw_set_input_format), every tap converted where it is fetched (remap_u8c3_px)
 // OUT_NV12 (not with BAL, whose pre-gain image is BGR): dense NV12 BEV images (bevw_set_output_format), converted after the car
-template <bool BLEND, bool BAL, bool NV12 = false, bool OUT_NV12 = false>
+// SURF: NV12 surfaces (bevw_run_surfaces_device) -- surf[frame set][camera] with rows of src_pitch bytes, `frames` is not read
+template <bool BLEND, bool BAL, bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
 static __global__ void k_stitch_pp(const uint8_t *__restrict__ frames, int fw, int fh, StitchTables T, int bw, int bh,
                             const int *__restrict__ deltas, const HsvTables *__restrict__ tab,
                             const uint8_t *__restrict__ car, unsigned long long *__restrict__ chsums,
-                            uint8_t *__restrict__ out, int ties_even = 0)
+                            uint8_t *__restrict__ out, int ties_even = 0, const Nv12Surface *__restrict__ surf = nullptr, int src_pitch = 0)
 {
     __shared__ HsvTables hsv;
     __shared__ unsigned long long part[3][4];
@@ -434,6 +450,11 @@ static __global__ void k_stitch_pp(const uint8_t *__restrict__ frames, int fw, i
             const uint8_t *src = frames + ((size_t)b * 4 + c) * frame_bytes;
             const int sx = T.lut1[c][o * 2], sy = T.lut1[c][o * 2 + 1];
             int v[3];
+            if constexpr (SURF) {
+                const Nv12Surface sf = surf[(size_t)b * 4 + c];
+                remap_u8c3_px<BAL, true, true>(sf.y, fw, fh, sx, sy, T.lut2[c][o] & (kQTab2 - 1), v, BAL ? deltas[b * 4 + c] : 0, &hsv, ties_even, sf.uv,
+                                               src_pitch);
+            } else
             remap_u8c3_px<BAL, NV12>(src, fw, fh, sx, sy, T.lut2[c][o] & (kQTab2 - 1), v, BAL ? deltas[b * 4 + c] : 0, &hsv, ties_even);
             if (BLEND) {
                 const float wgt = blend_weight_f32(m);

@@ -164,13 +164,16 @@ static __global__ void k_plan_touch(const uint2 *__restrict__ plan, int ntiles, 
 // NV12: the raw frames are NV12 frame sets (bevw_set_input_format), `groups` holds two offsets per group (Y, U / V: unit_gsrc_nv12, in the
 // same order) and frame_bytes is an NV12 frame's; a lane loads 4 Y and 4 U / V bytes and converts its texels (nv12_row_bgr) before the shift.
 // The scratch is BGR either way.
+// SURF: NV12 surfaces (bevw_run_surfaces_device): surf[frame set][4], `groups` holds the offsets inside the camera's own planes and the camera
+// in the low bits of the second one (unit_gsrc_surf); `frames` is not read.
 constexpr int kLumTrips = 8;
-template <bool NV12 = false>
+template <bool NV12 = false, bool SURF = false>
 static __global__ void __launch_bounds__(256) k_lum_groups(const uint8_t *__restrict__ frames, uint8_t *__restrict__ scratch, size_t set_bytes,
                                                             size_t scratch_stride, uint32_t frame_bytes, const uint32_t *__restrict__ groups, int ngroups,
                                                             const int *__restrict__ deltas, const HsvTables *__restrict__ tab,
-                                                            uint32_t blocks_per_frame, uint32_t nframes)
+                                                            uint32_t blocks_per_frame, uint32_t nframes, const Nv12Surface *__restrict__ surf = nullptr)
 {
+    static_assert(!SURF || NV12, "surfaces are NV12");
     __shared__ HsvTables hsv;
     __shared__ int cam_delta[4];
     uint32_t frame, blk;
@@ -191,8 +194,14 @@ static __global__ void __launch_bounds__(256) k_lum_groups(const uint8_t *__rest
         }
 #pragma unroll
         for (int t = 0; t < kLumTrips; ++t) {   // v.x = Y bytes, v.y = U / V bytes of texels x .. x+3
-            v[t].x = *reinterpret_cast<const uint32_t *>(fin + goff[t]);
-            v[t].y = *reinterpret_cast<const uint32_t *>(fin + coff[t]);
+            if constexpr (SURF) {   // (past the list: texels 0 .. 3 of camera 0 once more, not stored)
+                const Nv12Surface sf = surf[(size_t)frame * 4 + unit_surf_cam(coff[t])];
+                v[t].x = *reinterpret_cast<const uint32_t *>(sf.y + goff[t]);
+                v[t].y = *reinterpret_cast<const uint32_t *>(sf.uv + unit_surf_uv(coff[t]));
+            } else {
+                v[t].x = *reinterpret_cast<const uint32_t *>(fin + goff[t]);
+                v[t].y = *reinterpret_cast<const uint32_t *>(fin + coff[t]);
+            }
             v[t].z = 0u;
         }
     } else {
@@ -207,7 +216,7 @@ static __global__ void __launch_bounds__(256) k_lum_groups(const uint8_t *__rest
         const int gi = g0 + t * 256;
         if (gi >= ngroups) break;
         const uint32_t w[3] = {v[t].x, v[t].y, v[t].z};
-        const int cam = (int)(goff[t] >= frame_bytes) + (int)(goff[t] >= 2u * frame_bytes) + (int)(goff[t] >= 3u * frame_bytes);
+        const int cam = SURF ? (int)unit_surf_cam(coff[t]) : (int)(goff[t] >= frame_bytes) + (int)(goff[t] >= 2u * frame_bytes) + (int)(goff[t] >= 3u * frame_bytes);
         const int delta = cam_delta[cam];
         // the 4 texels of the group as dwords (byte 3 is ignored), shifted, and packed back into the 12 bytes
         uint32_t P[4] = {w[0], __builtin_amdgcn_alignbyte(w[1], w[0], 3), __builtin_amdgcn_alignbyte(w[2], w[1], 2), w[2] >> 8};
@@ -277,15 +286,20 @@ __device__ __forceinline__ void entry_to_taps(EntryRegs &e, int fw, uint32_t fra
 
 // NV12: `fb` is an NV12 frame set, frame_bytes an NV12 frame's, every valid entry on the per-tap path (entry_to_taps) with the conversion per
 // fetched texel (remap_u8c3_px); an entry without a contributor adds 0
-template <bool BLEND, bool BAL, bool NV12 = false>
+// SURF: `fs` holds the surfaces of the frame set's cameras (rows of src_pitch bytes), `fb` is not read
+template <bool BLEND, bool BAL, bool NV12 = false, bool SURF = false>
 __device__ __forceinline__ void eval_entry(const uint8_t *__restrict__ fb, const EntryRegs &e, uint32_t row_bytes, int fw,
                                            int fh, uint32_t frame_bytes, bool tile_slow, const int *__restrict__ fdeltas,
-                                           const HsvTables &hsv, int v[3])
+                                           const HsvTables &hsv, int v[3], const Nv12Surface *__restrict__ fs = nullptr, int src_pitch = 0)
 {
     const int cam = (e.meta >> 18) & 3;
     if (NV12) {
         if (e.meta & kMetaValid) {
             const int sx = (int)(int16_t)(e.off & 0xffffu), sy = (int)(int16_t)(e.off >> 16);
+            if constexpr (SURF) {
+                const Nv12Surface sf = fs[cam];
+                remap_u8c3_px<BAL, true, true>(sf.y, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv, 0, sf.uv, src_pitch);
+            } else
             remap_u8c3_px<BAL, true>(fb + (size_t)cam * frame_bytes, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv);
         } else {
             v[0] = v[1] = v[2] = 0;
@@ -340,6 +354,10 @@ struct PlanArgs {
     // channel sums (balance): psums[frame][nsum][3], ONE writer per entry and frame -- unit u writes entry u, the per-tap kernel entry
     // sum_base + its position in the tile list (sum_base = number of units; 0 when it serves every tile)
     int nsum, sum_base;
+    // NV12 surfaces (bevw_run_surfaces_device; the SURF instantiations): surf[frame set][ncams] instead of `frames`, rows of src_pitch bytes;
+    // un_gsrc then holds the units' group lists relative to the camera's own planes (unit_gsrc_surf)
+    const Nv12Surface *surf;
+    int src_pitch;
 };
 
 // Block index -> (batch chunk, tile group).  Blocks are dealt to the 8 XCDs round-robin (block id % 8), and each XCD has
@@ -373,9 +391,11 @@ __device__ __forceinline__ bool plan_block_map(const PlanArgs &a, uint32_t id, u
 // NV12: NV12 frame sets (bevw_set_input_format), every tap converted where it is fetched (eval_entry)
 // OUT_NV12: NV12 BEV images (bevw_set_output_format; a.pitch % 4 == 0, no SUMS: the balance modes store BGR for the gain pass) -- a lane's
 // quad as one Y dword and, on even rows, one U / V dword (nv12_quad), after the car
-template <bool BLEND, bool LUM, bool SUMS = LUM, bool NV12 = false, bool OUT_NV12 = false>
+// SURF: NV12 surfaces (a.surf, a.src_pitch) instead of a.frames
+template <bool BLEND, bool LUM, bool SUMS = LUM, bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) k_stitch_plan(PlanArgs a)
 {
+    static_assert(!SURF || NV12, "surfaces are NV12");
     constexpr bool BAL = LUM;
     __shared__ __attribute__((aligned(16))) uint32_t hsv_words[BAL ? sizeof(HsvTables) / 4 : 1];   // (no LDS for the variants without the luminance round trip)
     const HsvTables &hsv = *reinterpret_cast<const HsvTables *>(hsv_words);
@@ -417,7 +437,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
     const int b_begin = (int)chunk * a.nb, b_end = min(a.batch, b_begin + a.nb);
 #pragma unroll 1
     for (int b = b_begin; b < b_end; ++b) {
-        const uint8_t *fb = a.frames + (size_t)b * set_bytes;
+        const uint8_t *fb = SURF ? nullptr : a.frames + (size_t)b * set_bytes;
+        const Nv12Surface *fs = SURF ? a.surf + (size_t)b * a.ncams : nullptr;
         const int *fdeltas = BAL ? a.deltas + b * 4 : nullptr;
         int px[4][3];
         if (hdr & kHdrEmpty) {
@@ -426,13 +447,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                eval_entry<BLEND, BAL, NV12>(fb, e0[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, px[j]);
+                eval_entry<BLEND, BAL, NV12, SURF>(fb, e0[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, px[j], fs, a.src_pitch);
             }
             if (second) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     int w[3];
-                    eval_entry<BLEND, BAL, NV12>(fb, e1[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, w);
+                    eval_entry<BLEND, BAL, NV12, SURF>(fb, e1[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, w, fs, a.src_pitch);
                     px[j][0] = min(255, px[j][0] + w[0]); px[j][1] = min(255, px[j][1] + w[1]); px[j][2] = min(255, px[j][2] + w[2]);
                 }
             }
@@ -600,6 +621,7 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
         }
         p.band_ok = true;
         groups_host.swap(list);
+        p.groups_host = groups_host;   // (kept for plan_set_src_pitch)
     }
     std::vector<uint32_t> hdr((size_t)p.ntiles);
     if ((e = hipMemcpyAsync(hdr.data(), p.hdr, hdr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
@@ -627,6 +649,8 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
         if (!up.desc.empty()) {
             hdr.swap(hdr_un);
             if ((e = plan_upload_units(p, up)) != hipSuccess) return e;
+            p.un_gsrc_host = up.gsrc;   // (kept for plan_set_src_pitch)
+            p.un_ranges_host = unit_slot_ranges(up);
             if (fh % 2 == 0) {   // the units' group lists for NV12 frame sets (k_plan_units<.., true>)
                 std::vector<uint32_t> nv;
                 unit_gsrc_nv12(up.gsrc, fw, fh, nv);
@@ -648,6 +672,30 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
     // 12-byte stores need 4-byte aligned pixel quads: rows of `pitch` pixels (bw % 4 != 0: padded scratch + k_plan_unpad)
     p.pitch = plan_pitch(bw, out_pitch);
     p.out_pitched = out_pitch > 0 && out_pitch != bw;
+    return hipSuccess;
+}
+
+// NV12 surfaces: the third translation of the group lists (unit_gsrc_surf) -- the units' and the sampled-group list of the balance schedule --
+// for surfaces whose rows are `pitch` bytes apart.  The plan itself does not change.  Called when the pitch is set or after the plan was
+// built, whichever comes last (plan_build resets it); no step of the plan may be queued.
+static inline hipError_t plan_src_pitch_impl(Plan &p, int pitch)
+{
+    for (void **q : {&p.un_gsrc_surf, &p.groups_surf}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    p.src_pitch = pitch;
+    if (pitch <= 0 || p.fh % 2 != 0 || p.fw % 4 != 0) return hipSuccess;
+    hipError_t e;
+    std::vector<uint32_t> nv;
+    if (!p.un_gsrc_host.empty()) {
+        // (a list with a unit of more than two cameras is not used: the per-tap kernel then serves every tile)
+        if (unit_gsrc_surf(p.un_gsrc_host, p.fw, p.fh, pitch, nv, &p.un_ranges_host) && (e = plan_upload_list(nv, &p.un_gsrc_surf)) != hipSuccess) return e;
+    }
+    if (!p.groups_host.empty()) {
+        unit_gsrc_surf(p.groups_host, p.fw, p.fh, pitch, nv);
+        if ((e = plan_upload_list(nv, &p.groups_surf)) != hipSuccess) return e;
+    }
     return hipSuccess;
 }
 
@@ -699,10 +747,15 @@ static inline unsigned plan_grid(const PlanArgs &a)
 static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t *d_frames, int batch, bool blend, bool balance,
                                           const int *d_deltas, const HsvTables *d_tab, const uint8_t *d_car,
                                           unsigned long long *d_chsums, uint8_t *d_out, const PlanTuning &tune, bool sums = false,
-                                          int psums_frames = 0, int psums_first = 0, const uint8_t *d_scratch = nullptr)
+                                          int psums_frames = 0, int psums_first = 0, const uint8_t *d_scratch = nullptr,
+                                          const Nv12Surface *d_surf = nullptr)
 {
+    // d_surf: the frames are NV12 surfaces (surf[frame set][ncams], rows of p.src_pitch bytes; p.nv12 is set) and d_frames is not read
     hipError_t e;
+    const bool surf = d_surf != nullptr;
+    if (surf && (!p.nv12 || p.src_pitch < p.fw || p.src_pitch % 4 != 0)) return hipErrorInvalidValue;
     PlanArgs a = plan_args(p, d_frames, batch, d_car, d_out, tune);
+    a.surf = d_surf; a.src_pitch = p.src_pitch;
     a.plan = static_cast<const uint2 *>(p.entries); a.hdr = static_cast<const uint32_t *>(p.hdr);
     a.deltas = d_deltas; a.tab = d_tab;
     const bool padded = p.pitch != p.bw, scratch = padded && !p.out_pitched;
@@ -731,7 +784,7 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
     const bool nv12_units = p.nv12 && !compact;
     const bool use_units = !balance && tune.units && p.n_un_all > 0 && (((uintptr_t)d_frames) & 3u) == 0 &&
                            (!compact || (p.un_gsrc_compact != nullptr && (((uintptr_t)d_scratch) & 3u) == 0)) &&
-                           (!nv12_units || (p.un_gsrc_nv12 != nullptr && !sums));
+                           (!nv12_units || ((surf ? p.un_gsrc_surf : p.un_gsrc_nv12) != nullptr && !sums));
     const bool with_sums = balance || sums;
     // channel-sum entries per frame: one per unit + one per base tile left to the per-tap kernel (or one per tile without units).  Every
     // entry has exactly one writer per frame (no atomics, round 5: 2.4 M atomic adds per config-4 step cost 58 us of the 600), and every writer
@@ -759,9 +812,12 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         if (compact) { a.frames = d_scratch; a.set_stride = (uint32_t)p.compact_stride; a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_compact); }
         if (nv12_units) {
             a.set_stride = (uint32_t)(frame_bytes_of(p.fw, p.fh, true) * p.ncams);
-            a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_nv12);
+            a.un_gsrc = static_cast<const uint32_t *>(surf ? p.un_gsrc_surf : p.un_gsrc_nv12);
         }
-        if (out_nv12) {
+        if (surf && nv12_units) {
+            if (out_nv12) with_flags([&](auto bl) { hipLaunchKernelGGL((k_units_out_surf<bl>), dim3(plan_grid(a)), block, 0, st, a); }, blend);
+            else with_flags([&](auto bl) { hipLaunchKernelGGL((k_units_surf<bl>), dim3(plan_grid(a)), block, 0, st, a); }, blend);
+        } else if (out_nv12) {
             with_flags([&](auto bl, auto nv) { hipLaunchKernelGGL((k_units_out_nv12<bl, nv>), dim3(plan_grid(a)), block, 0, st, a); }, blend, nv12_units);
         } else if (nv12_units) {
             with_flags([&](auto bl) { hipLaunchKernelGGL((k_units_nv12<bl>), dim3(plan_grid(a)), block, 0, st, a); }, blend);
@@ -778,7 +834,12 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         a.frames = d_frames; a.set_stride = 0;   // the per-tap kernel reads whole frames: RAW ones in the balance modes
         // LUM: luminance round trip per tap (the RAW frames of balance, or the tiles no unit owns beside the compact scratch); compact
         // without sums: camera-per-GPU shards, whose stitch rank balances the colours
-        if (out_nv12)
+        if (surf && out_nv12)
+            with_flags([&](auto bl) { hipLaunchKernelGGL((k_stitch_plan<bl, false, false, true, true, true>), dim3(plan_grid(a)), block, 0, st, a); }, blend);
+        else if (surf)
+            with_flags([&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm, true, false, true>), dim3(plan_grid(a)), block, 0, st, a); },
+                       blend, balance || compact, balance || sums);
+        else if (out_nv12)
             with_flags([&](auto bl, auto nv) { hipLaunchKernelGGL((k_stitch_plan<bl, false, false, nv, true>), dim3(plan_grid(a)), block, 0, st, a); },
                        blend, p.nv12);
         else if (p.nv12)
@@ -818,10 +879,20 @@ static inline hipError_t plan_unit_wide_launch(const Plan &p, hipStream_t st, co
 
 // luminance-shift the sampled texel groups of every raw frame of the batch into the compact scratch (p.compact_stride bytes per frame set)
 static inline hipError_t plan_lum_band(const Plan &p, hipStream_t st, const uint8_t *d_frames, uint8_t *d_scratch, int batch,
-                                       const int *d_deltas, const HsvTables *d_tab)
+                                       const int *d_deltas, const HsvTables *d_tab, const Nv12Surface *d_surf = nullptr)
 {
     if (p.n_groups == 0 || p.compact_stride == 0) return hipSuccess;
     if (p.nv12 && !p.groups_nv12) return hipErrorInvalidValue;
+    if (d_surf) {   // NV12 surfaces: the sampled groups relative to the camera's own planes (plan_src_pitch_impl)
+        if (!p.nv12 || !p.groups_surf) return hipErrorInvalidValue;
+        const unsigned bpf = (unsigned)(p.n_groups + 256 * kLumTrips - 1) / (256 * kLumTrips);
+        for_each_chunk(batch, [&](int b0, int nb) {
+            hipLaunchKernelGGL((k_lum_groups<true, true>), dim3(xcd_frame_grid(bpf, (unsigned)nb)), dim3(256), 0, st, nullptr,
+                               d_scratch + (size_t)b0 * p.compact_stride, (size_t)0, p.compact_stride, 0u, static_cast<const uint32_t *>(p.groups_surf),
+                               p.n_groups, d_deltas + (size_t)b0 * 4, d_tab, bpf, (uint32_t)nb, d_surf + (size_t)b0 * 4);
+        });
+        return hipGetLastError();
+    }
     const size_t frame_bytes = frame_bytes_of(p.fw, p.fh, p.nv12), set_bytes = frame_bytes * p.ncams;
     const unsigned bpf = (unsigned)(p.n_groups + 256 * kLumTrips - 1) / (256 * kLumTrips);
     for_each_chunk(batch, [&](int b0, int nb) {

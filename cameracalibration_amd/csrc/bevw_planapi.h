@@ -14,6 +14,7 @@ struct StitchTables {
 };
 
 struct HsvTables;   // bevw_device.h
+struct Nv12Surface; // bevw_device.h: the two plane pointers of one decoded NV12 frame (bevw_nv12_surface)
 
 // a compiled tile plan: its device buffers and the geometry they were built for (plan_build / plan_build_wide)
 struct Plan {
@@ -57,6 +58,13 @@ struct Plan {
     // the per-frame kernels write NV12 images of `pitch` bytes per row (bevw_set_output_format; needs pitch % 4 == 0 and no padded scratch):
     // set by the owner after plan_build.  Steps with channel sums (balance) still write the BGR pre-gain image: their gain pass converts.
     bool out_nv12 = false;
+    // NV12 surfaces (bevw_set_input_pitch / bevw_run_surfaces_device): rows of src_pitch bytes, and the group lists translated for them
+    // (unit_gsrc_surf: offsets inside the camera's own planes, camera in the low bits).  Set by the owner through plan_set_src_pitch after
+    // plan_build, which resets them; the host copies of the lists the translation starts from stay with the plan.
+    int src_pitch = 0;
+    void *un_gsrc_surf = nullptr;            // the units' group lists, two dwords per slot
+    void *groups_surf = nullptr;             // the sampled groups of the balance schedule (k_lum_groups<true, true>), two dwords per group
+    std::vector<uint32_t> un_gsrc_host, groups_host, un_ranges_host;   // (un_ranges_host: first slot and slot count of every unit's list)
 };
 
 // compile LUT + masks into a plan (table kernels, unit compiler on the host).  out_pitch: pixels per output row when the caller's images
@@ -66,10 +74,14 @@ int plan_build(Plan &p, hipStream_t st, const StitchTables &T, int fw, int fh, i
 // one step: see plan_stitch_impl (bevw_plan.h)
 int plan_stitch(Plan &p, hipStream_t st, const uint8_t *d_frames, int batch, bool blend, bool balance, const int *d_deltas, const HsvTables *d_tab,
                 const uint8_t *d_car, unsigned long long *d_chsums, uint8_t *d_out, bool sums = false, int psums_frames = 0, int psums_first = 0,
-                const uint8_t *d_scratch = nullptr);
+                const uint8_t *d_scratch = nullptr, const Nv12Surface *d_surf = nullptr);
 
 // balance: luminance round trip of the sampled texel groups of the raw frames into the compact scratch (p.compact_stride bytes per frame set)
-int plan_lum_groups(const Plan &p, hipStream_t st, const uint8_t *d_frames, uint8_t *d_scratch, int batch, const int *d_deltas, const HsvTables *d_tab);
+int plan_lum_groups(const Plan &p, hipStream_t st, const uint8_t *d_frames, uint8_t *d_scratch, int batch, const int *d_deltas, const HsvTables *d_tab,
+                    const Nv12Surface *d_surf = nullptr);
+
+// NV12 surfaces: translate the plan's group lists for surfaces with rows of `pitch` bytes (0: drop them).  After plan_build, with no step queued.
+int plan_set_src_pitch(Plan &p, int pitch);
 
 // rows of bw pixels -> rows of pitch pixels (the car sprite of a pitched handle)
 int plan_pad_image(hipStream_t st, const uint8_t *d_src, int bw, int pitch, int bh, uint8_t *d_dst);

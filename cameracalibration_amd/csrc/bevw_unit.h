@@ -542,6 +542,52 @@ static inline void unit_gsrc_nv12(const std::vector<uint32_t> &gsrc, int fw, int
         out[2 * i + 1] = cam * nv_frame + y_bytes + (y >> 1) * (uint32_t)fw + x;
     }
 }
+// NV12 surfaces (bevw_run_surfaces_device): the same list translated into offsets relative to the CAMERA'S OWN planes, whose rows are `pitch`
+// bytes apart (bevw_set_input_pitch; >= fw, a multiple of 4): out[2 i] = Y of texel (x, y) inside the Y plane, out[2 i + 1] = U of texel
+// (x, y) inside the U / V plane | the camera (0 .. 3) in the two low bits -- group offsets are multiples of 4 (x % 4 == 0, pitch % 4 == 0),
+// so the bits are free (unit_surf_cam / unit_surf_uv).  A slot without a group holds kPairNoGroup twice (out of every plane's range).
+// Planes are pitch * fh and pitch * fh / 2 bytes, both multiples of 4: every dword of a group load lies either inside its plane or outside
+// the plane's buffer descriptor as a whole.
+// `units` != nullptr (a unit list; units[2 k], units[2 k + 1] = first slot and slot count of unit k): returns false when some unit names more
+// than two cameras or names them out of ascending slot order -- the unit kernel keeps two cameras per wave and one boundary lane per round
+// (plan_unit_run).  A unit samples at most two cameras and its slots are dealt in ascending frame-set order, so this does not happen; a
+// list that fails is not used (the per-tap kernel then serves every tile).
+static inline bool unit_gsrc_surf(const std::vector<uint32_t> &gsrc, int fw, int fh, int pitch, std::vector<uint32_t> &out,
+                                  const std::vector<uint32_t> *units = nullptr)
+{
+    out.assign(gsrc.size() * 2, kPairNoGroup);
+    const uint32_t frame_bytes = (uint32_t)fw * fh * 3, row_bytes = (uint32_t)fw * 3;
+    for (size_t i = 0; i < gsrc.size(); ++i) {
+        if (gsrc[i] == kPairNoGroup) continue;
+        const uint32_t cam = gsrc[i] / frame_bytes, t = gsrc[i] % frame_bytes, y = t / row_bytes, x = t % row_bytes / 3;
+        out[2 * i] = y * (uint32_t)pitch + x;
+        out[2 * i + 1] = ((y >> 1) * (uint32_t)pitch + x) | cam;
+    }
+    if (!units) return true;
+    for (size_t k = 0; k + 1 < units->size(); k += 2) {
+        uint32_t first = 0, last = 0;
+        bool any = false;
+        for (size_t i = (*units)[k]; i < (size_t)(*units)[k] + (*units)[k + 1] && i < gsrc.size(); ++i) {
+            if (gsrc[i] == kPairNoGroup) continue;
+            const uint32_t cam = gsrc[i] / frame_bytes;
+            if (!any) { first = last = cam; any = true; }
+            if (cam < last || (cam != first && last != first && cam != last)) return false;
+            last = cam;
+        }
+    }
+    return true;
+}
+// first slot and slot count of every unit's group list, for unit_gsrc_surf
+static inline std::vector<uint32_t> unit_slot_ranges(const UnitPlanHost &up)
+{
+    std::vector<uint32_t> r;
+    for (int c = 0; c < kUnitClasses; ++c)
+        for (uint32_t u : up.list[c]) {
+            r.push_back(up.desc[u].gs_off * (uint32_t)kUnitThreads);
+            r.push_back(up.desc[u].groups ? (uint32_t)(kUnitClassGR[c] * kUnitThreads) : 0u);
+        }
+    return r;
+}
 // bytes between the compact scratch copies of consecutive frame sets: the groups + the 4 bytes the last slot's load reaches beyond them,
 // rounded to whole 64-byte sectors
 static inline size_t unit_compact_stride(size_t ngroups) { return (ngroups * 12 + 16 + 63) / 64 * 64; }
@@ -779,9 +825,20 @@ __device__ __forceinline__ void unit_store_dword(uint32_t v, __amdgpu_buffer_rsr
 // and stores one Y dword and, on even rows, one U / V dword -- the chroma of the two 2 x 2 blocks whose top-left pixels it holds.  Quads start
 // at x % 4 == 0 (unit left edges and the skew are multiples of 4), so no unit needs another unit's pixels and the plan is the BGR one.
 // The 16-byte store format does not apply (a quad is 4 bytes of Y).  ooff_masked holds the quad's Y offset; the car (BGR) is read at 3 times it.
-template <bool BLEND, bool SUMS, int NQ, int GR, int NCON, bool WIDE = false, bool NV12 = false, bool OUT_NV12 = false>
+// SURF (with NV12): the frames are NV12 surfaces -- a.surf[frame set][camera] = the two plane pointers, rows of a.src_pitch bytes -- and
+// a.un_gsrc holds offsets inside the camera's own planes with the camera in the low bits (unit_gsrc_surf).  A unit samples one camera or
+// two, and its group slots are dealt in ascending frame-set order (unit_gsrc_surf verifies both): a wave's lanes name camera A, or -- from
+// one lane of one round on -- camera B.  Per FRAME the wave reads the two cameras' plane pointers from the table with two scalar loads
+// (s_load_dwordx4 through the constant address space, wave-uniform index; tests/test_nv12_surfaces_host.py finds them in the built code
+// object), one frame ahead of the group loads that use them, and builds one range-checked descriptor per plane (num_records = the plane's
+// bytes): wave-uniform by construction, no waterfall loop, nothing per round or lane.  A round that names one camera issues its loads
+// once; the one mixed instruction of a unit is issued twice, under the execution masks lane < split and lane >= split: the masked-off lanes
+// issue no request, so every group is requested exactly once, and nothing is kept per lane beyond the two offsets the packed NV12 kernel
+// keeps.  (Option (b) of the three in DESIGN.md "NV12 surfaces".)
+template <bool BLEND, bool SUMS, int NQ, int GR, int NCON, bool WIDE = false, bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
 __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk, uint32_t unit, uint8_t *lds, uint4 *wave_sums = nullptr)
 {
+    static_assert(!SURF || NV12, "surfaces are NV12");
     static_assert(NQ >= 1 && NQ <= kUnitMaxNQ && GR >= 1 && GR <= kUnitMaxGR && (NCON == 1 || NCON == 2), "unit class");
     static_assert(!(WIDE && SUMS), "wide plans carry no channel sums");
     static_assert(!(NV12 && (SUMS || WIDE)), "NV12 units: table projection, raw frames");
@@ -916,6 +973,48 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
             gs[r] = once_load<BEVW_PLAN_NT>(a.un_gsrc + ((size_t)gs_off + r) * kUnitThreads + threadIdx.x);
         }
     }
+    // SURF: the wave's two cameras -- A = its first lane's, B = the other one its lanes name (B == A: one camera) -- and per round r the
+    // first lane of camera B (split_bits byte r; 64: the round is all A, 0: all B).  A unit's list names at most two cameras, in ascending
+    // order (unit_gsrc_surf checks it), so "lane < split" is "camera A" in every round.  The camera bits leave the lanes' offsets here.
+    uint32_t cam_a = 0, cam_b = 0, split_bits = 0;
+    if (SURF) {
+        {
+            const unsigned long long act = __builtin_amdgcn_ballot_w64(gs[0] != kPairNoGroup);
+            cam_a = cam_b = (uint32_t)__builtin_amdgcn_readlane((int)unit_surf_cam(gc[0]), act ? (int)__builtin_ctzll(act) : 0);
+        }
+#pragma unroll
+        for (int r = 0; r < GR; ++r) {
+            const bool has = gs[r] != kPairNoGroup;
+            const uint32_t cam = unit_surf_cam(gc[r]);
+            const unsigned long long other = __builtin_amdgcn_ballot_w64(has && cam != cam_a);
+            const uint32_t split = other ? (uint32_t)__builtin_ctzll(other) : 64u;
+            if (other) cam_b = (uint32_t)__builtin_amdgcn_readlane((int)cam, (int)(split & 63u));
+            split_bits |= split << (8 * r);
+            gc[r] = has ? unit_surf_uv(gc[r]) : kPairNoGroup;
+        }
+        cam_a = __builtin_amdgcn_readfirstlane(cam_a);
+        cam_b = __builtin_amdgcn_readfirstlane(cam_b);
+        split_bits = __builtin_amdgcn_readfirstlane(split_bits);
+    }
+    const uint32_t y_plane = (uint32_t)a.src_pitch * (uint32_t)a.fh, uv_plane = y_plane / 2;   // SURF: bytes of a surface's planes
+    // SURF: the plane pointers of cameras A and B of ONE frame set, in scalar registers: sp[0..3] = A's Y and U / V pointer, sp[4..7] = B's.
+    // The table is read through the constant address space with a wave-uniform index: two s_load_dwordx4 per frame, nothing per round or
+    // lane.  They are fetched one frame AHEAD of the group loads that use them (behind the stores of the frame before), so no vector load
+    // ever waits for a scalar load.
+    uint32_t sp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    typedef const __attribute__((address_space(4))) uint32_t *surf_table_ptr;
+    auto surf_fetch = [&](int b) {
+        const Nv12Surface *fs = a.surf + (size_t)min(b, b_end - 1) * (uint32_t)a.ncams;
+        const surf_table_ptr ta = (surf_table_ptr)(uintptr_t)(fs + cam_a), tb = (surf_table_ptr)(uintptr_t)(fs + cam_b);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { sp[k] = ta[k]; sp[4 + k] = tb[k]; }
+    };
+    // one range-checked descriptor per plane (num_records = the plane's bytes) of camera A (which = 0) or B (1)
+    auto surf_rsrc = [&](int which, __amdgpu_buffer_rsrc_t &ry, __amdgpu_buffer_rsrc_t &rc) {
+        const uint32_t *w = sp + 4 * which;
+        ry = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint8_t *>((uintptr_t)w[0] | ((uintptr_t)w[1] << 32)), 0, y_plane, kBufferWord3);
+        rc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint8_t *>((uintptr_t)w[2] | ((uintptr_t)w[3] << 32)), 0, uv_plane, kBufferWord3);
+    };
 
     // (Dealing the frames of a chunk strided over the batch, or rotating the class lists per XCD, changes nothing: profiles/r03/placement.md)
     auto frame_of = [&](int b) { return min(b, b_end - 1); };   // past the chunk: the last frame once more
@@ -925,6 +1024,34 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
     static_assert(D >= 2 && D % 2 == 0, "the patch halves alternate with the ring");
     pair_u32x4 pf[D][GR];
     auto issue = [&](int b, int ring) {
+        if constexpr (SURF) {
+            // (sp holds the pointers of frame b: surf_fetch ran a frame earlier)
+            __amdgpu_buffer_rsrc_t ry, rc;
+#pragma unroll
+            for (int r = 0; r < GR; ++r) {
+                // Y bytes x .. x+7 and U / V bytes x .. x+7 of the group, each inside its own plane: the second dword of the last group of a
+                // plane's last row lies past the plane (pitch == fw) -- outside the descriptor as a whole dword: zeros, no memory touched.
+                // A lane without a group is out of range of every plane.
+                const uint32_t split = (split_bits >> (8 * r)) & 255u;
+                if (split > 0u) {          // wave-uniform; all 64 lanes when the round names camera A alone
+                    surf_rsrc(0, ry, rc);
+                    if ((uint32_t)lane < split) {
+                        const pair_u32x2 yv = __builtin_amdgcn_raw_buffer_load_b64(ry, (int)gs[r], 0, kPairLoadAux);
+                        const pair_u32x2 cv = __builtin_amdgcn_raw_buffer_load_b64(rc, (int)gc[r], 0, kPairLoadAux);
+                        pf[ring][r] = pair_u32x4{yv.x, yv.y, cv.x, cv.y};
+                    }
+                }
+                if (split < 64u) {         // the lanes of camera B under their own execution mask: the others issue no request
+                    surf_rsrc(1, ry, rc);
+                    if ((uint32_t)lane >= split) {
+                        const pair_u32x2 yv = __builtin_amdgcn_raw_buffer_load_b64(ry, (int)gs[r], 0, kPairLoadAux);
+                        const pair_u32x2 cv = __builtin_amdgcn_raw_buffer_load_b64(rc, (int)gc[r], 0, kPairLoadAux);
+                        pf[ring][r] = pair_u32x4{yv.x, yv.y, cv.x, cv.y};
+                    }
+                }
+            }
+            return;
+        }
         const uint8_t *src = a.frames + (size_t)frame_of(b) * set_bytes;
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), 0, (uint32_t)set_bytes, kBufferWord3);
 #pragma unroll
@@ -1054,6 +1181,7 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
                 else store_slot(j, d[j][0], d[j][1], d[j][2], ro);
             }
         }
+        if constexpr (SURF) surf_fetch(b + D + 1);   // the pointers of the frame whose groups the NEXT step issues
         block_lds_barrier();       // DB: half[ring ^ 1] complete for everybody, half[ring] free for frame b+2; else: the patch is free
         if (SUMS && wave == 0 && lane < 3 && b < b_end) {
             // (slot ring & 1 is written again in frame b + 2, behind the barrier of frame b + 1, which this wave passes after these reads)
@@ -1063,7 +1191,11 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
     };
 #endif
 #pragma unroll
-    for (int u = 0; u < D; ++u) issue(b_begin + u, u);
+    for (int u = 0; u < D; ++u) {
+        if constexpr (SURF) surf_fetch(b_begin + u);
+        issue(b_begin + u, u);
+    }
+    if constexpr (SURF) surf_fetch(b_begin + D);
 #ifndef BEVW_EXPERIMENT_FRAME
     if (DB) {
         land(0);
@@ -1079,14 +1211,14 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
 
 // block -> (chunk, unit) of the list of ALL units in the partition's own (spatial) order, class in bits 28..31: neighbouring units run
 // at the same time on the same XCD, whatever their class, so the two halves of a sector that two units share meet in the L2
-template <bool BLEND, bool SUMS, bool NV12, bool OUT_NV12 = false>
+template <bool BLEND, bool SUMS, bool NV12, bool OUT_NV12 = false, bool SURF = false>
 __device__ __forceinline__ void plan_unit_any(const PlanArgs &a, uint32_t block_id, uint8_t *lds, uint4 *wave_sums)
 {
     uint32_t chunk, group;
     if (!plan_block_map(a, block_id, chunk, group)) return;
     if ((int)group >= a.nlist) return;
     const uint32_t e = __builtin_amdgcn_readfirstlane(a.tile_list[group]), unit = e & 0x0fffffffu;
-#define BEVW_UNIT_CASE(C) case C: plan_unit_run<BLEND, SUMS, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C], false, NV12, OUT_NV12>(a, chunk, unit, lds, wave_sums); break;
+#define BEVW_UNIT_CASE(C) case C: plan_unit_run<BLEND, SUMS, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C], false, NV12, OUT_NV12, SURF>(a, chunk, unit, lds, wave_sums); break;
     switch (e >> 28) {
         BEVW_UNIT_CASE(0) BEVW_UNIT_CASE(1) BEVW_UNIT_CASE(2) BEVW_UNIT_CASE(3)
         // class 4 (two quads per lane, two contributors): with float blend weights (rounds 3 - 5) its blend variant needed 177 .. 197 VGPRs and
@@ -1096,7 +1228,7 @@ __device__ __forceinline__ void plan_unit_any(const PlanArgs &a, uint32_t block_
 #if !BEVW_UNIT_NO_BIG   // (experiment builds without the (4, 4) class: every other class fits 128 VGPRs = 4 waves per SIMD; plans then need BEVW_UNIT_BIG=0)
         BEVW_UNIT_CASE(7)
 #endif
-        default: plan_unit_run<BLEND, SUMS, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6], false, NV12, OUT_NV12>(a, chunk, unit, lds, wave_sums); break;
+        default: plan_unit_run<BLEND, SUMS, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6], false, NV12, OUT_NV12, SURF>(a, chunk, unit, lds, wave_sums); break;
     }
 #undef BEVW_UNIT_CASE
 }
@@ -1136,6 +1268,21 @@ __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_
 {
     __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
     plan_unit_any<BLEND, false, IN_NV12, true>(a, blockIdx.x, patch, nullptr);
+}
+
+// NV12 surfaces (bevw_run_surfaces_device): the same launch over the SURF instantiation of plan_unit_run, writing BGR (k_units_surf) or NV12
+// images (k_units_out_surf).  Names of their own: k_plan_units stays the four BGR instantiations, k_units_nv12 / k_units_out_nv12 the packed ones.
+template <bool BLEND>
+__global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_surf(PlanArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
+    plan_unit_any<BLEND, false, true, false, true>(a, blockIdx.x, patch, nullptr);
+}
+template <bool BLEND>
+__global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_out_surf(PlanArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
+    plan_unit_any<BLEND, false, true, true, true>(a, blockIdx.x, patch, nullptr);
 }
 
 // wide plans (analytic projection): every unit class in one launch, partition order, as plan_unit_any

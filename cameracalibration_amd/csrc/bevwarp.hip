@@ -255,6 +255,77 @@ static void camera_mat_dst(const double K[9], int fw, int fh, double fs, double 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// NV12 surface tables (bevw_run_surfaces_device, bevw_remap_surfaces_device)
+// ---------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(bevw_nv12_surface) == sizeof(Nv12Surface) && sizeof(Nv12Surface) == 16, "a surface is two device pointers");
+
+// A caller's HOST table on its way to the device: copied into one of kSlots pinned buffers (the caller's array is free when the call
+// returns), uploaded on the engine's stream and read there by the step's kernels.  A slot is taken again only after the event recorded
+// behind the step that used it: up to kSlots steps are queued without any host synchronisation, the next one waits for the oldest.
+struct SurfStage {
+    static constexpr int kSlots = 4;
+    void *host[kSlots] = {}, *dev[kSlots] = {};
+    size_t cap[kSlots] = {};
+    hipEvent_t ev[kSlots] = {};
+    bool used[kSlots] = {};
+    int next = 0;
+    // checks the table (n entries) and enqueues its upload; d_tab: the device copy, slot: to be handed to done() behind the step
+    int stage(hipStream_t st, const bevw_nv12_surface *tab, size_t n, const Nv12Surface *&d_tab, int &slot)
+    {
+        for (size_t i = 0; i < n; ++i) {
+            if (!tab[i].y || !tab[i].uv) return fail(BEVW_E_INVALID, "surface %zu of the table has a NULL %s plane pointer", i, tab[i].y ? "U/V" : "Y");
+            if ((((uintptr_t)tab[i].y) | ((uintptr_t)tab[i].uv)) & 3u)
+                return fail(BEVW_E_INVALID, "surface %zu of the table has a plane pointer that is not 4-byte aligned", i);
+        }
+        slot = next;
+        next = (next + 1) % kSlots;
+        if (used[slot]) HIP_TRY(hipEventSynchronize(ev[slot]));
+        used[slot] = false;
+        const size_t bytes = n * sizeof(Nv12Surface);
+        if (bytes > cap[slot]) {
+            if (host[slot]) (void)hipHostFree(host[slot]);
+            if (dev[slot]) (void)hipFree(dev[slot]);
+            host[slot] = dev[slot] = nullptr; cap[slot] = 0;
+            HIP_TRY(hipHostMalloc(&host[slot], bytes, hipHostMallocDefault));
+            HIP_TRY(hipMalloc(&dev[slot], bytes));
+            cap[slot] = bytes;
+        }
+        if (!ev[slot]) HIP_TRY(hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming));
+        memcpy(host[slot], tab, bytes);
+        HIP_TRY(hipMemcpyAsync(dev[slot], host[slot], bytes, hipMemcpyHostToDevice, st));
+        d_tab = static_cast<const Nv12Surface *>(dev[slot]);
+        return BEVW_OK;
+    }
+    int done(hipStream_t st, int slot)
+    {
+        HIP_TRY(hipEventRecord(ev[slot], st));
+        used[slot] = true;
+        return BEVW_OK;
+    }
+    void release()
+    {
+        for (int i = 0; i < kSlots; ++i) {
+            if (used[i]) (void)hipEventSynchronize(ev[i]);
+            if (host[i]) (void)hipHostFree(host[i]);
+            if (dev[i]) (void)hipFree(dev[i]);
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+            host[i] = dev[i] = nullptr; ev[i] = nullptr; cap[i] = 0; used[i] = false;
+        }
+    }
+};
+
+// the rules of an input pitch (bevw_set_input_pitch, bevw_remapper_set_input_pitch): 0 = the frame width
+static int check_input_pitch(int pitch_bytes, int fw, int fh, bool nv12)
+{
+    if (pitch_bytes == 0) return BEVW_OK;
+    if (!nv12) return fail(BEVW_E_INVALID, "an input pitch needs NV12 input (BEVW_INPUT_NV12): BGR frames are dense");
+    if (pitch_bytes < fw || pitch_bytes % 4 != 0)
+        return fail(BEVW_E_INVALID, "input pitch must be a multiple of 4 bytes >= the frame width %d, got %d", fw, pitch_bytes);
+    if ((long long)pitch_bytes * fh >= (1ll << 30)) return fail(BEVW_E_INVALID, "input pitch %d x %d rows: plane too large for 30-bit texel offsets", pitch_bytes, fh);
+    return BEVW_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // bevw_remapper
 // ---------------------------------------------------------------------------------------------------------------
 struct bevw_remapper {
@@ -270,6 +341,9 @@ struct bevw_remapper {
     int input_format = BEVW_INPUT_BGR;   // bevw_remapper_set_input_format
     int output_format = BEVW_OUTPUT_BGR; // bevw_remapper_set_output_format
     bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
+    int in_pitch_request = 0;            // bevw_remapper_set_input_pitch (0: the source width)
+    int in_pitch() const { return in_pitch_request ? in_pitch_request : sw; }
+    SurfStage surf_stage;                // bevw_remap_surfaces_device
 };
 
 // cv2.remap as a 1-camera stitch: every destination pixel has exactly one contributor with mask 255.
@@ -313,11 +387,18 @@ static int remapper_alloc(int device, int sw, int sh, int dw, int dh, bevw_remap
 
 // nv12: the sources are NV12 frames (bevw_remapper_set_input_format); out_nv12: the destinations are dense NV12 images
 // (bevw_remapper_set_output_format)
+// d_surf: the sources are NV12 surfaces with rows of src_pitch bytes (bevw_remap_surfaces_device), d_src is not read
 static int remap_launch(hipStream_t st, const uint8_t *d_src, int sw, int sh, const int16_t *m1, const uint16_t *m2,
-                        int dw, int dh, int batch, uint8_t *d_dst, int ties_even = 0, bool nv12 = false, bool out_nv12 = false)
+                        int dw, int dh, int batch, uint8_t *d_dst, int ties_even = 0, bool nv12 = false, bool out_nv12 = false,
+                        const Nv12Surface *d_surf = nullptr, int src_pitch = 0)
 {
     for_each_chunk(batch, [&](int b0, int nb) {
-        if (out_nv12)
+        if (d_surf)
+            with_flags([&](auto on) {
+                hipLaunchKernelGGL((k_remap_lut<true, on, true>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, nullptr, sw, sh, m1, m2, dw, dh,
+                                   d_dst + (size_t)b0 * image_bytes_of(dw, dh, on), ties_even, d_surf + b0, src_pitch);
+            }, out_nv12);
+        else if (out_nv12)
             with_flags([&](auto nv) {
                 hipLaunchKernelGGL((k_remap_lut<nv, true>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, d_src + (size_t)b0 * frame_bytes_of(sw, sh, nv),
                                    sw, sh, m1, m2, dw, dh, d_dst + (size_t)b0 * image_bytes_of(dw, dh, true), ties_even);
@@ -509,9 +590,64 @@ int bevw_remapper_get_maps(bevw_remapper *r, int16_t *map1, uint16_t *map2)
     return BEVW_OK;
 }
 
+int bevw_remapper_set_input_pitch(bevw_remapper *r, int pitch_bytes)
+{
+    if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    BEVW_TRY(check_input_pitch(pitch_bytes, r->sw, r->sh, r->input_format == BEVW_INPUT_NV12));
+    BEVW_TRY(use_device(r->device));
+    HIP_TRY(hipStreamSynchronize(r->stream));   // (the group lists are read at launch: no step with the old pitch is still queued)
+    r->in_pitch_request = pitch_bytes;
+    if (r->plan_ready) BEVW_TRY(plan_set_src_pitch(r->plan, r->input_format == BEVW_INPUT_NV12 ? r->in_pitch() : 0));
+    return BEVW_OK;
+}
+
+// the checks the two surface entry points of a remapper share
+static int remap_need_surfaces(bevw_remapper *r, const void *table, int batch, void *d_dst)
+{
+    if (!r || !table || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
+    if (r->input_format != BEVW_INPUT_NV12) return fail(BEVW_E_INVALID, "surfaces are NV12: the remapper's input format is BGR (bevw_remapper_set_input_format)");
+    if (r->in_pitch() % 4 != 0)
+        return fail(BEVW_E_INVALID, "the source width %d is not a multiple of 4: surfaces need an input pitch that is (bevw_remapper_set_input_pitch)", r->sw);
+    return BEVW_OK;
+}
+
+// one remap step over a DEVICE table of `batch` surfaces
+static int remap_surfaces(bevw_remapper *r, const Nv12Surface *d_surf, int batch, void *d_dst)
+{
+    if (r->plan_ready && r->plan.src_pitch == r->in_pitch() && (((uintptr_t)d_dst) & 3u) == 0 && (!r->out_nv12() || r->dw % 4 == 0))
+        return plan_stitch(r->plan, r->stream, nullptr, batch, false, false, nullptr, nullptr, nullptr, nullptr, (uint8_t *)d_dst, false, 0, 0, nullptr, d_surf);
+    return remap_launch(r->stream, nullptr, r->sw, r->sh, r->map1.as<int16_t>(), r->map2.as<uint16_t>(), r->dw, r->dh, batch, (uint8_t *)d_dst,
+                        r->ties_even, true, r->out_nv12(), d_surf, r->in_pitch());
+}
+
+int bevw_remap_surface_table_device(bevw_remapper *r, const void *d_surfaces, int batch, void *d_dst)
+{
+    BEVW_TRY(remap_need_surfaces(r, d_surfaces, batch, d_dst));
+    if (((uintptr_t)d_surfaces) & 7u) return fail(BEVW_E_INVALID, "the surface table is not 8-byte aligned");
+    if (batch == 0) return BEVW_OK;
+    BEVW_TRY(use_device(r->device));
+    return remap_surfaces(r, static_cast<const Nv12Surface *>(d_surfaces), batch, d_dst);
+}
+
+int bevw_remap_surfaces_device(bevw_remapper *r, const bevw_nv12_surface *surfaces, int batch, void *d_dst)
+{
+    BEVW_TRY(remap_need_surfaces(r, surfaces, batch, d_dst));
+    if (batch == 0) return BEVW_OK;
+    BEVW_TRY(use_device(r->device));
+    const Nv12Surface *d_surf = nullptr;
+    int slot = 0;
+    BEVW_TRY(r->surf_stage.stage(r->stream, surfaces, (size_t)batch, d_surf, slot));
+    const int s = remap_surfaces(r, d_surf, batch, d_dst);
+    BEVW_TRY(r->surf_stage.done(r->stream, slot));
+    return s;
+}
+
 int bevw_remap_device(bevw_remapper *r, const void *d_src, int batch, void *d_dst)
 {
     if (!r || !d_src || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
+    if (r->in_pitch() != r->sw)
+        return fail(BEVW_E_INVALID, "the remapper's input pitch is %d, not the source width %d: its sources are NV12 surfaces, use bevw_remap_surfaces_device",
+                    r->in_pitch(), r->sw);
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
     // (NV12 images on the plan need dword-aligned quads in the caller's rows: a width that is not a multiple of 4 takes the per-pixel kernel)
@@ -545,12 +681,17 @@ int bevw_remapper_set_input_format(bevw_remapper *r, int format)
     HIP_TRY(hipStreamSynchronize(r->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
     r->input_format = format;
     r->plan.nv12 = format == BEVW_INPUT_NV12;
+    if (format != BEVW_INPUT_NV12) r->in_pitch_request = 0;   // (BGR sources are dense)
+    if (r->plan_ready) BEVW_TRY(plan_set_src_pitch(r->plan, format == BEVW_INPUT_NV12 ? r->in_pitch() : 0));
     return BEVW_OK;
 }
 
 int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst)
 {
     if (!r || !src || !dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
+    if (r->in_pitch() != r->sw)
+        return fail(BEVW_E_INVALID, "the remapper's input pitch is %d, not the source width %d: its sources are NV12 surfaces, use bevw_remap_surfaces_device",
+                    r->in_pitch(), r->sw);
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
     const size_t nin = (size_t)batch * frame_bytes_of(r->sw, r->sh, r->input_format == BEVW_INPUT_NV12), nout = (size_t)batch * image_bytes_of(r->dw, r->dh, r->out_nv12());
@@ -605,6 +746,7 @@ void bevw_remapper_destroy(bevw_remapper *r)
     if (hipSetDevice(r->device) == hipSuccess) {
         if (r->stream) (void)hipStreamSynchronize(r->stream);
         r->map1.release(); r->map2.release(); r->in.release(); r->out.release(); r->ones.release();
+        r->surf_stage.release();
         plan_release(r->plan);
         r->laps.release();
         if (r->ev0) (void)hipEventDestroy(r->ev0);
@@ -714,6 +856,9 @@ struct bevw_handle {
     int input_format = BEVW_INPUT_BGR;   // bevw_set_input_format
     bool nv12() const { return input_format == BEVW_INPUT_NV12; }
     size_t set_bytes() const { return frame_bytes_of(cfg.frame_width, cfg.frame_height, nv12()) * 4; }   // one camera frame set as the handle reads it
+    int in_pitch_request = 0;            // bevw_set_input_pitch (0: the frame width)
+    int in_pitch() const { return in_pitch_request ? in_pitch_request : cfg.frame_width; }   // bytes between the rows of an NV12 surface
+    SurfStage surf_stage;                // bevw_run_surfaces_device
     int output_format = BEVW_OUTPUT_BGR;   // bevw_set_output_format
     bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
     int compat[BEVW_COMPAT_KEYS] = {1, 1, 0, 0};   // bevw_set_compat values at bevw_build: a handle keeps the arithmetic it was built with
@@ -779,7 +924,7 @@ static int ensure_stats(bevw_handle *h, int batch)
     return BEVW_OK;
 }
 
-static int stitch_per_pixel(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out)
+static int stitch_per_pixel(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out, const Nv12Surface *d_surf = nullptr)
 {
     const bevw_config &c = h->cfg;
     const StitchTables T = stitch_tables(h);
@@ -788,7 +933,25 @@ static int stitch_per_pixel(bevw_handle *h, const uint8_t *d_frames, int batch, 
     unsigned long long *chs = h->chsums.as<unsigned long long>();
     for_each_chunk(batch, [&](int b0, int nb) {
         const dim3 grid((c.bev_width + 255) / 256, c.bev_height, nb), block(256);
-        const uint8_t *fr = d_frames + (size_t)b0 * h->set_bytes();
+        const uint8_t *fr = d_surf ? nullptr : d_frames + (size_t)b0 * h->set_bytes();
+        if (d_surf) {   // NV12 surfaces: surf[frame set][camera], rows of in_pitch() bytes
+            const Nv12Surface *sf = d_surf + (size_t)b0 * 4;
+            if (h->out_nv12() && !c.balance) {
+                uint8_t *o = d_out + (size_t)b0 * image_bytes_of(c.bev_width, c.bev_height, true);
+                with_flags([&](auto bl) {
+                    hipLaunchKernelGGL((k_stitch_pp<bl, false, true, true, true>), grid, block, 0, h->stream, nullptr, c.frame_width, c.frame_height, T,
+                                       c.bev_width, c.bev_height, nullptr, tab, d_car, nullptr, o, h->compat[BEVW_COMPAT_REMAP], sf, h->in_pitch());
+                }, c.blend != 0);
+                return;
+            }
+            uint8_t *o = d_out + (size_t)b0 * c.bev_width * c.bev_height * 3;
+            with_flags([&](auto bl, auto ba) {
+                hipLaunchKernelGGL((k_stitch_pp<bl, ba, true, false, true>), grid, block, 0, h->stream, nullptr, c.frame_width, c.frame_height, T,
+                                   c.bev_width, c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car, chs ? chs + b0 * 3 : nullptr, o,
+                                   h->compat[BEVW_COMPAT_REMAP], sf, h->in_pitch());
+            }, c.blend != 0, c.balance != 0);
+            return;
+        }
         if (h->out_nv12() && !c.balance) {   // NV12 images (the balance modes store the BGR pre-gain image: the gain pass converts)
             uint8_t *o = d_out + (size_t)b0 * image_bytes_of(c.bev_width, c.bev_height, true);
             with_flags([&](auto bl, auto nv) {
@@ -894,8 +1057,9 @@ static int stitch_analytic(bevw_handle *h, const uint8_t *d_frames, int batch, c
 
 // k_vsum over `nframes` frames on `st`; returns its blocks per frame.  part_stride > 0: every block stores its partial sum, part_stride entries
 // per frame; 0: the blocks of a frame add into its one entry (zeroed by the caller).  nv12_width > 0: NV12 frames of that width
+// d_surf: the frames are NV12 surfaces (one per frame) with rows of src_pitch bytes; d_frames is not read
 static int vsum_launch(hipStream_t st, const uint8_t *d_frames, int nframes, size_t frame_bytes, unsigned long long *d_vsums, int part_stride,
-                       int nv12_width = 0)
+                       int nv12_width = 0, const Nv12Surface *d_surf = nullptr, int src_pitch = 0)
 {
     const int vec_ok = (frame_bytes % 4 == 0 && ((uintptr_t)d_frames & 3u) == 0) ? 1 : 0;   // k_vsum's 12-byte loads
     int bpf = 2048 / (nframes > 0 ? nframes : 1);
@@ -903,6 +1067,11 @@ static int vsum_launch(hipStream_t st, const uint8_t *d_frames, int nframes, siz
     if (bpf > 256) bpf = 256;
     const size_t per_frame = part_stride > 0 ? (size_t)part_stride : 1;
     for_each_chunk(nframes, [&](int f0, int nf) {
+        if (d_surf) {
+            hipLaunchKernelGGL((k_vsum<true, true>), dim3(bpf, nf), dim3(256), 0, st, nullptr, frame_bytes, 0, d_vsums + (size_t)f0 * per_frame, part_stride,
+                               nv12_width, d_surf + f0, src_pitch);
+            return;
+        }
         with_flags([&](auto nv) {
             hipLaunchKernelGGL((k_vsum<nv>), dim3(bpf, nf), dim3(256), 0, st, d_frames + (size_t)f0 * frame_bytes, frame_bytes, vec_ok,
                                d_vsums + (size_t)f0 * per_frame, part_stride, nv12_width);
@@ -915,9 +1084,9 @@ static int vsum_launch(hipStream_t st, const uint8_t *d_frames, int nframes, siz
 // of k_vsum stores its partial sum, k_lum_delta adds them -- no atomics and no zeroing pass per step (round 5: the 4 KB hipMemsetAsync in
 // front of every slice's k_vsum cost 20 us of stream time, twice per config-4 step).
 static int luminance_stats(hipStream_t st, const uint8_t *d_frames, int nsets, int fw, int fh, unsigned long long *d_vsums, int *d_deltas,
-                           bool nv12 = false)
+                           bool nv12 = false, const Nv12Surface *d_surf = nullptr, int src_pitch = 0)
 {
-    const int bpf = vsum_launch(st, d_frames, nsets * 4, frame_bytes_of(fw, fh, nv12), d_vsums, kVsumParts, nv12 ? fw : 0);
+    const int bpf = vsum_launch(st, d_frames, nsets * 4, frame_bytes_of(fw, fh, nv12), d_vsums, kVsumParts, nv12 ? fw : 0, d_surf, src_pitch);
     hipLaunchKernelGGL(k_lum_delta, dim3((nsets + 63) / 64), dim3(64), 0, st, d_vsums, (double)fw * (double)fh, nsets,
                        d_deltas, bpf, kVsumParts);
     return launch_check("k_vsum/k_lum_delta");
@@ -986,7 +1155,7 @@ static int gain_car(bevw_handle *h, const uint8_t *d_car, const uint8_t *&car)
 // decode batch, bevwarp_jpeg.hip).  BEVW_BAL_SKEW=1 starts the second stream one V-sum pass late (measured: no better).
 // (Round 2 measured sub-batches of 16 ... 128 frame sets run ONE AFTER THE OTHER for Infinity-Cache residency: slower, the small grids
 // cost more than the cache returns; profiles/r02/sweeps.log.)
-static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out)
+static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out, const Nv12Surface *d_surf = nullptr)
 {
     const bevw_config &c = h->cfg;
     const size_t npx = (size_t)h->pitch_px * c.bev_height;
@@ -1034,11 +1203,12 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
         const int b0 = (int)((long long)batch * part / parts), n = (int)((long long)batch * (part + 1) / parts) - b0;
         if (!n) continue;
         hipStream_t st = (part & 1) ? h->stream2 : h->stream;
-        const uint8_t *fr = d_frames + (size_t)b0 * set_bytes;
+        const uint8_t *fr = d_surf ? nullptr : d_frames + (size_t)b0 * set_bytes;
+        const Nv12Surface *sf = d_surf ? d_surf + (size_t)b0 * 4 : nullptr;   // NV12 surfaces: the slice's part of the table
         // (Deriving the deltas inside k_lum_groups instead of by k_lum_delta, a kernel of its own in between, measured SLOWER: 1.669 against
         // 1.660 ms, profiles/r05/ab_call17...: 22 k blocks repeat four fp64 divisions.  The switch is gone.)
         BEVW_TRY(luminance_stats(st, fr, n, c.frame_width, c.frame_height, h->vsums.as<unsigned long long>() + (size_t)b0 * 4 * kVsumParts,
-                                 h->deltas.as<int>() + (size_t)b0 * 4, h->nv12()));
+                                 h->deltas.as<int>() + (size_t)b0 * 4, h->nv12(), sf, h->in_pitch()));
         if (part == 0 && parts > 1 && skew_env) {   // the other stream's first slice starts when this one's V sums are done
             HIP_TRY(hipEventRecord(h->ev_skew, h->stream));
             HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_skew, 0));
@@ -1046,10 +1216,10 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
         const size_t slot0 = ring ? (size_t)(part & 1) * slice_max : (size_t)b0;   // the slice's first frame-set slot in the intermediate buffers
         uint8_t *shifted = h->tmp.as<uint8_t>() + slot0 * cstride;
         uint8_t *pre = gain_in + (pre_ring ? slot0 : (size_t)b0) * npx * 3;
-        BEVW_TRY(plan_lum_groups(h->plan, st, fr, shifted, n, h->deltas.as<int>() + (size_t)b0 * 4, h->hsv.as<HsvTables>()));
+        BEVW_TRY(plan_lum_groups(h->plan, st, fr, shifted, n, h->deltas.as<int>() + (size_t)b0 * 4, h->hsv.as<HsvTables>(), sf));
         const bool lut_ok = npx % 4 == 0;   // (odd image sizes: the byte-wise gain kernel, in place, from k_reduce_psums' sums)
         BEVW_TRY(plan_stitch(h->plan, st, fr, n, c.blend != 0, false, h->deltas.as<int>() + (size_t)b0 * 4, h->hsv.as<HsvTables>(), nullptr,
-                             lut_ok ? nullptr : h->chsums.as<unsigned long long>() + (size_t)b0 * 3, pre, true, batch, b0, shifted));
+                             lut_ok ? nullptr : h->chsums.as<unsigned long long>() + (size_t)b0 * 3, pre, true, batch, b0, shifted, sf));
         BEVW_TRY(gain_pass(h, st, pre, car, d_car, d_out, b0, n, lut_ok, true));
     }
     if (parts > 1) {   // everything the caller enqueues on the handle's stream afterwards sees the whole batch
@@ -1059,7 +1229,9 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
     return BEVW_OK;
 }
 
-static int run_device(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out)
+// d_surf: the frames are NV12 surfaces (bevw_run_surfaces_device: surf[frame set][4] on the device, rows of in_pitch() bytes) and d_frames is
+// nullptr; every kernel reads them in place -- no packing pass on any path
+static int run_device(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out, const Nv12Surface *d_surf = nullptr)
 {
     const bevw_config &c = h->cfg;
     const bool pitched = h->pitch_px != c.bev_width;
@@ -1072,11 +1244,11 @@ static int run_device(bevw_handle *h, const uint8_t *d_frames, int batch, const 
     // 0 = luminance round trip per fetched texel inside the per-tap kernel
     static const int bal_mode = [] { const char *s = getenv("BEVW_BAL_MODE"); return s ? atoi(s) : 1; }();
     if (h->projection == BEVW_PROJ_LUT && h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && c.balance && bal_mode == 1 && h->plan.compact_stride != 0)
-        return balance_plan_run(h, d_frames, batch, d_car, d_out);
+        return balance_plan_run(h, d_frames, batch, d_car, d_out, d_surf);
     if (c.balance) {
         BEVW_TRY(ensure_stats(h, batch));
         BEVW_TRY(luminance_stats(h->stream, d_frames, batch, c.frame_width, c.frame_height,
-                                 h->vsums.as<unsigned long long>(), h->deltas.as<int>(), h->nv12()));
+                                 h->vsums.as<unsigned long long>(), h->deltas.as<int>(), h->nv12(), d_surf, h->in_pitch()));
         HIP_TRY(hipMemsetAsync(h->chsums.p, 0, sizeof(unsigned long long) * 3 * (size_t)batch, h->stream));
     }
     // NV12 images: the balance modes stitch their BGR pre-gain image into a buffer of the handle's own (the gain pass converts); without
@@ -1091,9 +1263,9 @@ static int run_device(bevw_handle *h, const uint8_t *d_frames, int batch, const 
         BEVW_TRY(stitch_analytic(h, d_frames, batch, d_car, d_out));
     } else if (h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && plan_ok) {
         BEVW_TRY(plan_stitch(h->plan, h->stream, d_frames, batch, c.blend != 0, c.balance != 0, h->deltas.as<int>(),
-                             h->hsv.as<HsvTables>(), d_car, h->chsums.as<unsigned long long>(), st_out));
+                             h->hsv.as<HsvTables>(), d_car, h->chsums.as<unsigned long long>(), st_out, false, 0, 0, nullptr, d_surf));
     } else {
-        BEVW_TRY(stitch_per_pixel(h, d_frames, batch, d_car, st_out));
+        BEVW_TRY(stitch_per_pixel(h, d_frames, batch, d_car, st_out, d_surf));
     }
     if (c.balance) {
         const uint8_t *car = nullptr;
@@ -1237,6 +1409,7 @@ int bevw_build(bevw_handle *h)
     BEVW_TRY(plan_build(h->plan, st, T, cfg.frame_width, cfg.frame_height, bw, bh, ncams, h->pitch_px != bw ? h->pitch_px : 0, cfg.blend != 0));
     h->plan.nv12 = h->nv12();
     h->plan.out_nv12 = h->out_nv12();
+    BEVW_TRY(plan_set_src_pitch(h->plan, h->nv12() ? h->in_pitch() : 0));   // the group lists of NV12 surfaces (bevw_run_surfaces_device)
     if (h->shard_n) {
         if (!h->plan.usable) return fail(BEVW_E_INVALID, "camera shard needs the tile plan: %d contributors on some pixel", h->plan.max_contrib);
         // bounding box of the owned masks, widened to multiples of 4 pixels in x so that packed rows stay dword aligned
@@ -1293,6 +1466,8 @@ void bevw_destroy(bevw_handle *h)
         }
         h->hsv.release(); h->vsums.release(); h->deltas.release(); h->chsums.release(); h->sdeltas.release();
         h->in.release(); h->out.release(); h->car.release(); h->tmp.release(); h->pre.release(); h->car_pitched.release();
+        if (h->stream2) (void)hipStreamSynchronize(h->stream2);
+        h->surf_stage.release();
         plan_release(h->plan);
         plan_release(h->aplan);
         h->laps.release();
@@ -1400,7 +1575,27 @@ int bevw_set_input_format(bevw_handle *h, int format)
     if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
     h->input_format = format;
     h->plan.nv12 = h->nv12();
+    if (!h->nv12()) h->in_pitch_request = 0;   // (BGR frames are dense)
+    if (h->built) BEVW_TRY(plan_set_src_pitch(h->plan, h->nv12() ? h->in_pitch() : 0));
     return BEVW_OK;
+}
+
+int bevw_set_input_pitch(bevw_handle *h, int pitch_bytes)
+{
+    if (!h) return fail(BEVW_E_INVALID, "null handle");
+    BEVW_TRY(check_input_pitch(pitch_bytes, h->cfg.frame_width, h->cfg.frame_height, h->nv12()));
+    BEVW_TRY(use_device(h->cfg.device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (the group lists are read at launch: no step with the old pitch is still queued)
+    if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
+    h->in_pitch_request = pitch_bytes;
+    if (h->built) BEVW_TRY(plan_set_src_pitch(h->plan, h->nv12() ? h->in_pitch() : 0));
+    return BEVW_OK;
+}
+
+int bevw_input_pitch(bevw_handle *h)
+{
+    if (!h) return fail(BEVW_E_INVALID, "null handle");
+    return h->in_pitch();
 }
 
 int bevw_input_format(bevw_handle *h)
@@ -1450,13 +1645,55 @@ static int download_images(bevw_handle *h, uint8_t *out, const void *d_src, size
     return BEVW_OK;
 }
 
+// the packed entry points on a handle with a padded input pitch: refused before anything is reserved or enqueued
+static int need_packed_frames(bevw_handle *h)
+{
+    if (h->in_pitch() != h->cfg.frame_width)
+        return fail(BEVW_E_INVALID, "the handle's input pitch is %d, not FRAME_WIDTH %d: its frames are NV12 surfaces, use bevw_run_surfaces_device "
+                    "or bevw_run_surface_table_device", h->in_pitch(), h->cfg.frame_width);
+    return BEVW_OK;
+}
+
 int bevw_run_device(bevw_handle *h, const void *d_frames, int batch, const void *d_car, void *d_out)
 {
     BEVW_TRY(need_built(h));
     if (h->shard_n) return fail(BEVW_E_INVALID, "handle is a camera shard: use bevw_shard_run_device + bevw_combine_device");
     if (!d_frames || !d_out || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
+    BEVW_TRY(need_packed_frames(h));
     if (batch == 0) return BEVW_OK;
     return run_device(h, (const uint8_t *)d_frames, batch, (const uint8_t *)d_car, (uint8_t *)d_out);
+}
+
+static int need_surfaces(bevw_handle *h, const void *table, int batch, void *d_out)
+{
+    BEVW_TRY(need_built(h));
+    if (h->shard_n) return fail(BEVW_E_INVALID, "NV12 surfaces are not available on camera-shard handles");
+    if (!h->nv12()) return fail(BEVW_E_INVALID, "surfaces are NV12: the handle's input format is BGR (bevw_set_input_format)");
+    if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "NV12 surfaces are not available with the analytic projection");
+    if (h->in_pitch() % 4 != 0)   // (a frame width that is even but not a multiple of 4: the default pitch, FRAME_WIDTH, does not serve)
+        return fail(BEVW_E_INVALID, "FRAME_WIDTH %d is not a multiple of 4: surfaces need an input pitch that is (bevw_set_input_pitch)", h->cfg.frame_width);
+    if (!table || !d_out || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
+    return BEVW_OK;
+}
+
+int bevw_run_surface_table_device(bevw_handle *h, const void *d_surfaces, int batch, const void *d_car, void *d_out)
+{
+    BEVW_TRY(need_surfaces(h, d_surfaces, batch, d_out));
+    if (((uintptr_t)d_surfaces) & 7u) return fail(BEVW_E_INVALID, "the surface table is not 8-byte aligned");
+    if (batch == 0) return BEVW_OK;
+    return run_device(h, nullptr, batch, (const uint8_t *)d_car, (uint8_t *)d_out, static_cast<const Nv12Surface *>(d_surfaces));
+}
+
+int bevw_run_surfaces_device(bevw_handle *h, const bevw_nv12_surface *surfaces, int batch, const void *d_car, void *d_out)
+{
+    BEVW_TRY(need_surfaces(h, surfaces, batch, d_out));
+    if (batch == 0) return BEVW_OK;
+    const Nv12Surface *d_surf = nullptr;
+    int slot = 0;
+    BEVW_TRY(h->surf_stage.stage(h->stream, surfaces, (size_t)batch * 4, d_surf, slot));
+    const int s = run_device(h, nullptr, batch, (const uint8_t *)d_car, (uint8_t *)d_out, d_surf);
+    BEVW_TRY(h->surf_stage.done(h->stream, slot));   // (behind whatever was enqueued: the slot's table stays until then)
+    return s;
 }
 
 int bevw_run(bevw_handle *h, const uint8_t *frames, int batch, const uint8_t *car, uint8_t *out)
@@ -1464,6 +1701,7 @@ int bevw_run(bevw_handle *h, const uint8_t *frames, int batch, const uint8_t *ca
     BEVW_TRY(need_built(h));
     if (h->shard_n) return fail(BEVW_E_INVALID, "handle is a camera shard: use bevw_shard_run_device + bevw_combine_device");
     if (!frames || !out || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
+    BEVW_TRY(need_packed_frames(h));
     if (batch == 0) return BEVW_OK;
     const bevw_config &c = h->cfg;
     const size_t nin = (size_t)batch * h->set_bytes();
@@ -1490,6 +1728,7 @@ int bevw_run_cameras(bevw_handle *h, const uint8_t *front, const uint8_t *back, 
     BEVW_TRY(need_built(h));
     if (h->shard_n) return fail(BEVW_E_INVALID, "handle is a camera shard: use bevw_shard_run_device + bevw_combine_device");
     if (!front || !back || !left || !right || !out) return fail(BEVW_E_INVALID, "bad argument");
+    BEVW_TRY(need_packed_frames(h));
     const bevw_config &c = h->cfg;
     const size_t frame = h->set_bytes() / 4, bev = (size_t)c.bev_width * c.bev_height * 3;
     BEVW_TRY(h->in.reserve(frame * 4));

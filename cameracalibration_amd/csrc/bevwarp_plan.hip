@@ -7,7 +7,7 @@ namespace bevw {
 
 void plan_release(Plan &p)
 {
-    void *ptrs[] = {p.un_desc, p.un_entries, p.un_gsrc, p.un_gsrc_compact, p.un_gsrc_nv12, p.list_un_all, p.entries, p.hdr, p.groups, p.groups_nv12, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
+    void *ptrs[] = {p.un_desc, p.un_entries, p.un_gsrc, p.un_gsrc_compact, p.un_gsrc_nv12, p.list_un_all, p.entries, p.hdr, p.groups, p.groups_nv12, p.un_gsrc_surf, p.groups_surf, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     p = Plan();
@@ -74,17 +74,26 @@ int plan_build(Plan &p, hipStream_t st, const StitchTables &T, int fw, int fh, i
 }
 
 int plan_stitch(Plan &p, hipStream_t st, const uint8_t *d_frames, int batch, bool blend, bool balance, const int *d_deltas, const HsvTables *d_tab,
-                const uint8_t *d_car, unsigned long long *d_chsums, uint8_t *d_out, bool sums, int psums_frames, int psums_first, const uint8_t *d_scratch)
+                const uint8_t *d_car, unsigned long long *d_chsums, uint8_t *d_out, bool sums, int psums_frames, int psums_first, const uint8_t *d_scratch,
+                const Nv12Surface *d_surf)
 {
     hipError_t e = plan_stitch_impl(p, st, d_frames, batch, blend, balance, d_deltas, d_tab, d_car, d_chsums, d_out, plan_tuning(), sums, psums_frames,
-                                    psums_first, d_scratch);
+                                    psums_first, d_scratch, d_surf);
     if (e != hipSuccess) return fail(BEVW_E_HIP, "tile-plan stitch launch failed: %s", hipGetErrorString(e));
     return BEVW_OK;
 }
 
-int plan_lum_groups(const Plan &p, hipStream_t st, const uint8_t *d_frames, uint8_t *d_scratch, int batch, const int *d_deltas, const HsvTables *d_tab)
+int plan_set_src_pitch(Plan &p, int pitch)
 {
-    hipError_t e = plan_lum_band(p, st, d_frames, d_scratch, batch, d_deltas, d_tab);
+    hipError_t e = plan_src_pitch_impl(p, pitch);
+    if (e != hipSuccess) return fail(BEVW_E_HIP, "uploading the surface group lists failed: %s", hipGetErrorString(e));
+    return BEVW_OK;
+}
+
+int plan_lum_groups(const Plan &p, hipStream_t st, const uint8_t *d_frames, uint8_t *d_scratch, int batch, const int *d_deltas, const HsvTables *d_tab,
+                    const Nv12Surface *d_surf)
+{
+    hipError_t e = plan_lum_band(p, st, d_frames, d_scratch, batch, d_deltas, d_tab, d_surf);
     if (e != hipSuccess) return fail(BEVW_E_HIP, "k_lum_groups launch failed: %s", hipGetErrorString(e));
     return BEVW_OK;
 }

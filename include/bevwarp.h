@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define BEVW_ABI_VERSION 7
+#define BEVW_ABI_VERSION 8
 
 typedef enum bevw_status {
     BEVW_OK = 0,
@@ -169,12 +169,47 @@ int bevw_output_pitch(bevw_handle *h);   /* pixels per row of the handle's devic
  *   - an odd FW or FH;
  *   - together with BEVW_PROJ_ANALYTIC / BEVW_PROJ_ANALYTIC_F32 (in either order);
  *   - on camera-shard handles (in either order with bevw_set_camera_shard).
- * Not provided: BT.709 or full-range matrices, NV21, I420, YUYV / UYVY, a row pitch or separate plane pointers, a standalone converter.
+ * Decoder surfaces (a row pitch, every frame at an address of its own): bevw_set_input_pitch / bevw_run_surfaces_device below.
+ * Not provided: BT.709 or full-range matrices, NV21, I420, YUYV / UYVY, a standalone converter.
  * The per-camera tools (bevw_camera_undistort, ...) and the JPEG entry points keep taking BGR. */
 #define BEVW_INPUT_BGR 0
 #define BEVW_INPUT_NV12 1
 int bevw_set_input_format(bevw_handle *h, int format);
 int bevw_input_format(bevw_handle *h);   /* BEVW_INPUT_BGR or BEVW_INPUT_NV12 */
+/* NV12 decoder surfaces, read where they lie.  Four cameras are four decode sessions, each with its own pool of surfaces: a surface has a
+ * row pitch (padded to an alignment of the decoder's choosing), its U / V plane need not follow its Y plane, and the four frames of a frame
+ * set live at four unrelated addresses.  A surface is a pair of DEVICE pointers; a table holds one per (frame set, camera), camera order
+ * front, back, left, right.  The kernels read the planes in place -- no packing pass runs anywhere -- and the result is, byte for byte,
+ * what the same handle returns from bevw_run_device for the same frames packed densely (same arithmetic, taps outside the frame 0).
+ *   bevw_set_input_pitch   bytes between the rows of BOTH planes of EVERY surface of the handle; 0 = FRAME_WIDTH (the default).  Needs
+ *                          BEVW_INPUT_NV12 (set the format first); pitch >= FRAME_WIDTH and a multiple of 4.  Before or after bevw_build
+ *                          (after: the handle's queued steps are waited for; the tile plan itself does not change).  Setting the input
+ *                          format back to BGR resets the pitch to 0.
+ *   bevw_run_surfaces_device   `surfaces` is a HOST array [batch][4].  It is copied before the call returns (it may be reused at once), and
+ *                          consecutive calls on a handle need no host synchronisation between them (a fifth queued call waits for the first).
+ *   bevw_run_surface_table_device   the same table already in DEVICE memory (8-byte aligned): a decoder ring repeats, so build the table once.
+ *                          The library cannot look into a device table: NULL or misaligned plane pointers in it are NOT detected.
+ * Contract of a surface: the Y plane is pitch * FH bytes (FH rows, the first FW bytes of a row are texels), the U / V plane pitch * FH / 2
+ * bytes (FH / 2 rows, U first); both pointers 4-byte aligned; the planes may lie anywhere, in any order, any distance apart.  No load
+ * addresses a byte outside the two declared planes of the surface it reads: every group load goes through a range-checked buffer
+ * descriptor of exactly the plane's size.  Bytes of the padding columns FW .. pitch-1 may be read but never influence a result.  The same
+ * surface may appear any number of times in a table.
+ * d_car, d_out, the output pitch and the output format are exactly those of bevw_run_device; all three modes (direct, blend, blend +
+ * balance) and both schedules are served.  A frame width that is even but not a multiple of 4 runs without the unit schedule, as it does
+ * for packed frames.
+ * With an input pitch other than FRAME_WIDTH the packed entry points (bevw_run, bevw_run_device, bevw_run_cameras) are refused with
+ * BEVW_E_INVALID -- a packed layout with padded rows is not provided.  Also refused (BEVW_E_INVALID, the reason in bevw_last_error()): a BGR
+ * handle; a pitch < FRAME_WIDTH or not a multiple of 4 (a FRAME_WIDTH that is not a multiple of 4 therefore needs an explicit pitch); a NULL or misaligned plane pointer in a host table; camera-shard handles and the
+ * analytic projection (they refuse NV12 input already).
+ * Not provided: BGR surfaces, a pitch per plane or per camera, output surfaces with separate plane pointers. */
+typedef struct bevw_nv12_surface {   /* one decoded frame, device memory */
+    const void *y;    /* FH rows of `pitch` bytes, FW of them used */
+    const void *uv;   /* FH/2 rows of `pitch` bytes, U first; anywhere: not tied to y */
+} bevw_nv12_surface;
+int bevw_set_input_pitch(bevw_handle *h, int pitch_bytes);
+int bevw_input_pitch(bevw_handle *h);    /* bytes between the rows of a surface (FRAME_WIDTH unless set) */
+int bevw_run_surfaces_device(bevw_handle *h, const bevw_nv12_surface *surfaces, int batch, const void *d_car, void *d_out);
+int bevw_run_surface_table_device(bevw_handle *h, const void *d_surfaces, int batch, const void *d_car, void *d_out);
 /* BEV images as NV12 (what a hardware video encoder takes).  With BEVW_OUTPUT_NV12 one device image is a Y plane of BH rows of `pitch`
  * bytes followed by one interleaved U / V plane (U first) of BH/2 rows of `pitch` bytes, where pitch = bevw_output_pitch() (unchanged by the
  * format: BEV_WIDTH, BEV_WIDTH rounded up to 64, or the explicit multiple of 4): pitch * BH * 3 / 2 bytes per image, images back to back.
@@ -309,6 +344,13 @@ int bevw_remap_device(bevw_remapper *r, const void *d_src, int batch, void *d_ds
  * [batch][src_h*3/2][src_w] NV12 frames and write what cv2.remap writes for cv2.cvtColor(src, cv2.COLOR_YUV2BGR_NV12), in either
  * BEVW_COMPAT_REMAP mode.  Refused (BEVW_E_INVALID) for an odd src_w or src_h. */
 int bevw_remapper_set_input_format(bevw_remapper *r, int format);
+/* NV12 surfaces as sources (bevw_set_input_pitch has the contract): one pitch for the remapper, `surfaces` a HOST array [batch] of plane
+ * pairs, copied before the call returns; bevw_remap_surface_table_device takes the same table already in DEVICE memory (8-byte aligned; its
+ * pointers cannot be checked).  Either BEVW_COMPAT_REMAP mode, either output format.  With a pitch other than src_w bevw_remap and
+ * bevw_remap_device are refused. */
+int bevw_remapper_set_input_pitch(bevw_remapper *r, int pitch_bytes);
+int bevw_remap_surfaces_device(bevw_remapper *r, const bevw_nv12_surface *surfaces, int batch, void *d_dst);
+int bevw_remap_surface_table_device(bevw_remapper *r, const void *d_surfaces, int batch, void *d_dst);
 /* BEVW_OUTPUT_NV12 (bevw_set_output_format has the layout and the arithmetic): bevw_remap and bevw_remap_device write dst as dense NV12
  * images [batch][dst_h*3/2][dst_w] -- the NV12 form of what the BGR remapper writes.  Combines with either input format.  Refused
  * (BEVW_E_INVALID) for an odd dst_w or dst_h. */

@@ -1,0 +1,426 @@
+"""NV12 decoder surfaces read in place (bevw_set_input_pitch, bevw_run_surfaces_device, bevw_run_surface_table_device,
+bevw_remap_surfaces_device; BevGenerator.run_surfaces / run_surface_table, Undistorter.run_surfaces) on the GPU.
+
+The reference result is always the CPU oracle (oracle.RefBevGenerator, oracle.remap) on the BGR frames the NumPy specification
+(tests/_nv12_spec.py) makes of the NV12 input, compared with tolerance 0; NV12 output goes through tests/_nv12_out_spec.py.  Equality with
+the PACKED handle on the same frames is asserted in addition, never instead.  Every surface lies inside one arena allocated for the test
+(tests/_nv12_surfaces.py); no test points a table outside an allocation.  Run with `-m gpu` on an MI355X."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from cameracalibration_amd import workloads as W
+from tests import _nv12_out_spec as SO
+from tests import _nv12_spec as S
+from tests import _nv12_surfaces as SF
+from tests import test_nv12_gpu as TI
+from tests import test_nv12_out_gpu as TO
+
+pytestmark = pytest.mark.gpu
+
+SMALL_CFG = TI.SMALL_CFG
+small_rig, generator, uncovered, assert_same, random_car = TI.small_rig, TI.generator, TI.uncovered, TI.assert_same, TI.random_car
+assert_nv12 = TO.assert_nv12
+E_INVALID = -1
+
+
+@pytest.fixture(scope="module")
+def ffi():
+    from cameracalibration_amd import _ffi
+
+    _ffi.require_device()
+    return _ffi
+
+
+@pytest.fixture(scope="module")
+def SB():
+    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV
+
+    return surroundBEV
+
+
+def fetch(ffi, bev, d_out, cfg, b):
+    """Image b of a device buffer of the generator's images -> dense host array: BGR [BH, BW, 3] or NV12 [BH * 3 // 2, BW]."""
+    bh, bw = cfg["BEV_HEIGHT"], cfg["BEV_WIDTH"]
+    if bev.output_format == "nv12":
+        return d_out.download((bh * 3 // 2, bev.out_pitch), offset=b * bev.out_image_bytes)[:, :bw]
+    return d_out.download((bh, bev.out_pitch, 3), offset=b * bev.out_image_bytes)[:, :bw]
+
+
+def check_image(bev, got, want_bgr, none, what, car):
+    if bev.output_format == "nv12":
+        assert_nv12(got, want_bgr, none, what, black=car is None)
+    else:
+        assert_same(got, want_bgr, none, what)
+
+
+def run_table(ffi, bev, table, car, cfg):
+    """run_surfaces on a host table [B, 4, 2]; returns the device output buffer (caller frees) after the step finished."""
+    B = table.shape[0]
+    d_out = ffi.DeviceBuffer(B * bev.out_image_bytes)
+    d_out.fill(0x5a)
+    d_car = ffi.DeviceBuffer(car.nbytes).upload(car) if car is not None else None
+    try:
+        bev.run_surfaces(table, d_car.ptr if d_car else None, d_out.ptr, out_bytes=d_out.nbytes)
+        bev.sync()
+    finally:
+        if d_car:
+            d_car.free()
+    return d_out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 1. small rig: every mode, both schedules, with and without the car, BGR and NV12 images, three pitches
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pitch", ["fw", "fw+4", 512])
+@pytest.mark.parametrize("output_format", ["bgr", "nv12"])
+@pytest.mark.parametrize("with_car", [False, True])
+@pytest.mark.parametrize("sched", ["auto", "per_pixel"])
+@pytest.mark.parametrize("blend,balance", [(False, False), (True, False), (True, True)])
+def test_small_rig_matches_oracle_and_packed_handle(ffi, SB, oracle, blend, balance, sched, with_car, output_format, pitch):
+    cfg = SMALL_CFG
+    fw, fh = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"]
+    pitch = {"fw": fw, "fw+4": fw + 4}.get(pitch, pitch)
+    rng = np.random.default_rng(3000 + 16 * blend + 8 * balance + 4 * with_car + 2 * (output_format == "nv12") + pitch)
+    schedule = ffi.SCHED_PER_PIXEL if sched == "per_pixel" else ffi.SCHED_AUTO
+    kw = dict(blend=blend, balance=balance, schedule=schedule, input_format="nv12", output_format=output_format)
+    bev = generator(SB, small_rig(), cfg, input_pitch=pitch, **kw)
+    assert bev.in_pitch == pitch == ffi.lib().bevw_input_pitch(bev._engine.h)
+    if sched == "auto":
+        info = bev.plan_info()
+        assert info["schedule"] == ffi.SCHED_TILE_PLAN and info["tiles_staged"] > 0   # the unit kernel's surface instantiation runs
+    ref = oracle.RefBevGenerator(small_rig(), cfg, blend=blend, balance=balance)
+    car = random_car(rng, cfg) if with_car else None
+    nv = S.random_nv12(rng, (3, 4), fw, fh)
+    none = uncovered(ref)
+    assert none.any()
+    surf = SF.Surfaces(ffi, nv.reshape(12, fh * 3 // 2, fw), fw, fh, pitch, layout_seed=int(rng.integers(1 << 30)), fill_seed=7, mode="shuffled")
+    try:
+        d_out = run_table(ffi, bev, surf.table.reshape(3, 4, 2), car, cfg)
+        try:
+            packed = generator(SB, small_rig(), cfg, **kw).batch(nv, car)   # the packed handle on the same frames: an additional assertion
+            for b in range(3):
+                got = fetch(ffi, bev, d_out, cfg, b)
+                check_image(bev, got, ref(*S.nv12_to_bgr(nv[b]), car), none, "set %d" % b, car)
+                assert np.array_equal(got, packed[b]), "set %d differs from the packed handle" % b
+        finally:
+            d_out.free()
+    finally:
+        surf.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 1b. a frame width that is even but not a multiple of 4: no units (the per-tap kernel reads the surfaces), and the default pitch -- FW --
+#     is not a pitch: one must be set
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("blend,balance", [(False, False), (True, True)])
+def test_frame_width_not_a_multiple_of_4(ffi, SB, oracle, blend, balance):
+    cfg = dict(SMALL_CFG, FRAME_WIDTH=322)
+    fw, fh, pitch = 322, cfg["FRAME_HEIGHT"], 324
+    rng = np.random.default_rng(322 + blend)
+    nv = S.random_nv12(rng, (2, 4), fw, fh)
+    ref = oracle.RefBevGenerator(small_rig(), cfg, blend=blend, balance=balance)
+    none = uncovered(ref)
+    bev = generator(SB, small_rig(), cfg, blend=blend, balance=balance, input_format="nv12", input_pitch=pitch)
+    assert bev.plan_info()["tiles_staged"] == 0   # units need fw % 4 == 0
+    surf = SF.Surfaces(ffi, nv.reshape(8, fh * 3 // 2, fw), fw, fh, pitch, layout_seed=8, fill_seed=9, mode="split")
+    try:
+        d_out = run_table(ffi, bev, surf.table.reshape(2, 4, 2), None, cfg)
+        try:
+            packed = generator(SB, small_rig(), cfg, blend=blend, balance=balance, input_format="nv12").batch(nv)
+            for b in range(2):
+                got = fetch(ffi, bev, d_out, cfg, b)
+                assert_same(got, ref(*S.nv12_to_bgr(nv[b])), none, "set %d" % b)
+                assert np.array_equal(got, packed[b])
+            # without a pitch: refused, with the reason
+            plain = generator(SB, small_rig(), cfg, blend=blend, balance=balance, input_format="nv12")
+            assert ffi.lib().bevw_run_surfaces_device(plain._engine.h, ffi.ptr(surf.table), 2, None, d_out.ptr) == E_INVALID
+            assert b"bevw_set_input_pitch" in ffi.lib().bevw_last_error()
+        finally:
+            d_out.free()
+    finally:
+        surf.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 2. padding independence: two arenas that differ in every gap and padding byte (and in the layout of the U / V planes)
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("blend,balance", [(False, False), (True, True)])
+def test_gaps_and_padding_columns_never_reach_a_result(ffi, SB, blend, balance):
+    cfg = SMALL_CFG
+    fw, fh, pitch = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"], 384
+    rng = np.random.default_rng(41 + blend)
+    nv = S.random_nv12(rng, (2, 4), fw, fh).reshape(8, fh * 3 // 2, fw)
+    bev = generator(SB, small_rig(), cfg, blend=blend, balance=balance, input_format="nv12", input_pitch=pitch)
+    outs = []
+    for fill_seed, mode in ((11, "shuffled"), (12, "split")):
+        surf = SF.Surfaces(ffi, nv, fw, fh, pitch, layout_seed=5, fill_seed=fill_seed, mode=mode)
+        try:
+            if mode == "split":
+                d = surf.table[:, 1].astype(np.int64) - surf.table[:, 0].astype(np.int64)
+                assert len(set(d.tolist())) == 8 and (d < 0).any() and (d > 0).any()   # uv - y differs per surface, both signs
+            d_out = run_table(ffi, bev, surf.table.reshape(2, 4, 2), None, cfg)
+            outs.append(d_out.download((d_out.nbytes,)))
+            d_out.free()
+        finally:
+            surf.free()
+    # (padding columns of the OUTPUT images are unspecified: compare the BW columns only)
+    bh, bw = cfg["BEV_HEIGHT"], cfg["BEV_WIDTH"]
+    a, b = (o.reshape(2, bh, bev.out_pitch, 3)[:, :, :bw] for o in outs)
+    assert np.array_equal(a, b)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 3. ring reuse: a pool of 3 surfaces per camera, 8 frame sets drawing from it with repeats
+# ---------------------------------------------------------------------------------------------------------------
+def test_ring_reuse(ffi, SB, oracle):
+    cfg = SMALL_CFG
+    fw, fh, pitch = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"], 448
+    rng = np.random.default_rng(77)
+    pool = S.random_nv12(rng, (4, 3), fw, fh)   # [camera][slot]
+    surf = SF.Surfaces(ffi, pool.reshape(12, fh * 3 // 2, fw), fw, fh, pitch, layout_seed=9, fill_seed=10, mode="split")
+    try:
+        pick = rng.integers(0, 3, (8, 4))
+        pick[:, 2] = 1   # a stalled camera repeats one surface in every set
+        pick[3] = pick[2]   # a whole set handed out again
+        table = np.stack([np.stack([surf.table[c * 3 + pick[b, c]] for c in range(4)]) for b in range(8)])
+        for blend, balance in ((False, False), (True, True)):
+            bev = generator(SB, small_rig(), cfg, blend=blend, balance=balance, input_format="nv12", input_pitch=pitch)
+            ref = oracle.RefBevGenerator(small_rig(), cfg, blend=blend, balance=balance)
+            none = uncovered(ref)
+            d_out = run_table(ffi, bev, table, None, cfg)
+            try:
+                for b in range(8):
+                    frames = [S.nv12_to_bgr(pool[c, pick[b, c]]) for c in range(4)]
+                    assert_same(fetch(ffi, bev, d_out, cfg, b), ref(*frames), none, "set %d (blend %d)" % (b, blend))
+            finally:
+                d_out.free()
+    finally:
+        surf.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 4. BASELINE config 3 / config 4 geometry, batch 256, device-resident table, four per-camera regions
+# ---------------------------------------------------------------------------------------------------------------
+SAMPLED = TI.SAMPLED
+POOL = 12   # surfaces per camera: the 256 x 4 table draws from 48 surfaces through a permutation (keeps the upload at ~100 MB per pitch)
+
+
+@pytest.fixture(scope="module", params=[1280, 1536], ids=["pitch1280", "pitch1536"])
+def big_pool(ffi, request):
+    cfg = W.CONFIG_S
+    fw, fh, pitch = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"], request.param
+    rng = np.random.default_rng(330 + pitch)
+    frames = np.frombuffer(rng.bytes(4 * POOL * fw * fh * 3 // 2), np.uint8).reshape(4, POOL, fh * 3 // 2, fw)
+    # one arena PER CAMERA (four decode sessions, four unrelated regions), each with its own shuffled layout
+    arenas = [SF.Surfaces(ffi, frames[c], fw, fh, pitch, layout_seed=50 + c, fill_seed=60 + c, mode=("shuffled", "split")[c % 2]) for c in range(4)]
+    pick = np.stack([rng.permutation(256) % POOL for _ in range(4)], axis=1)   # [256, 4]
+    table = np.stack([np.stack([arenas[c].table[pick[b, c]] for c in range(4)]) for b in range(256)]).astype(np.uint64)
+    d_table = ffi.DeviceBuffer(table.nbytes).upload(table)
+    yield pitch, frames, pick, d_table
+    d_table.free()
+    for a in arenas:
+        a.free()
+
+
+@pytest.mark.parametrize("out_pitch", ["auto", "dense"])
+@pytest.mark.parametrize("blend,balance", [(False, False), (True, True)], ids=["config3", "config4"])
+def test_baseline_geometry_batch256_device_table(ffi, SB, oracle, big_pool, blend, balance, out_pitch):
+    cfg = W.CONFIG_S
+    pitch, frames, pick, d_table = big_pool
+    bev = generator(SB, W.rig_s(), cfg, blend=blend, balance=balance, output_pitch=out_pitch, input_format="nv12", input_pitch=pitch)
+    assert bev.plan_info()["tiles_staged"] > 0
+    d_out = ffi.DeviceBuffer(256 * bev.out_image_bytes)
+    try:
+        bev.run_surface_table(d_table.ptr, 256, None, d_out.ptr, out_bytes=d_out.nbytes)
+        bev.sync()
+        ref = oracle.RefBevGenerator(W.rig_s(), cfg, blend=blend, balance=balance)
+        none = uncovered(ref)
+        for b in SAMPLED:
+            want = ref(*[S.nv12_to_bgr(frames[c, pick[b, c]]) for c in range(4)])
+            assert_same(fetch(ffi, bev, d_out, cfg, b), want, none, "set %d of 256" % b)
+    finally:
+        d_out.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 5. the reference's own four camera images, CONFIG_R, blend + balance, with the car sprite, both schedules
+# ---------------------------------------------------------------------------------------------------------------
+def test_reference_images_blend_balance(ffi, SB, oracle, repo_rig):
+    cfg = W.CONFIG_R
+    fw, fh = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"]
+    nv = np.stack([S.bgr_to_nv12(f) for f in repo_rig.frames()])   # input generation only
+    car = SB.padding(repo_rig.image("car"), cfg["BEV_WIDTH"], cfg["BEV_HEIGHT"])
+    ref = oracle.RefBevGenerator(W.repo_rig(), cfg, blend=True, balance=True)
+    want = ref(*[S.nv12_to_bgr(f) for f in nv], car)
+    none = uncovered(ref)
+    pitch = (fw + 255) // 256 * 256 + 256
+    surf = SF.Surfaces(ffi, nv, fw, fh, pitch, layout_seed=3, fill_seed=4, mode="split")
+    try:
+        for sched in (ffi.SCHED_AUTO, ffi.SCHED_PER_PIXEL):
+            bev = generator(SB, W.repo_rig(), cfg, blend=True, balance=True, schedule=sched, input_format="nv12", input_pitch=pitch)
+            d_out = run_table(ffi, bev, surf.table.reshape(1, 4, 2), car, cfg)
+            try:
+                assert_same(fetch(ffi, bev, d_out, cfg, 0), want, none, "schedule %d" % sched)
+            finally:
+                d_out.free()
+    finally:
+        surf.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 6. undistort (BASELINE config 2 geometry) at batch 64, both BEVW_COMPAT_REMAP modes, pitch FW and a padded one
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("padded", [False, True], ids=["pitch_fw", "pitch_padded"])
+@pytest.mark.parametrize("ties_even", [0, 1])
+def test_undistort_batch64(ffi, oracle, ties_even, padded):
+    from cameracalibration_amd.Tools import undistort as U
+
+    cfg = W.CONFIG_UNDISTORT
+    w, h = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"]
+    pitch = (w + 255) // 256 * 256 + 64 if padded else w
+    K, D = W.undistort_calibration()
+    L = ffi.lib()
+    rng = np.random.default_rng(640 + ties_even + 2 * padded)
+    nv = S.random_nv12(rng, (64,), w, h)
+    surf = SF.Surfaces(ffi, nv, w, h, pitch, layout_seed=21, fill_seed=22, mode="split" if padded else "shuffled")
+    try:
+        ffi.check(L.bevw_set_compat(ffi.COMPAT_REMAP, ties_even))
+        oracle.set_variant(oracle.VARIANT_REMAP, ties_even)
+        und = U.Undistorter(K, D, w, h, focalscale=cfg["FOCAL_SCALE"], sizescale=cfg["SIZE_SCALE"], input_format="nv12", input_pitch=pitch)
+        assert und.in_pitch == pitch
+        d_out = ffi.DeviceBuffer(64 * und.out_image_bytes)
+        try:
+            und.run_surfaces(surf.table, d_out.ptr, out_bytes=d_out.nbytes)
+            und.sync()
+            got = d_out.download((64, und.out_h, und.out_w, 3))
+            d_out.fill(0x5a)   # the same table from device memory
+            d_table = ffi.DeviceBuffer(surf.table.nbytes).upload(surf.table)
+            try:
+                und.run_surface_table(d_table.ptr, 64, d_out.ptr, out_bytes=d_out.nbytes)
+                und.sync()
+                assert np.array_equal(got, d_out.download((64, und.out_h, und.out_w, 3))), "device table differs from host table"
+            finally:
+                d_table.free()
+        finally:
+            d_out.free()
+        Kd = oracle.camera_mat_dst(K, w, h, cfg["FOCAL_SCALE"], cfg["SIZE_SCALE"])
+        o1, o2 = oracle.fisheye_init_undistort_rectify_map(K, D, Kd, (und.out_w, und.out_h))
+        outside = (o1[..., 0] < -1) | (o1[..., 0] >= w) | (o1[..., 1] < -1) | (o1[..., 1] >= h)
+        for b in range(64):
+            assert_same(got[b], oracle.remap(S.nv12_to_bgr(nv[b]), o1, o2), outside, "image %d" % b)
+        if not padded:
+            assert np.array_equal(got, und(nv)), "differs from the packed remapper"
+        else:
+            with pytest.raises(ffi.BevwError, match="bevw_remap_surfaces_device"):
+                und(nv)
+        und.close()
+    finally:
+        L.bevw_set_compat(ffi.COMPAT_REMAP, 0)
+        oracle.set_variant(oracle.VARIANT_REMAP, 0)
+        surf.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 7. refusals
+# ---------------------------------------------------------------------------------------------------------------
+def test_refusals(ffi, SB):
+    L = ffi.lib()
+    cfg = SMALL_CFG
+    fw, fh = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"]
+    err = lambda: L.bevw_last_error()
+    # a BGR handle: no pitch, no surfaces
+    bgr = generator(SB, small_rig(), cfg)
+    assert L.bevw_set_input_pitch(bgr._engine.h, 512) == E_INVALID and b"NV12" in err()
+    dummy = np.zeros((1, 4, 2), np.uint64)
+    d_out = ffi.DeviceBuffer(bgr.out_image_bytes)
+    try:
+        assert L.bevw_run_surfaces_device(bgr._engine.h, ffi.ptr(dummy), 1, None, d_out.ptr) == E_INVALID and b"BGR" in err()
+        assert L.bevw_run_surface_table_device(bgr._engine.h, d_out.ptr, 1, None, d_out.ptr) == E_INVALID and b"BGR" in err()
+        with pytest.raises(Exception, match="input_format='nv12'"):
+            bgr.run_surfaces(dummy, None, d_out.ptr, out_bytes=d_out.nbytes)
+    finally:
+        d_out.free()
+    # the pitch rules
+    nv = generator(SB, small_rig(), cfg, input_format="nv12")
+    h = nv._engine.h
+    assert nv.in_pitch == fw
+    for bad in (fw - 4, fw + 2, 2, -4):
+        assert L.bevw_set_input_pitch(h, bad) == E_INVALID and b"multiple of 4" in err(), bad
+    assert L.bevw_input_pitch(h) == fw
+    # NULL and misaligned plane pointers in a host table; out_bytes too small
+    frames = S.random_nv12(np.random.default_rng(1), (4,), fw, fh)
+    surf = SF.Surfaces(ffi, frames, fw, fh, fw, mode="shuffled")
+    d_out = ffi.DeviceBuffer(nv.out_image_bytes)
+    try:
+        good = surf.table.reshape(1, 4, 2)
+        for cam, plane, value, word in ((1, 0, 0, b"NULL"), (2, 1, 0, b"NULL"), (0, 0, int(good[0, 0, 0]) + 2, b"aligned"), (3, 1, int(good[0, 3, 1]) + 1, b"aligned")):
+            t = good.copy()
+            t[0, cam, plane] = value
+            assert L.bevw_run_surfaces_device(h, ffi.ptr(t), 1, None, d_out.ptr) == E_INVALID and word in err(), (cam, plane)
+        with pytest.raises(Exception, match="need"):
+            nv.run_surfaces(good, None, d_out.ptr, out_bytes=d_out.nbytes - 1)
+        with pytest.raises(Exception, match="need"):
+            nv.run_surface_table(d_out.ptr, 2, None, d_out.ptr, out_bytes=d_out.nbytes)
+        with pytest.raises(Exception, match=r"\[B, 4, 2\]"):
+            nv.run_surfaces(good.reshape(4, 2), None, d_out.ptr, out_bytes=d_out.nbytes)
+        with pytest.raises(Exception, match=r"\[B, 4, 2\]"):
+            nv.run_surfaces(good.astype(np.int64), None, d_out.ptr, out_bytes=d_out.nbytes)
+        # a padded pitch: the packed entry points are refused and say which call to use; pitch 0 / FW: as before
+        ffi.check(L.bevw_set_input_pitch(h, fw + 64))
+        packed = np.zeros((1, 4, fh * 3 // 2, fw), np.uint8)
+        d_in = ffi.DeviceBuffer(packed.nbytes).upload(packed)
+        try:
+            assert L.bevw_run_device(h, d_in.ptr, 1, None, d_out.ptr) == E_INVALID and b"bevw_run_surfaces_device" in err()
+            with pytest.raises(ffi.BevwError, match="bevw_run_surfaces_device"):
+                nv.batch(packed)
+            with pytest.raises(ffi.BevwError, match="bevw_run_surfaces_device"):
+                nv(*packed[0])
+            ffi.check(L.bevw_set_input_pitch(h, 0))
+            assert L.bevw_input_pitch(h) == fw
+            ffi.check(L.bevw_run_device(h, d_in.ptr, 1, None, d_out.ptr))
+            ffi.check(L.bevw_sync(h))
+        finally:
+            d_in.free()
+    finally:
+        d_out.free()
+        surf.free()
+    # analytic projection and camera shards, in both orders where an order exists
+    with pytest.raises(ffi.BevwError, match="analytic"):
+        generator(SB, small_rig(), cfg, projection="analytic", input_format="nv12", input_pitch=512)
+    hh = TI.raw_handle(ffi)
+    try:
+        assert L.bevw_set_input_pitch(hh, 512) == E_INVALID and b"NV12" in err()        # BGR still
+        ffi.check(L.bevw_set_input_format(hh, ffi.INPUT_NV12))
+        ffi.check(L.bevw_set_input_pitch(hh, 512))
+        cams = (C.c_int32 * 2)(0, 2)
+        assert L.bevw_set_camera_shard(hh, cams, 2) == E_INVALID and b"NV12" in err()
+        assert L.bevw_set_projection(hh, ffi.PROJ_ANALYTIC) == E_INVALID and b"NV12" in err()
+        ffi.check(L.bevw_set_input_format(hh, ffi.INPUT_BGR))
+        assert L.bevw_input_pitch(hh) == fw                                              # BGR frames are dense again
+        ffi.check(L.bevw_set_camera_shard(hh, cams, 2))
+        assert L.bevw_set_input_format(hh, ffi.INPUT_NV12) == E_INVALID and b"shard" in err()
+        assert L.bevw_set_input_pitch(hh, 512) == E_INVALID and b"NV12" in err()
+    finally:
+        L.bevw_destroy(hh)
+    ana = generator(SB, small_rig(), cfg, projection="analytic_f32")
+    assert L.bevw_set_input_pitch(ana._engine.h, 512) == E_INVALID and b"NV12" in err()
+    # the remapper
+    from cameracalibration_amd.Tools import undistort as U
+
+    K, D = W.undistort_calibration()
+    with pytest.raises(Exception, match="input_format='nv12'"):
+        U.Undistorter(K, D, 64, 48, input_pitch=128)
+    with pytest.raises(Exception, match="multiple of 4"):
+        U.Undistorter(K, D, 64, 48, input_format="nv12", input_pitch=66)
+    und = U.Undistorter(K, D, 64, 48, input_format="nv12", input_pitch=128)
+    assert L.bevw_remapper_set_input_pitch(und._r, 60) == E_INVALID and b"multiple of 4" in err()
+    with pytest.raises(Exception, match=r"\[B, 2\]"):
+        und.run_surfaces(np.zeros((2, 4, 2), np.uint64), 0)
+    with pytest.raises(ffi.BevwError, match="NULL"):
+        und.run_surfaces(np.zeros((1, 2), np.uint64), 1)
+    und.close()
+    b = U.Undistorter(K, D, 64, 48)
+    assert L.bevw_remap_surfaces_device(b._r, ffi.ptr(np.ones((1, 2), np.uint64)), 1, 1) == E_INVALID and b"BGR" in err()
+    b.close()
