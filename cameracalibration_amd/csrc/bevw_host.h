@@ -1,7 +1,7 @@
 // bevw_host.h -- host-side plumbing shared by the translation units of libbevwarp.so (bevwarp.hip: handles, tables, tools, the
 // camera-per-GPU exchange; bevwarp_plan.hip: the tile plan and its kernels; bevwarp_jpeg.hip: the JPEG codec): the thread-local
-// error string behind bevw_last_error(), the HIP_TRY / BEVW_TRY early-return macros, device / pinned buffers, the lap timer, and the two
-// launch helpers (batch chunks, compile-time flags).
+// error string behind bevw_last_error(), the HIP_TRY / BEVW_TRY early-return macros, device / pinned buffers, the lap timer, and the
+// launch helpers (batch chunks, compile-time flags, compile-time pixel formats).
 #pragma once
 #include "../../include/bevwarp.h"
 
@@ -75,6 +75,21 @@ static inline void with_flags(F &&f, bool b, B... rest)
     if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
     else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
+
+// What a format-templated kernel reads, as a compile-time constant: packed BGR frames, packed NV12 frames or NV12 surfaces -- surfaces are
+// NV12, so a kernel's <NV12, SURF> pair is one of these three.  with_input: f(in) launches k<.., in.nv12, in.surf>.
+template <bool NV12, bool SURF> struct InputKind { static constexpr bool nv12 = NV12, surf = SURF; };
+template <typename F>
+static inline void with_input(bool nv12, bool surf, F &&f)
+{
+    if (surf) f(InputKind<true, true>{});
+    else if (nv12) f(InputKind<true, false>{});
+    else f(InputKind<false, false>{});
+}
+// ... x BGR / NV12 images: f(in, out_nv12) launches k<.., in.nv12, out_nv12, in.surf>.  Flags that exist with BGR images only (luminance
+// round trip, channel sums) stay with the caller: fixed under `if constexpr (out_nv12)`, walked by with_flags otherwise.
+template <typename F>
+static inline void with_formats(bool nv12, bool surf, bool out_nv12, F &&f) { with_input(nv12, surf, [&](auto in) { with_flags([&](auto on) { f(in, on); }, out_nv12); }); }
 
 // Lap timer: HIP events recorded on an engine's own stream WITHOUT synchronising, read back after the caller's final sync
 // (bench.py: one mark in front of every step -> per-step durations, median instead of one mean over a 13 ms region).

@@ -621,7 +621,7 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
         }
         p.band_ok = true;
         groups_host.swap(list);
-        p.groups_host = groups_host;   // (kept for plan_set_src_pitch)
+        p.groups_host = groups_host;   // (kept for plan_set_format)
     }
     std::vector<uint32_t> hdr((size_t)p.ntiles);
     if ((e = hipMemcpyAsync(hdr.data(), p.hdr, hdr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
@@ -649,7 +649,7 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
         if (!up.desc.empty()) {
             hdr.swap(hdr_un);
             if ((e = plan_upload_units(p, up)) != hipSuccess) return e;
-            p.un_gsrc_host = up.gsrc;   // (kept for plan_set_src_pitch)
+            p.un_gsrc_host = up.gsrc;   // (kept for plan_set_format)
             p.un_ranges_host = unit_slot_ranges(up);
             if (fh % 2 == 0) {   // the units' group lists for NV12 frame sets (k_plan_units<.., true>)
                 std::vector<uint32_t> nv;
@@ -676,15 +676,13 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
 }
 
 // NV12 surfaces: the third translation of the group lists (unit_gsrc_surf) -- the units' and the sampled-group list of the balance schedule --
-// for surfaces whose rows are `pitch` bytes apart.  The plan itself does not change.  Called when the pitch is set or after the plan was
-// built, whichever comes last (plan_build resets it); no step of the plan may be queued.
+// for surfaces whose rows are `pitch` bytes apart (plan_set_format).  The plan itself does not change; no step of the plan may be queued.
 static inline hipError_t plan_src_pitch_impl(Plan &p, int pitch)
 {
     for (void **q : {&p.un_gsrc_surf, &p.groups_surf}) {
         if (*q) (void)hipFree(*q);
         *q = nullptr;
     }
-    p.src_pitch = pitch;
     if (pitch <= 0 || p.fh % 2 != 0 || p.fw % 4 != 0) return hipSuccess;
     hipError_t e;
     std::vector<uint32_t> nv;
@@ -704,10 +702,11 @@ struct PlanTuning { int nb = 0; int xcd_map = 1; int units = 1; };
 
 // The PlanArgs fields the per-frame plan kernels share: geometry, unit tables, frames per block and the XCD map.  The caller adds its
 // tile list, its group count and what its kernel reads beyond these.
-static inline PlanArgs plan_args(const Plan &p, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out, const PlanTuning &tune)
+static inline PlanArgs plan_args(const Plan &p, const FrameSource &src, int batch, const uint8_t *d_car, uint8_t *d_out, const PlanTuning &tune)
 {
     PlanArgs a = {};
-    a.frames = d_frames; a.car = d_car; a.out = d_out;
+    a.frames = src.packed; a.surf = src.surf; a.src_pitch = src.pitch;
+    a.car = d_car; a.out = d_out;
     a.fw = p.fw; a.fh = p.fh; a.bw = p.bw; a.bh = p.bh; a.pitch = p.pitch;
     a.tiles_x = p.tiles_x; a.ntiles = p.ntiles; a.ncams = p.ncams;
     a.un_desc = static_cast<const UnitDesc *>(p.un_desc);
@@ -736,31 +735,37 @@ static inline unsigned plan_grid(const PlanArgs &a)
     return (unsigned)(a.ngroups * a.nchunks);
 }
 
-// One step of the tile plan on `st`.
-//   balance   = luminance round trip per tap on RAW frames (per-tap kernel over every tile) + per-tile channel sums;
-//   d_scratch = the compact scratch plan_lum_band filled from d_frames (balance schedule 1): the units read IT (p.compact_stride bytes per
-//               frame set, group lists p.un_gsrc_compact), the per-tap kernel serves what no unit owns from the RAW frames with the luminance
-//               round trip per tap (d_deltas, d_tab); everything on the per-tap kernel when the units cannot run;
-//   sums      = per-unit / per-tile channel sums, the car left to the gain pass (with d_scratch; or: d_frames are luminance-shifted already).
-// balance and sums end with k_reduce_psums into d_chsums.  psums_frames / psums_first: the psums buffer is sized for psums_frames frame sets
-// and this call's frames start at slot psums_first of it (two half-batches of one balance step run concurrently on two streams: run_device).
-static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t *d_frames, int batch, bool blend, bool balance,
-                                          const int *d_deltas, const HsvTables *d_tab, const uint8_t *d_car,
-                                          unsigned long long *d_chsums, uint8_t *d_out, const PlanTuning &tune, bool sums = false,
-                                          int psums_frames = 0, int psums_first = 0, const uint8_t *d_scratch = nullptr,
-                                          const Nv12Surface *d_surf = nullptr)
+// The unit kernel of a step.  Five names, so that k_plan_units stays the four BGR instantiations (bevw_unit.h).  nv12 / surf: what the UNITS
+// read -- the step's frames, or the BGR compact scratch of the balance schedule; channel sums exist with BGR in and out only.
+static inline void plan_launch_units(const PlanArgs &a, hipStream_t st, bool blend, bool sums, bool nv12, bool surf, bool out_nv12)
 {
-    // d_surf: the frames are NV12 surfaces (surf[frame set][ncams], rows of p.src_pitch bytes; p.nv12 is set) and d_frames is not read
+    const dim3 grid(plan_grid(a)), block(256);
+    with_formats(nv12, surf, out_nv12, [&](auto in, auto on) {
+        constexpr bool NV12 = decltype(in)::nv12, SURF = decltype(in)::surf, OUT_NV12 = decltype(on)::value;
+        with_flags([&](auto bl) {
+            if constexpr (SURF && OUT_NV12) hipLaunchKernelGGL((k_units_out_surf<bl>), grid, block, 0, st, a);
+            else if constexpr (SURF) hipLaunchKernelGGL((k_units_surf<bl>), grid, block, 0, st, a);
+            else if constexpr (OUT_NV12) hipLaunchKernelGGL((k_units_out_nv12<bl, NV12>), grid, block, 0, st, a);
+            else if constexpr (NV12) hipLaunchKernelGGL((k_units_nv12<bl>), grid, block, 0, st, a);
+            else with_flags([&](auto sm) { hipLaunchKernelGGL((k_plan_units<bl, sm>), grid, block, 0, st, a); }, sums);
+        }, blend);
+    });
+}
+
+// One step of the tile plan on `st` (PlanStep, bevw_planapi.h).
+static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanStep &s, const PlanTuning &tune)
+{
     hipError_t e;
-    const bool surf = d_surf != nullptr;
-    if (surf && (!p.nv12 || p.src_pitch < p.fw || p.src_pitch % 4 != 0)) return hipErrorInvalidValue;
-    PlanArgs a = plan_args(p, d_frames, batch, d_car, d_out, tune);
-    a.surf = d_surf; a.src_pitch = p.src_pitch;
+    const int batch = s.batch;
+    const bool surf = s.src.is_surf();
+    if (s.src.nv12 != p.nv12 || s.src.cams != p.ncams || (surf && (s.src.pitch != p.src_pitch || p.src_pitch < p.fw || p.src_pitch % 4 != 0)))
+        return hipErrorInvalidValue;   // (not the frames the plan's format was set for: plan_set_format)
+    PlanArgs a = plan_args(p, s.src, batch, s.car, s.out, tune);
     a.plan = static_cast<const uint2 *>(p.entries); a.hdr = static_cast<const uint32_t *>(p.hdr);
-    a.deltas = d_deltas; a.tab = d_tab;
+    a.deltas = s.deltas; a.tab = s.tab;
     const bool padded = p.pitch != p.bw, scratch = padded && !p.out_pitched;
     // NV12 images (p.out_nv12) unless the step leaves a pre-gain BGR image for a gain pass (channel sums) or serves a shard (compact scratch)
-    const bool out_nv12 = p.out_nv12 && !balance && !sums && d_scratch == nullptr;
+    const bool out_nv12 = p.out_nv12 && !s.balance && !s.sums && s.scratch == nullptr;
     if (out_nv12 && (scratch || p.pitch % 4 != 0)) return hipErrorInvalidValue;   // (the caller runs the per-pixel kernel instead)
     if (padded) {
         const size_t img = (size_t)p.pitch * p.bh * 3, need = scratch ? img * (size_t)batch : 0;
@@ -770,28 +775,29 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
             if ((e = hipMalloc(&p.pad_out, need)) != hipSuccess) return e;
             p.pad_cap = need;
         }
-        if (d_car && !p.pad_car && (e = hipMalloc(&p.pad_car, img)) != hipSuccess) return e;
-        if (d_car) {
-            hipLaunchKernelGGL(k_plan_pad, dim3((unsigned)((img + 255) / 256)), dim3(256), 0, st, d_car, p.bw, p.pitch, p.bh,
+        if (s.car && !p.pad_car && (e = hipMalloc(&p.pad_car, img)) != hipSuccess) return e;
+        if (s.car) {
+            hipLaunchKernelGGL(k_plan_pad, dim3((unsigned)((img + 255) / 256)), dim3(256), 0, st, s.car, p.bw, p.pitch, p.bh,
                                static_cast<uint8_t *>(p.pad_car));
             a.car = static_cast<const uint8_t *>(p.pad_car);
         }
         if (scratch) a.out = static_cast<uint8_t *>(p.pad_out);
     }
     // the units need 4-byte aligned frame sets (dword-addressed group loads) and are not combined with the per-tap luminance kernel
-    const bool compact = d_scratch != nullptr;
-    // p.nv12: d_frames are NV12 frame sets -- the units read them through the NV12 group lists unless they read the compact scratch (BGR)
+    const bool compact = s.scratch != nullptr;
+    // NV12 frames: the units read them through the NV12 group lists unless they read the compact scratch (BGR)
     const bool nv12_units = p.nv12 && !compact;
-    const bool use_units = !balance && tune.units && p.n_un_all > 0 && (((uintptr_t)d_frames) & 3u) == 0 &&
-                           (!compact || (p.un_gsrc_compact != nullptr && (((uintptr_t)d_scratch) & 3u) == 0)) &&
-                           (!nv12_units || ((surf ? p.un_gsrc_surf : p.un_gsrc_nv12) != nullptr && !sums));
-    const bool with_sums = balance || sums;
+    const bool use_units = !s.balance && tune.units && p.n_un_all > 0 && s.src.aligned4() &&
+                           (!compact || (p.un_gsrc_compact != nullptr && (((uintptr_t)s.scratch) & 3u) == 0)) &&
+                           (!nv12_units || ((surf ? p.un_gsrc_surf : p.un_gsrc_nv12) != nullptr && !s.sums));
+    const bool with_sums = s.balance || s.sums;
     // channel-sum entries per frame: one per unit + one per base tile left to the per-tap kernel (or one per tile without units).  Every
     // entry has exactly one writer per frame (no atomics, round 5: 2.4 M atomic adds per config-4 step cost 58 us of the 600), and every writer
     // writes every frame of the call (units without a contributor write zeros): no entry depends on what the buffer held before
     a.nsum = use_units ? p.n_un_all + p.n_slow : p.ntiles;
     a.sum_base = use_units ? p.n_un_all : 0;
     if (with_sums) {
+        int psums_frames = s.psums_frames, psums_first = s.psums_first;
         if (psums_frames < batch) { psums_frames = batch; psums_first = 0; }
         const size_t per_frame = (size_t)(p.n_un_all + p.n_slow > p.ntiles ? p.n_un_all + p.n_slow : p.ntiles) * 3;   // either layout fits
         const size_t need = (size_t)psums_frames * per_frame * sizeof(uint32_t);
@@ -805,53 +811,35 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         p.psums_layout = a.nsum;   // (entries per frame of the layout in use: plan_sum_entries)
         a.psums = static_cast<uint32_t *>(p.psums) + (size_t)psums_first * a.nsum * 3;
     }
-    const dim3 block(256);
     if (use_units) {
-        if (sums) a.car = nullptr;   // the car is added behind the gains
+        if (s.sums) a.car = nullptr;   // the car is added behind the gains
         a.tile_list = static_cast<const uint32_t *>(p.list_un_all); a.nlist = p.n_un_all; a.ngroups = p.n_un_all;
-        if (compact) { a.frames = d_scratch; a.set_stride = (uint32_t)p.compact_stride; a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_compact); }
+        if (compact) { a.frames = s.scratch; a.set_stride = (uint32_t)p.compact_stride; a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_compact); }
         if (nv12_units) {
             a.set_stride = (uint32_t)(frame_bytes_of(p.fw, p.fh, true) * p.ncams);
             a.un_gsrc = static_cast<const uint32_t *>(surf ? p.un_gsrc_surf : p.un_gsrc_nv12);
         }
-        if (surf && nv12_units) {
-            if (out_nv12) with_flags([&](auto bl) { hipLaunchKernelGGL((k_units_out_surf<bl>), dim3(plan_grid(a)), block, 0, st, a); }, blend);
-            else with_flags([&](auto bl) { hipLaunchKernelGGL((k_units_surf<bl>), dim3(plan_grid(a)), block, 0, st, a); }, blend);
-        } else if (out_nv12) {
-            with_flags([&](auto bl, auto nv) { hipLaunchKernelGGL((k_units_out_nv12<bl, nv>), dim3(plan_grid(a)), block, 0, st, a); }, blend, nv12_units);
-        } else if (nv12_units) {
-            with_flags([&](auto bl) { hipLaunchKernelGGL((k_units_nv12<bl>), dim3(plan_grid(a)), block, 0, st, a); }, blend);
-        } else {
-            with_flags([&](auto bl, auto sm) { hipLaunchKernelGGL((k_plan_units<bl, sm>), dim3(plan_grid(a)), block, 0, st, a); }, blend, sums);
-        }
+        plan_launch_units(a, st, s.blend, s.sums, nv12_units, surf && nv12_units, out_nv12);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const int n_tap = use_units ? p.n_slow : p.ntiles;
     if (n_tap) {
         a.tile_list = use_units ? static_cast<const uint32_t *>(p.list_slow) : nullptr;
         a.nlist = n_tap; a.ngroups = (n_tap + 3) / 4;
-        if (sums) a.car = nullptr;
-        a.frames = d_frames; a.set_stride = 0;   // the per-tap kernel reads whole frames: RAW ones in the balance modes
-        // LUM: luminance round trip per tap (the RAW frames of balance, or the tiles no unit owns beside the compact scratch); compact
-        // without sums: camera-per-GPU shards, whose stitch rank balances the colours
-        if (surf && out_nv12)
-            with_flags([&](auto bl) { hipLaunchKernelGGL((k_stitch_plan<bl, false, false, true, true, true>), dim3(plan_grid(a)), block, 0, st, a); }, blend);
-        else if (surf)
-            with_flags([&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm, true, false, true>), dim3(plan_grid(a)), block, 0, st, a); },
-                       blend, balance || compact, balance || sums);
-        else if (out_nv12)
-            with_flags([&](auto bl, auto nv) { hipLaunchKernelGGL((k_stitch_plan<bl, false, false, nv, true>), dim3(plan_grid(a)), block, 0, st, a); },
-                       blend, p.nv12);
-        else if (p.nv12)
-            with_flags([&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm, true>), dim3(plan_grid(a)), block, 0, st, a); },
-                       blend, balance || compact, balance || sums);
-        else
-            with_flags([&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm>), dim3(plan_grid(a)), block, 0, st, a); },
-                       blend, balance || compact, balance || sums);
+        if (s.sums) a.car = nullptr;
+        a.frames = s.src.packed; a.set_stride = 0;   // the per-tap kernel reads whole frames: RAW ones in the balance modes
+        with_formats(p.nv12, surf, out_nv12, [&](auto in, auto on) {
+            constexpr bool NV12 = decltype(in)::nv12, SURF = decltype(in)::surf, OUT_NV12 = decltype(on)::value;
+            auto launch = [&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm, NV12, OUT_NV12, SURF>), dim3(plan_grid(a)), dim3(256), 0, st, a); };
+            // LUM: luminance round trip per tap (the RAW frames of balance, or the tiles no unit owns beside the compact scratch); compact
+            // without sums: camera-per-GPU shards, whose stitch rank balances the colours.  Neither exists with NV12 images (out_nv12 above)
+            if constexpr (OUT_NV12) with_flags([&](auto bl) { launch(bl, std::false_type{}, std::false_type{}); }, s.blend);
+            else with_flags(launch, s.blend, s.balance || compact, s.balance || s.sums);
+        });
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if (with_sums && d_chsums != nullptr) {   // (nullptr: the caller's gain pass adds the partial sums itself: plan_sum_entries)
-        hipLaunchKernelGGL(k_reduce_psums, dim3(batch), dim3(256), 0, st, a.psums, a.nsum, d_chsums);
+    if (with_sums && s.chsums != nullptr) {   // (nullptr: the caller's gain pass adds the partial sums itself: plan_sum_entries)
+        hipLaunchKernelGGL(k_reduce_psums, dim3(batch), dim3(256), 0, st, a.psums, a.nsum, s.chsums);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     if (scratch) {
@@ -859,7 +847,7 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const uint8_t
         for (size_t r0 = 0; r0 < rows; r0 += (size_t)1 << 20) {   // <= 2^20 rows per launch keeps the grid below 2^31 blocks
             const size_t nr = rows - r0 < ((size_t)1 << 20) ? rows - r0 : ((size_t)1 << 20);
             hipLaunchKernelGGL(k_plan_unpad, dim3((unsigned)((nr * p.bw * 3 + 255) / 256)), dim3(256), 0, st,
-                               static_cast<const uint8_t *>(p.pad_out) + r0 * p.pitch * 3, p.bw, p.pitch, nr, d_out + r0 * p.bw * 3);
+                               static_cast<const uint8_t *>(p.pad_out) + r0 * p.pitch * 3, p.bw, p.pitch, nr, s.out + r0 * p.bw * 3);
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
@@ -871,36 +859,29 @@ static inline hipError_t plan_unit_wide_launch(const Plan &p, hipStream_t st, co
                                                uint8_t *d_out, const PlanTuning &tune)
 {
     if (p.n_un_all == 0) return hipSuccess;
-    PlanArgs a = plan_args(p, d_frames, batch, d_car, d_out, tune);
+    PlanArgs a = plan_args(p, FrameSource{d_frames}, batch, d_car, d_out, tune);
     a.tile_list = static_cast<const uint32_t *>(p.list_un_all); a.nlist = p.n_un_all; a.ngroups = p.n_un_all;
     with_flags([&](auto bl) { hipLaunchKernelGGL((k_plan_unit_wide<bl>), dim3(plan_grid(a)), dim3(kUnitThreads), 0, st, a); }, blend);
     return hipGetLastError();
 }
 
 // luminance-shift the sampled texel groups of every raw frame of the batch into the compact scratch (p.compact_stride bytes per frame set)
-static inline hipError_t plan_lum_band(const Plan &p, hipStream_t st, const uint8_t *d_frames, uint8_t *d_scratch, int batch,
-                                       const int *d_deltas, const HsvTables *d_tab, const Nv12Surface *d_surf = nullptr)
+static inline hipError_t plan_lum_band(const Plan &p, hipStream_t st, const FrameSource &src, uint8_t *d_scratch, int batch,
+                                       const int *d_deltas, const HsvTables *d_tab)
 {
     if (p.n_groups == 0 || p.compact_stride == 0) return hipSuccess;
-    if (p.nv12 && !p.groups_nv12) return hipErrorInvalidValue;
-    if (d_surf) {   // NV12 surfaces: the sampled groups relative to the camera's own planes (plan_src_pitch_impl)
-        if (!p.nv12 || !p.groups_surf) return hipErrorInvalidValue;
-        const unsigned bpf = (unsigned)(p.n_groups + 256 * kLumTrips - 1) / (256 * kLumTrips);
-        for_each_chunk(batch, [&](int b0, int nb) {
-            hipLaunchKernelGGL((k_lum_groups<true, true>), dim3(xcd_frame_grid(bpf, (unsigned)nb)), dim3(256), 0, st, nullptr,
-                               d_scratch + (size_t)b0 * p.compact_stride, (size_t)0, p.compact_stride, 0u, static_cast<const uint32_t *>(p.groups_surf),
-                               p.n_groups, d_deltas + (size_t)b0 * 4, d_tab, bpf, (uint32_t)nb, d_surf + (size_t)b0 * 4);
-        });
-        return hipGetLastError();
-    }
-    const size_t frame_bytes = frame_bytes_of(p.fw, p.fh, p.nv12), set_bytes = frame_bytes * p.ncams;
+    // the sampled groups as this kind of source addresses them (surfaces: relative to the camera's own planes, plan_src_pitch_impl)
+    const void *groups = src.is_surf() ? p.groups_surf : (src.nv12 ? p.groups_nv12 : p.groups);
+    if (!groups || src.nv12 != p.nv12 || src.cams != p.ncams || (src.is_surf() && src.pitch != p.src_pitch)) return hipErrorInvalidValue;
+    const size_t frame_bytes = frame_bytes_of(p.fw, p.fh, src.nv12);
     const unsigned bpf = (unsigned)(p.n_groups + 256 * kLumTrips - 1) / (256 * kLumTrips);
     for_each_chunk(batch, [&](int b0, int nb) {
-        with_flags([&](auto nv) {
-            hipLaunchKernelGGL((k_lum_groups<nv>), dim3(xcd_frame_grid(bpf, (unsigned)nb)), dim3(256), 0, st, d_frames + (size_t)b0 * set_bytes,
-                               d_scratch + (size_t)b0 * p.compact_stride, set_bytes, p.compact_stride, (uint32_t)frame_bytes,
-                               static_cast<const uint32_t *>(nv ? p.groups_nv12 : p.groups), p.n_groups, d_deltas + (size_t)b0 * 4, d_tab, bpf, (uint32_t)nb);
-        }, p.nv12);
+        const FrameSource fr = src.from(b0, p.fw, p.fh);
+        with_input(src.nv12, src.is_surf(), [&](auto in) {
+            hipLaunchKernelGGL((k_lum_groups<decltype(in)::nv12, decltype(in)::surf>), dim3(xcd_frame_grid(bpf, (unsigned)nb)), dim3(256), 0, st, fr.packed,
+                               d_scratch + (size_t)b0 * p.compact_stride, src.set_bytes(p.fw, p.fh), p.compact_stride, (uint32_t)frame_bytes,
+                               static_cast<const uint32_t *>(groups), p.n_groups, d_deltas + (size_t)b0 * 4, d_tab, bpf, (uint32_t)nb, fr.surf);
+        });
     });
     return hipGetLastError();
 }

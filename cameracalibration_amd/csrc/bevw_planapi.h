@@ -1,7 +1,8 @@
 // bevw_planapi.h -- what the rest of the library sees of the tile plan: the Plan a handle owns, the tables it is compiled from and the
-// entry points.  Declarations only: the plan kernels (bevw_plan.h, bevw_unit.h) are compiled in bevwarp_plan.hip alone, which defines
-// everything declared here.  Every plan_* function that returns an int returns a BEVW_* status and leaves its message in bevw_last_error().
+// entry points with their arguments (FrameSource, PlanStep).  No kernels: the plan kernels (bevw_plan.h, bevw_unit.h) are compiled in
+// bevwarp_plan.hip alone, which defines every function declared here.  Every plan_* function that returns an int returns a BEVW_* status and leaves its message in bevw_last_error().
 #pragma once
+#include "bevw_device.h"   // Nv12Surface, HsvTables, frame_bytes_of
 #include "bevw_host.h"
 
 namespace bevw {
@@ -13,8 +14,26 @@ struct StitchTables {
     const uint8_t *mask[4];
 };
 
-struct HsvTables;   // bevw_device.h
-struct Nv12Surface; // bevw_device.h: the two plane pointers of one decoded NV12 frame (bevw_nv12_surface)
+// Where the camera frames of a step are.  Packed: `packed` points at frame sets of `cams` dense frames, BGR or NV12.  Surfaces: `surf` is a
+// device table surf[frame set][cams] of NV12 surfaces with rows of `pitch` bytes, which every kernel reads in place; `packed` is then nullptr
+// and is never read.
+struct FrameSource {
+    const uint8_t *packed = nullptr;
+    const Nv12Surface *surf = nullptr;
+    int pitch = 0;       // bytes between the rows of a surface
+    bool nv12 = false;
+    int cams = 4;        // frames per set: 4 for a BevGenerator, 1 for a remapper or a list of single frames
+    bool is_surf() const { return surf != nullptr; }
+    size_t set_bytes(int fw, int fh) const { return frame_bytes_of(fw, fh, nv12) * (size_t)cams; }
+    bool aligned4() const { return (((uintptr_t)packed) & 3u) == 0; }   // dword loads (a surface's planes were checked when its table was staged)
+    FrameSource from(int b0, int fw, int fh) const   // the source of frame set b0 onward
+    {
+        FrameSource s = *this;
+        if (surf) s.surf += (size_t)b0 * cams;
+        else s.packed += (size_t)b0 * set_bytes(fw, fh);
+        return s;
+    }
+};
 
 // a compiled tile plan: its device buffers and the geometry they were built for (plan_build / plan_build_wide)
 struct Plan {
@@ -53,14 +72,14 @@ struct Plan {
     int n_unit_tiles = 0;                    // base tiles the units own
     size_t un_lines = 0, un_sectors = 0;     // request arithmetic of the partition (per frame)
     int un_skew = 0;
-    // the per-frame kernels read NV12 frame sets (bevw_set_input_format): set by the plan's owner after plan_build, which resets it
+    // The formats of the plan's steps, written by plan_set_format alone (plan_build resets them).  nv12: they read NV12 frame sets (bevw_set_input_format).
     bool nv12 = false;
-    // the per-frame kernels write NV12 images of `pitch` bytes per row (bevw_set_output_format; needs pitch % 4 == 0 and no padded scratch):
-    // set by the owner after plan_build.  Steps with channel sums (balance) still write the BGR pre-gain image: their gain pass converts.
+    // out_nv12: they write NV12 images of `pitch` bytes per row (bevw_set_output_format; needs pitch % 4 == 0 and no padded scratch).  Steps
+    // with channel sums (balance) still write the BGR pre-gain image: their gain pass converts.
     bool out_nv12 = false;
-    // NV12 surfaces (bevw_set_input_pitch / bevw_run_surfaces_device): rows of src_pitch bytes, and the group lists translated for them
-    // (unit_gsrc_surf: offsets inside the camera's own planes, camera in the low bits).  Set by the owner through plan_set_src_pitch after
-    // plan_build, which resets them; the host copies of the lists the translation starts from stay with the plan.
+    // src_pitch: NV12 surfaces (bevw_set_input_pitch / bevw_run_surfaces_device) have rows of src_pitch bytes, and the group lists are
+    // translated for them (unit_gsrc_surf: offsets inside the camera's own planes, camera in the low bits); the host copies of the lists
+    // the translation starts from stay with the plan.
     int src_pitch = 0;
     void *un_gsrc_surf = nullptr;            // the units' group lists, two dwords per slot
     void *groups_surf = nullptr;             // the sampled groups of the balance schedule (k_lum_groups<true, true>), two dwords per group
@@ -71,17 +90,34 @@ struct Plan {
 // are pitched (0: dense); blend: the handle applies blend weights (its units carry no two-quad two-contributor class)
 int plan_build(Plan &p, hipStream_t st, const StitchTables &T, int fw, int fh, int bw, int bh, int ncams, int out_pitch, bool blend);
 
-// one step: see plan_stitch_impl (bevw_plan.h)
-int plan_stitch(Plan &p, hipStream_t st, const uint8_t *d_frames, int batch, bool blend, bool balance, const int *d_deltas, const HsvTables *d_tab,
-                const uint8_t *d_car, unsigned long long *d_chsums, uint8_t *d_out, bool sums = false, int psums_frames = 0, int psums_first = 0,
-                const uint8_t *d_scratch = nullptr, const Nv12Surface *d_surf = nullptr);
+// One step of the tile plan (plan_stitch).  A field left at its default is not used.
+struct PlanStep {
+    FrameSource src;
+    int batch = 0; bool blend = false;
+    // luminance round trip per tap on RAW frames (the per-tap kernel over every tile) + per-tile channel sums
+    bool balance = false;
+    // per-unit / per-tile channel sums, the car left to the gain pass (with `scratch`; or: the frames are luminance-shifted already)
+    bool sums = false;
+    const int *deltas = nullptr; const HsvTables *tab = nullptr;   // balance / scratch: luminance deltas[frame set][4], the HSV divisor tables
+    const uint8_t *car = nullptr; uint8_t *out = nullptr;
+    // balance and sums end with k_reduce_psums into chsums[frame set][3]; nullptr: the caller's gain pass adds the partial sums itself (plan_sum_entries)
+    unsigned long long *chsums = nullptr;
+    // the psums buffer is sized for psums_frames frame sets and this step's start at slot psums_first of it (two half-batches of one balance
+    // step run concurrently on two streams: balance_plan_run); 0: this step's batch alone
+    int psums_frames = 0, psums_first = 0;
+    // the compact scratch plan_lum_groups filled from the frames (balance schedule 1): the units read IT (p.compact_stride bytes per frame
+    // set, group lists p.un_gsrc_compact), the per-tap kernel serves what no unit owns from the RAW frames with the luminance round trip per
+    // tap (deltas, tab); everything on the per-tap kernel when the units cannot run
+    const uint8_t *scratch = nullptr;
+};
+int plan_stitch(Plan &p, hipStream_t st, const PlanStep &step);
 
 // balance: luminance round trip of the sampled texel groups of the raw frames into the compact scratch (p.compact_stride bytes per frame set)
-int plan_lum_groups(const Plan &p, hipStream_t st, const uint8_t *d_frames, uint8_t *d_scratch, int batch, const int *d_deltas, const HsvTables *d_tab,
-                    const Nv12Surface *d_surf = nullptr);
+int plan_lum_groups(const Plan &p, hipStream_t st, const FrameSource &src, uint8_t *d_scratch, int batch, const int *d_deltas, const HsvTables *d_tab);
 
-// NV12 surfaces: translate the plan's group lists for surfaces with rows of `pitch` bytes (0: drop them).  After plan_build, with no step queued.
-int plan_set_src_pitch(Plan &p, int pitch);
+// The pixel formats of the plan's steps, and for NV12 surfaces the row pitch the group lists are translated for (0: none).  After plan_build,
+// with no step queued.
+int plan_set_format(Plan &p, bool nv12, bool out_nv12, int src_pitch);
 
 // rows of bw pixels -> rows of pitch pixels (the car sprite of a pitched handle)
 int plan_pad_image(hipStream_t st, const uint8_t *d_src, int bw, int pitch, int bh, uint8_t *d_dst);

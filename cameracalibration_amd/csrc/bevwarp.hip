@@ -339,11 +339,15 @@ struct bevw_remapper {
     bool plan_ready = false;
     int ties_even = 0;    // BEVW_COMPAT_REMAP at creation: half-to-even ties -> the per-pixel kernel (the plan's arithmetic rounds half up)
     int input_format = BEVW_INPUT_BGR;   // bevw_remapper_set_input_format
+    bool nv12() const { return input_format == BEVW_INPUT_NV12; }
     int output_format = BEVW_OUTPUT_BGR; // bevw_remapper_set_output_format
     bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
     int in_pitch_request = 0;            // bevw_remapper_set_input_pitch (0: the source width)
     int in_pitch() const { return in_pitch_request ? in_pitch_request : sw; }
     SurfStage surf_stage;                // bevw_remap_surfaces_device
+    // the sources of a step: packed images behind d_src, or (d_surf) a device table of NV12 surfaces with rows of in_pitch() bytes
+    FrameSource source(const uint8_t *d_src, const Nv12Surface *d_surf) const { return {d_surf ? nullptr : d_src, d_surf, d_surf ? in_pitch() : 0, nv12(), 1}; }
+    int apply_format() { return plan_set_format(plan, nv12(), out_nv12(), nv12() ? in_pitch() : 0); }
 };
 
 // cv2.remap as a 1-camera stitch: every destination pixel has exactly one contributor with mask 255.
@@ -385,29 +389,16 @@ static int remapper_alloc(int device, int sw, int sh, int dw, int dh, bevw_remap
     return BEVW_OK;
 }
 
-// nv12: the sources are NV12 frames (bevw_remapper_set_input_format); out_nv12: the destinations are dense NV12 images
-// (bevw_remapper_set_output_format)
-// d_surf: the sources are NV12 surfaces with rows of src_pitch bytes (bevw_remap_surfaces_device), d_src is not read
-static int remap_launch(hipStream_t st, const uint8_t *d_src, int sw, int sh, const int16_t *m1, const uint16_t *m2,
-                        int dw, int dh, int batch, uint8_t *d_dst, int ties_even = 0, bool nv12 = false, bool out_nv12 = false,
-                        const Nv12Surface *d_surf = nullptr, int src_pitch = 0)
+// k_remap_lut over `batch` images of `src` (one frame per set); out_nv12: the destinations are dense NV12 images (bevw_remapper_set_output_format)
+static int remap_launch(hipStream_t st, const FrameSource &src, int sw, int sh, const int16_t *m1, const uint16_t *m2,
+                        int dw, int dh, int batch, uint8_t *d_dst, int ties_even, bool out_nv12)
 {
     for_each_chunk(batch, [&](int b0, int nb) {
-        if (d_surf)
-            with_flags([&](auto on) {
-                hipLaunchKernelGGL((k_remap_lut<true, on, true>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, nullptr, sw, sh, m1, m2, dw, dh,
-                                   d_dst + (size_t)b0 * image_bytes_of(dw, dh, on), ties_even, d_surf + b0, src_pitch);
-            }, out_nv12);
-        else if (out_nv12)
-            with_flags([&](auto nv) {
-                hipLaunchKernelGGL((k_remap_lut<nv, true>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, d_src + (size_t)b0 * frame_bytes_of(sw, sh, nv),
-                                   sw, sh, m1, m2, dw, dh, d_dst + (size_t)b0 * image_bytes_of(dw, dh, true), ties_even);
-            }, nv12);
-        else
-            with_flags([&](auto nv) {
-                hipLaunchKernelGGL((k_remap_lut<nv>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, d_src + (size_t)b0 * frame_bytes_of(sw, sh, nv),
-                                   sw, sh, m1, m2, dw, dh, d_dst + (size_t)b0 * dw * dh * 3, ties_even);
-            }, nv12);
+        const FrameSource fr = src.from(b0, sw, sh);
+        with_formats(src.nv12, src.is_surf(), out_nv12, [&](auto in, auto on) {
+            hipLaunchKernelGGL((k_remap_lut<decltype(in)::nv12, on, decltype(in)::surf>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, fr.packed, sw, sh,
+                               m1, m2, dw, dh, d_dst + (size_t)b0 * image_bytes_of(dw, dh, on), ties_even, fr.surf, fr.pitch);
+        });
     });
     return launch_check("k_remap_lut");
 }
@@ -593,11 +584,11 @@ int bevw_remapper_get_maps(bevw_remapper *r, int16_t *map1, uint16_t *map2)
 int bevw_remapper_set_input_pitch(bevw_remapper *r, int pitch_bytes)
 {
     if (!r) return fail(BEVW_E_INVALID, "null remapper");
-    BEVW_TRY(check_input_pitch(pitch_bytes, r->sw, r->sh, r->input_format == BEVW_INPUT_NV12));
+    BEVW_TRY(check_input_pitch(pitch_bytes, r->sw, r->sh, r->nv12()));
     BEVW_TRY(use_device(r->device));
     HIP_TRY(hipStreamSynchronize(r->stream));   // (the group lists are read at launch: no step with the old pitch is still queued)
     r->in_pitch_request = pitch_bytes;
-    if (r->plan_ready) BEVW_TRY(plan_set_src_pitch(r->plan, r->input_format == BEVW_INPUT_NV12 ? r->in_pitch() : 0));
+    if (r->plan_ready) BEVW_TRY(r->apply_format());
     return BEVW_OK;
 }
 
@@ -605,19 +596,23 @@ int bevw_remapper_set_input_pitch(bevw_remapper *r, int pitch_bytes)
 static int remap_need_surfaces(bevw_remapper *r, const void *table, int batch, void *d_dst)
 {
     if (!r || !table || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
-    if (r->input_format != BEVW_INPUT_NV12) return fail(BEVW_E_INVALID, "surfaces are NV12: the remapper's input format is BGR (bevw_remapper_set_input_format)");
+    if (!r->nv12()) return fail(BEVW_E_INVALID, "surfaces are NV12: the remapper's input format is BGR (bevw_remapper_set_input_format)");
     if (r->in_pitch() % 4 != 0)
         return fail(BEVW_E_INVALID, "the source width %d is not a multiple of 4: surfaces need an input pitch that is (bevw_remapper_set_input_pitch)", r->sw);
     return BEVW_OK;
 }
 
-// one remap step over a DEVICE table of `batch` surfaces
-static int remap_surfaces(bevw_remapper *r, const Nv12Surface *d_surf, int batch, void *d_dst)
+// one remap step: the plan, or the per-pixel kernel (NV12 images on the plan need dword-aligned quads in the caller's rows, dw % 4 == 0)
+static int remap_step(bevw_remapper *r, const FrameSource &src, int batch, void *d_dst)
 {
-    if (r->plan_ready && r->plan.src_pitch == r->in_pitch() && (((uintptr_t)d_dst) & 3u) == 0 && (!r->out_nv12() || r->dw % 4 == 0))
-        return plan_stitch(r->plan, r->stream, nullptr, batch, false, false, nullptr, nullptr, nullptr, nullptr, (uint8_t *)d_dst, false, 0, 0, nullptr, d_surf);
-    return remap_launch(r->stream, nullptr, r->sw, r->sh, r->map1.as<int16_t>(), r->map2.as<uint16_t>(), r->dw, r->dh, batch, (uint8_t *)d_dst,
-                        r->ties_even, true, r->out_nv12(), d_surf, r->in_pitch());
+    if (r->plan_ready && (!src.is_surf() || r->plan.src_pitch == src.pitch) && src.aligned4() && (((uintptr_t)d_dst) & 3u) == 0 &&
+        (!r->out_nv12() || r->dw % 4 == 0)) {
+        PlanStep step;
+        step.src = src; step.batch = batch; step.out = (uint8_t *)d_dst;
+        return plan_stitch(r->plan, r->stream, step);
+    }
+    return remap_launch(r->stream, src, r->sw, r->sh, r->map1.as<int16_t>(), r->map2.as<uint16_t>(), r->dw, r->dh, batch, (uint8_t *)d_dst,
+                        r->ties_even, r->out_nv12());
 }
 
 int bevw_remap_surface_table_device(bevw_remapper *r, const void *d_surfaces, int batch, void *d_dst)
@@ -626,7 +621,7 @@ int bevw_remap_surface_table_device(bevw_remapper *r, const void *d_surfaces, in
     if (((uintptr_t)d_surfaces) & 7u) return fail(BEVW_E_INVALID, "the surface table is not 8-byte aligned");
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
-    return remap_surfaces(r, static_cast<const Nv12Surface *>(d_surfaces), batch, d_dst);
+    return remap_step(r, r->source(nullptr, static_cast<const Nv12Surface *>(d_surfaces)), batch, d_dst);
 }
 
 int bevw_remap_surfaces_device(bevw_remapper *r, const bevw_nv12_surface *surfaces, int batch, void *d_dst)
@@ -637,8 +632,8 @@ int bevw_remap_surfaces_device(bevw_remapper *r, const bevw_nv12_surface *surfac
     const Nv12Surface *d_surf = nullptr;
     int slot = 0;
     BEVW_TRY(r->surf_stage.stage(r->stream, surfaces, (size_t)batch, d_surf, slot));
-    const int s = remap_surfaces(r, d_surf, batch, d_dst);
-    BEVW_TRY(r->surf_stage.done(r->stream, slot));
+    const int s = remap_step(r, r->source(nullptr, d_surf), batch, d_dst);
+    BEVW_TRY(r->surf_stage.done(r->stream, slot));   // (whether or not the step failed: the slot's table stays until then)
     return s;
 }
 
@@ -650,12 +645,7 @@ int bevw_remap_device(bevw_remapper *r, const void *d_src, int batch, void *d_ds
                     r->in_pitch(), r->sw);
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
-    // (NV12 images on the plan need dword-aligned quads in the caller's rows: a width that is not a multiple of 4 takes the per-pixel kernel)
-    if (r->plan_ready && ((((uintptr_t)d_src) | ((uintptr_t)d_dst)) & 3u) == 0 && (!r->out_nv12() || r->dw % 4 == 0))
-        return plan_stitch(r->plan, r->stream, (const uint8_t *)d_src, batch, false, false, nullptr, nullptr, nullptr, nullptr,
-                           (uint8_t *)d_dst);
-    return remap_launch(r->stream, (const uint8_t *)d_src, r->sw, r->sh, r->map1.as<int16_t>(), r->map2.as<uint16_t>(),
-                        r->dw, r->dh, batch, (uint8_t *)d_dst, r->ties_even, r->input_format == BEVW_INPUT_NV12, r->out_nv12());
+    return remap_step(r, r->source((const uint8_t *)d_src, nullptr), batch, d_dst);
 }
 
 int bevw_remapper_set_output_format(bevw_remapper *r, int format)
@@ -667,7 +657,7 @@ int bevw_remapper_set_output_format(bevw_remapper *r, int format)
     BEVW_TRY(use_device(r->device));
     HIP_TRY(hipStreamSynchronize(r->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
     r->output_format = format;
-    r->plan.out_nv12 = r->out_nv12();
+    if (r->plan_ready) BEVW_TRY(r->apply_format());
     return BEVW_OK;
 }
 
@@ -680,9 +670,8 @@ int bevw_remapper_set_input_format(bevw_remapper *r, int format)
     BEVW_TRY(use_device(r->device));
     HIP_TRY(hipStreamSynchronize(r->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
     r->input_format = format;
-    r->plan.nv12 = format == BEVW_INPUT_NV12;
-    if (format != BEVW_INPUT_NV12) r->in_pitch_request = 0;   // (BGR sources are dense)
-    if (r->plan_ready) BEVW_TRY(plan_set_src_pitch(r->plan, format == BEVW_INPUT_NV12 ? r->in_pitch() : 0));
+    if (!r->nv12()) r->in_pitch_request = 0;   // (BGR sources are dense)
+    if (r->plan_ready) BEVW_TRY(r->apply_format());
     return BEVW_OK;
 }
 
@@ -694,7 +683,7 @@ int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst)
                     r->in_pitch(), r->sw);
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
-    const size_t nin = (size_t)batch * frame_bytes_of(r->sw, r->sh, r->input_format == BEVW_INPUT_NV12), nout = (size_t)batch * image_bytes_of(r->dw, r->dh, r->out_nv12());
+    const size_t nin = (size_t)batch * frame_bytes_of(r->sw, r->sh, r->nv12()), nout = (size_t)batch * image_bytes_of(r->dw, r->dh, r->out_nv12());
     BEVW_TRY(r->in.reserve(nin));
     BEVW_TRY(r->out.reserve(nout));
     HIP_TRY(hipMemcpyAsync(r->in.p, src, nin, hipMemcpyHostToDevice, r->stream));
@@ -865,6 +854,10 @@ struct bevw_handle {
     int pitch_request = BEVW_PITCH_DENSE;   // bevw_set_output_pitch
     int pitch_px = 0;                 // pixels per row of the device-side BEV images (== bev_width unless a pitch was requested)
     size_t out_image_bytes() const { return image_bytes_of(pitch_px, cfg.bev_height, out_nv12()); }   // one device-side BEV image
+    // the frames of a step: packed frame sets behind d_frames, or (d_surf) a device table surf[frame set][4] of NV12 surfaces, read in place
+    FrameSource source(const uint8_t *d_frames, const Nv12Surface *d_surf) const { return {d_surf ? nullptr : d_frames, d_surf, d_surf ? in_pitch() : 0, nv12(), shard_n ? shard_n : 4}; }
+    // the plan follows the handle's formats (bevw_build behind plan_build; the setters of a built handle, with its streams idle)
+    int apply_format() { return plan_set_format(plan, nv12(), out_nv12(), nv12() ? in_pitch() : 0); }
     DevBuf car_pitched;               // the car sprite with rows of pitch_px pixels (gain pass of a pitched handle)
     AnalyticRig arig;                 // filled by bevw_build
     Plan aplan;                       // analytic modes: the WIDE unit schedule compiled from the projection (analytic_units_build)
@@ -924,48 +917,27 @@ static int ensure_stats(bevw_handle *h, int batch)
     return BEVW_OK;
 }
 
-static int stitch_per_pixel(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out, const Nv12Surface *d_surf = nullptr)
+static int stitch_per_pixel(bevw_handle *h, const FrameSource &src, int batch, const uint8_t *d_car, uint8_t *d_out)
 {
     const bevw_config &c = h->cfg;
     const StitchTables T = stitch_tables(h);
     const int *deltas = h->deltas.as<int>();
     const HsvTables *tab = h->hsv.as<HsvTables>();
     unsigned long long *chs = h->chsums.as<unsigned long long>();
+    const bool out_nv12 = h->out_nv12() && !c.balance;   // NV12 images (the balance modes store the BGR pre-gain image: the gain pass converts)
     for_each_chunk(batch, [&](int b0, int nb) {
         const dim3 grid((c.bev_width + 255) / 256, c.bev_height, nb), block(256);
-        const uint8_t *fr = d_surf ? nullptr : d_frames + (size_t)b0 * h->set_bytes();
-        if (d_surf) {   // NV12 surfaces: surf[frame set][camera], rows of in_pitch() bytes
-            const Nv12Surface *sf = d_surf + (size_t)b0 * 4;
-            if (h->out_nv12() && !c.balance) {
-                uint8_t *o = d_out + (size_t)b0 * image_bytes_of(c.bev_width, c.bev_height, true);
-                with_flags([&](auto bl) {
-                    hipLaunchKernelGGL((k_stitch_pp<bl, false, true, true, true>), grid, block, 0, h->stream, nullptr, c.frame_width, c.frame_height, T,
-                                       c.bev_width, c.bev_height, nullptr, tab, d_car, nullptr, o, h->compat[BEVW_COMPAT_REMAP], sf, h->in_pitch());
-                }, c.blend != 0);
-                return;
-            }
-            uint8_t *o = d_out + (size_t)b0 * c.bev_width * c.bev_height * 3;
-            with_flags([&](auto bl, auto ba) {
-                hipLaunchKernelGGL((k_stitch_pp<bl, ba, true, false, true>), grid, block, 0, h->stream, nullptr, c.frame_width, c.frame_height, T,
-                                   c.bev_width, c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car, chs ? chs + b0 * 3 : nullptr, o,
-                                   h->compat[BEVW_COMPAT_REMAP], sf, h->in_pitch());
-            }, c.blend != 0, c.balance != 0);
-            return;
-        }
-        if (h->out_nv12() && !c.balance) {   // NV12 images (the balance modes store the BGR pre-gain image: the gain pass converts)
-            uint8_t *o = d_out + (size_t)b0 * image_bytes_of(c.bev_width, c.bev_height, true);
-            with_flags([&](auto bl, auto nv) {
-                hipLaunchKernelGGL((k_stitch_pp<bl, false, nv, true>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height, T, c.bev_width,
-                                   c.bev_height, nullptr, tab, d_car, nullptr, o, h->compat[BEVW_COMPAT_REMAP]);
-            }, c.blend != 0, h->nv12());
-            return;
-        }
-        uint8_t *o = d_out + (size_t)b0 * c.bev_width * c.bev_height * 3;
-        with_flags([&](auto bl, auto ba, auto nv) {
-            hipLaunchKernelGGL((k_stitch_pp<bl, ba, nv>), grid, block, 0, h->stream, fr, c.frame_width, c.frame_height, T, c.bev_width,
-                               c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car, chs ? chs + b0 * 3 : nullptr, o,
-                               h->compat[BEVW_COMPAT_REMAP]);
-        }, c.blend != 0, c.balance != 0, h->nv12());
+        const FrameSource fr = src.from(b0, c.frame_width, c.frame_height);
+        uint8_t *o = d_out + (size_t)b0 * image_bytes_of(c.bev_width, c.bev_height, out_nv12);
+        with_formats(src.nv12, src.is_surf(), out_nv12, [&](auto in, auto on) {
+            auto launch = [&](auto bl, auto ba) {
+                hipLaunchKernelGGL((k_stitch_pp<bl, ba, decltype(in)::nv12, on, decltype(in)::surf>), grid, block, 0, h->stream, fr.packed, c.frame_width,
+                                   c.frame_height, T, c.bev_width, c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car,
+                                   chs ? chs + b0 * 3 : nullptr, o, h->compat[BEVW_COMPAT_REMAP], fr.surf, fr.pitch);
+            };
+            if constexpr (on) with_flags([&](auto bl) { launch(bl, std::false_type{}); }, c.blend != 0);
+            else with_flags(launch, c.blend != 0, c.balance != 0);
+        });
     });
     return launch_check("k_stitch_pp");
 }
@@ -1055,27 +1027,24 @@ static int stitch_analytic(bevw_handle *h, const uint8_t *d_frames, int batch, c
     return launch_check("k_stitch_analytic");
 }
 
-// k_vsum over `nframes` frames on `st`; returns its blocks per frame.  part_stride > 0: every block stores its partial sum, part_stride entries
-// per frame; 0: the blocks of a frame add into its one entry (zeroed by the caller).  nv12_width > 0: NV12 frames of that width
-// d_surf: the frames are NV12 surfaces (one per frame) with rows of src_pitch bytes; d_frames is not read
-static int vsum_launch(hipStream_t st, const uint8_t *d_frames, int nframes, size_t frame_bytes, unsigned long long *d_vsums, int part_stride,
-                       int nv12_width = 0, const Nv12Surface *d_surf = nullptr, int src_pitch = 0)
+// k_vsum over the first `nframes` frames of `src` (fw x fh, taken one by one whatever its sets are) on `st`; returns its blocks per frame.
+// part_stride > 0: every block stores its partial sum, part_stride entries per frame; 0: the blocks of a frame add into its one entry
+// (zeroed by the caller).
+static int vsum_launch(hipStream_t st, FrameSource src, int nframes, int fw, int fh, unsigned long long *d_vsums, int part_stride)
 {
-    const int vec_ok = (frame_bytes % 4 == 0 && ((uintptr_t)d_frames & 3u) == 0) ? 1 : 0;   // k_vsum's 12-byte loads
+    src.cams = 1;
+    const size_t frame_bytes = src.set_bytes(fw, fh);
+    const int vec_ok = (!src.is_surf() && frame_bytes % 4 == 0 && src.aligned4()) ? 1 : 0;   // k_vsum's 12-byte loads
     int bpf = 2048 / (nframes > 0 ? nframes : 1);
     if (bpf < 8) bpf = 8;
     if (bpf > 256) bpf = 256;
     const size_t per_frame = part_stride > 0 ? (size_t)part_stride : 1;
     for_each_chunk(nframes, [&](int f0, int nf) {
-        if (d_surf) {
-            hipLaunchKernelGGL((k_vsum<true, true>), dim3(bpf, nf), dim3(256), 0, st, nullptr, frame_bytes, 0, d_vsums + (size_t)f0 * per_frame, part_stride,
-                               nv12_width, d_surf + f0, src_pitch);
-            return;
-        }
-        with_flags([&](auto nv) {
-            hipLaunchKernelGGL((k_vsum<nv>), dim3(bpf, nf), dim3(256), 0, st, d_frames + (size_t)f0 * frame_bytes, frame_bytes, vec_ok,
-                               d_vsums + (size_t)f0 * per_frame, part_stride, nv12_width);
-        }, nv12_width > 0);
+        const FrameSource fr = src.from(f0, fw, fh);
+        with_input(src.nv12, src.is_surf(), [&](auto in) {
+            hipLaunchKernelGGL((k_vsum<decltype(in)::nv12, decltype(in)::surf>), dim3(bpf, nf), dim3(256), 0, st, fr.packed, frame_bytes, vec_ok,
+                               d_vsums + (size_t)f0 * per_frame, part_stride, src.nv12 ? fw : 0, fr.surf, fr.pitch);
+        });
     });
     return bpf;
 }
@@ -1083,10 +1052,9 @@ static int vsum_launch(hipStream_t st, const uint8_t *d_frames, int nframes, siz
 // luminance statistics of a batch of 4-camera sets -> deltas[batch][4].  d_vsums: kVsumParts entries per frame (ensure_stats): every block
 // of k_vsum stores its partial sum, k_lum_delta adds them -- no atomics and no zeroing pass per step (round 5: the 4 KB hipMemsetAsync in
 // front of every slice's k_vsum cost 20 us of stream time, twice per config-4 step).
-static int luminance_stats(hipStream_t st, const uint8_t *d_frames, int nsets, int fw, int fh, unsigned long long *d_vsums, int *d_deltas,
-                           bool nv12 = false, const Nv12Surface *d_surf = nullptr, int src_pitch = 0)
+static int luminance_stats(hipStream_t st, const FrameSource &src, int nsets, int fw, int fh, unsigned long long *d_vsums, int *d_deltas)
 {
-    const int bpf = vsum_launch(st, d_frames, nsets * 4, frame_bytes_of(fw, fh, nv12), d_vsums, kVsumParts, nv12 ? fw : 0, d_surf, src_pitch);
+    const int bpf = vsum_launch(st, src, nsets * 4, fw, fh, d_vsums, kVsumParts);
     hipLaunchKernelGGL(k_lum_delta, dim3((nsets + 63) / 64), dim3(64), 0, st, d_vsums, (double)fw * (double)fh, nsets,
                        d_deltas, bpf, kVsumParts);
     return launch_check("k_vsum/k_lum_delta");
@@ -1155,11 +1123,10 @@ static int gain_car(bevw_handle *h, const uint8_t *d_car, const uint8_t *&car)
 // decode batch, bevwarp_jpeg.hip).  BEVW_BAL_SKEW=1 starts the second stream one V-sum pass late (measured: no better).
 // (Round 2 measured sub-batches of 16 ... 128 frame sets run ONE AFTER THE OTHER for Infinity-Cache residency: slower, the small grids
 // cost more than the cache returns; profiles/r02/sweeps.log.)
-static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out, const Nv12Surface *d_surf = nullptr)
+static int balance_plan_run(bevw_handle *h, const FrameSource &src, int batch, const uint8_t *d_car, uint8_t *d_out)
 {
     const bevw_config &c = h->cfg;
     const size_t npx = (size_t)h->pitch_px * c.bev_height;
-    const size_t set_bytes = h->set_bytes();
     BEVW_TRY(ensure_stats(h, batch));
     const size_t cstride = h->plan.compact_stride;   // the compact scratch: only the sampled texel groups of a frame set (bevw_unit.h: unit_gsrc_compact)
     static const int parts_env = [] { const char *s = getenv("BEVW_BAL_PARTS"); return s ? atoi(s) : 0; }();
@@ -1203,12 +1170,11 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
         const int b0 = (int)((long long)batch * part / parts), n = (int)((long long)batch * (part + 1) / parts) - b0;
         if (!n) continue;
         hipStream_t st = (part & 1) ? h->stream2 : h->stream;
-        const uint8_t *fr = d_surf ? nullptr : d_frames + (size_t)b0 * set_bytes;
-        const Nv12Surface *sf = d_surf ? d_surf + (size_t)b0 * 4 : nullptr;   // NV12 surfaces: the slice's part of the table
+        const FrameSource fr = src.from(b0, c.frame_width, c.frame_height);   // the slice's frames
         // (Deriving the deltas inside k_lum_groups instead of by k_lum_delta, a kernel of its own in between, measured SLOWER: 1.669 against
         // 1.660 ms, profiles/r05/ab_call17...: 22 k blocks repeat four fp64 divisions.  The switch is gone.)
         BEVW_TRY(luminance_stats(st, fr, n, c.frame_width, c.frame_height, h->vsums.as<unsigned long long>() + (size_t)b0 * 4 * kVsumParts,
-                                 h->deltas.as<int>() + (size_t)b0 * 4, h->nv12(), sf, h->in_pitch()));
+                                 h->deltas.as<int>() + (size_t)b0 * 4));
         if (part == 0 && parts > 1 && skew_env) {   // the other stream's first slice starts when this one's V sums are done
             HIP_TRY(hipEventRecord(h->ev_skew, h->stream));
             HIP_TRY(hipStreamWaitEvent(h->stream2, h->ev_skew, 0));
@@ -1216,10 +1182,13 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
         const size_t slot0 = ring ? (size_t)(part & 1) * slice_max : (size_t)b0;   // the slice's first frame-set slot in the intermediate buffers
         uint8_t *shifted = h->tmp.as<uint8_t>() + slot0 * cstride;
         uint8_t *pre = gain_in + (pre_ring ? slot0 : (size_t)b0) * npx * 3;
-        BEVW_TRY(plan_lum_groups(h->plan, st, fr, shifted, n, h->deltas.as<int>() + (size_t)b0 * 4, h->hsv.as<HsvTables>(), sf));
+        BEVW_TRY(plan_lum_groups(h->plan, st, fr, shifted, n, h->deltas.as<int>() + (size_t)b0 * 4, h->hsv.as<HsvTables>()));
         const bool lut_ok = npx % 4 == 0;   // (odd image sizes: the byte-wise gain kernel, in place, from k_reduce_psums' sums)
-        BEVW_TRY(plan_stitch(h->plan, st, fr, n, c.blend != 0, false, h->deltas.as<int>() + (size_t)b0 * 4, h->hsv.as<HsvTables>(), nullptr,
-                             lut_ok ? nullptr : h->chsums.as<unsigned long long>() + (size_t)b0 * 3, pre, true, batch, b0, shifted, sf));
+        PlanStep step;
+        step.src = fr; step.batch = n; step.blend = c.blend != 0; step.sums = true; step.scratch = shifted; step.out = pre;
+        step.deltas = h->deltas.as<int>() + (size_t)b0 * 4; step.tab = h->hsv.as<HsvTables>();
+        step.chsums = lut_ok ? nullptr : h->chsums.as<unsigned long long>() + (size_t)b0 * 3; step.psums_frames = batch; step.psums_first = b0;
+        BEVW_TRY(plan_stitch(h->plan, st, step));
         BEVW_TRY(gain_pass(h, st, pre, car, d_car, d_out, b0, n, lut_ok, true));
     }
     if (parts > 1) {   // everything the caller enqueues on the handle's stream afterwards sees the whole batch
@@ -1229,26 +1198,22 @@ static int balance_plan_run(bevw_handle *h, const uint8_t *d_frames, int batch, 
     return BEVW_OK;
 }
 
-// d_surf: the frames are NV12 surfaces (bevw_run_surfaces_device: surf[frame set][4] on the device, rows of in_pitch() bytes) and d_frames is
-// nullptr; every kernel reads them in place -- no packing pass on any path
-static int run_device(bevw_handle *h, const uint8_t *d_frames, int batch, const uint8_t *d_car, uint8_t *d_out, const Nv12Surface *d_surf = nullptr)
+static int run_device(bevw_handle *h, const FrameSource &src, int batch, const uint8_t *d_car, uint8_t *d_out)
 {
     const bevw_config &c = h->cfg;
     const bool pitched = h->pitch_px != c.bev_width;
     const size_t npx = (size_t)h->pitch_px * c.bev_height;   // pixels per device image, padding columns included
-    if (pitched && (h->projection != BEVW_PROJ_LUT || h->schedule_in_use != BEVW_SCHED_TILE_PLAN ||
-                    ((((uintptr_t)d_out | (uintptr_t)d_car | (uintptr_t)d_frames) & 3u) != 0)))
+    const bool aligned4 = (((uintptr_t)d_out | (uintptr_t)d_car) & 3u) == 0 && src.aligned4();
+    if (pitched && (h->projection != BEVW_PROJ_LUT || h->schedule_in_use != BEVW_SCHED_TILE_PLAN || !aligned4))
         return fail(BEVW_E_INVALID, "an output pitch needs the tile-plan schedule, the table projection and 4-byte aligned buffers");
-    const bool aligned4 = (((uintptr_t)d_out | (uintptr_t)d_car | (uintptr_t)d_frames) & 3u) == 0;
     // balance schedule of the tile plan: 1 = shift the sampled texel groups of the raw frames once (k_lum_groups), then the units;
     // 0 = luminance round trip per fetched texel inside the per-tap kernel
     static const int bal_mode = [] { const char *s = getenv("BEVW_BAL_MODE"); return s ? atoi(s) : 1; }();
     if (h->projection == BEVW_PROJ_LUT && h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && c.balance && bal_mode == 1 && h->plan.compact_stride != 0)
-        return balance_plan_run(h, d_frames, batch, d_car, d_out, d_surf);
+        return balance_plan_run(h, src, batch, d_car, d_out);
     if (c.balance) {
         BEVW_TRY(ensure_stats(h, batch));
-        BEVW_TRY(luminance_stats(h->stream, d_frames, batch, c.frame_width, c.frame_height,
-                                 h->vsums.as<unsigned long long>(), h->deltas.as<int>(), h->nv12(), d_surf, h->in_pitch()));
+        BEVW_TRY(luminance_stats(h->stream, src, batch, c.frame_width, c.frame_height, h->vsums.as<unsigned long long>(), h->deltas.as<int>()));
         HIP_TRY(hipMemsetAsync(h->chsums.p, 0, sizeof(unsigned long long) * 3 * (size_t)batch, h->stream));
     }
     // NV12 images: the balance modes stitch their BGR pre-gain image into a buffer of the handle's own (the gain pass converts); without
@@ -1260,12 +1225,14 @@ static int run_device(bevw_handle *h, const uint8_t *d_frames, int batch, const 
     }
     const bool plan_ok = !h->out_nv12() || c.balance || h->plan.pitch == h->pitch_px;
     if (h->projection != BEVW_PROJ_LUT) {
-        BEVW_TRY(stitch_analytic(h, d_frames, batch, d_car, d_out));
+        BEVW_TRY(stitch_analytic(h, src.packed, batch, d_car, d_out));   // (BGR frames only: bevw_set_projection, bevw_set_input_format)
     } else if (h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && plan_ok) {
-        BEVW_TRY(plan_stitch(h->plan, h->stream, d_frames, batch, c.blend != 0, c.balance != 0, h->deltas.as<int>(),
-                             h->hsv.as<HsvTables>(), d_car, h->chsums.as<unsigned long long>(), st_out, false, 0, 0, nullptr, d_surf));
+        PlanStep step;
+        step.src = src; step.batch = batch; step.blend = c.blend != 0; step.balance = c.balance != 0; step.car = d_car; step.out = st_out;
+        step.deltas = h->deltas.as<int>(); step.tab = h->hsv.as<HsvTables>(); step.chsums = h->chsums.as<unsigned long long>();
+        BEVW_TRY(plan_stitch(h->plan, h->stream, step));
     } else {
-        BEVW_TRY(stitch_per_pixel(h, d_frames, batch, d_car, st_out, d_surf));
+        BEVW_TRY(stitch_per_pixel(h, src, batch, d_car, st_out));
     }
     if (c.balance) {
         const uint8_t *car = nullptr;
@@ -1407,9 +1374,7 @@ int bevw_build(bevw_handle *h)
     // (seam block tiles: measured +0.7 % slower under the per-tile channel sums of the balance path, -1.4 .. -1.8 % without: sweeps.log)
     h->pitch_px = h->pitch_request == BEVW_PITCH_DENSE ? bw : (h->pitch_request == BEVW_PITCH_ALIGNED ? (bw + 63) / 64 * 64 : h->pitch_request);
     BEVW_TRY(plan_build(h->plan, st, T, cfg.frame_width, cfg.frame_height, bw, bh, ncams, h->pitch_px != bw ? h->pitch_px : 0, cfg.blend != 0));
-    h->plan.nv12 = h->nv12();
-    h->plan.out_nv12 = h->out_nv12();
-    BEVW_TRY(plan_set_src_pitch(h->plan, h->nv12() ? h->in_pitch() : 0));   // the group lists of NV12 surfaces (bevw_run_surfaces_device)
+    BEVW_TRY(h->apply_format());   // (with them the group lists of NV12 surfaces: bevw_run_surfaces_device)
     if (h->shard_n) {
         if (!h->plan.usable) return fail(BEVW_E_INVALID, "camera shard needs the tile plan: %d contributors on some pixel", h->plan.max_contrib);
         // bounding box of the owned masks, widened to multiples of 4 pixels in x so that packed rows stay dword aligned
@@ -1574,9 +1539,8 @@ int bevw_set_input_format(bevw_handle *h, int format)
     HIP_TRY(hipStreamSynchronize(h->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
     if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
     h->input_format = format;
-    h->plan.nv12 = h->nv12();
     if (!h->nv12()) h->in_pitch_request = 0;   // (BGR frames are dense)
-    if (h->built) BEVW_TRY(plan_set_src_pitch(h->plan, h->nv12() ? h->in_pitch() : 0));
+    if (h->built) BEVW_TRY(h->apply_format());
     return BEVW_OK;
 }
 
@@ -1588,7 +1552,7 @@ int bevw_set_input_pitch(bevw_handle *h, int pitch_bytes)
     HIP_TRY(hipStreamSynchronize(h->stream));   // (the group lists are read at launch: no step with the old pitch is still queued)
     if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
     h->in_pitch_request = pitch_bytes;
-    if (h->built) BEVW_TRY(plan_set_src_pitch(h->plan, h->nv12() ? h->in_pitch() : 0));
+    if (h->built) BEVW_TRY(h->apply_format());
     return BEVW_OK;
 }
 
@@ -1619,7 +1583,7 @@ int bevw_set_output_format(bevw_handle *h, int format)
     HIP_TRY(hipStreamSynchronize(h->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
     if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
     h->output_format = format;
-    h->plan.out_nv12 = h->out_nv12();
+    if (h->built) BEVW_TRY(h->apply_format());
     return BEVW_OK;
 }
 
@@ -1661,7 +1625,7 @@ int bevw_run_device(bevw_handle *h, const void *d_frames, int batch, const void 
     if (!d_frames || !d_out || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
     BEVW_TRY(need_packed_frames(h));
     if (batch == 0) return BEVW_OK;
-    return run_device(h, (const uint8_t *)d_frames, batch, (const uint8_t *)d_car, (uint8_t *)d_out);
+    return run_device(h, h->source((const uint8_t *)d_frames, nullptr), batch, (const uint8_t *)d_car, (uint8_t *)d_out);
 }
 
 static int need_surfaces(bevw_handle *h, const void *table, int batch, void *d_out)
@@ -1681,7 +1645,7 @@ int bevw_run_surface_table_device(bevw_handle *h, const void *d_surfaces, int ba
     BEVW_TRY(need_surfaces(h, d_surfaces, batch, d_out));
     if (((uintptr_t)d_surfaces) & 7u) return fail(BEVW_E_INVALID, "the surface table is not 8-byte aligned");
     if (batch == 0) return BEVW_OK;
-    return run_device(h, nullptr, batch, (const uint8_t *)d_car, (uint8_t *)d_out, static_cast<const Nv12Surface *>(d_surfaces));
+    return run_device(h, h->source(nullptr, static_cast<const Nv12Surface *>(d_surfaces)), batch, (const uint8_t *)d_car, (uint8_t *)d_out);
 }
 
 int bevw_run_surfaces_device(bevw_handle *h, const bevw_nv12_surface *surfaces, int batch, const void *d_car, void *d_out)
@@ -1691,8 +1655,8 @@ int bevw_run_surfaces_device(bevw_handle *h, const bevw_nv12_surface *surfaces, 
     const Nv12Surface *d_surf = nullptr;
     int slot = 0;
     BEVW_TRY(h->surf_stage.stage(h->stream, surfaces, (size_t)batch * 4, d_surf, slot));
-    const int s = run_device(h, nullptr, batch, (const uint8_t *)d_car, (uint8_t *)d_out, d_surf);
-    BEVW_TRY(h->surf_stage.done(h->stream, slot));   // (behind whatever was enqueued: the slot's table stays until then)
+    const int s = run_device(h, h->source(nullptr, d_surf), batch, (const uint8_t *)d_car, (uint8_t *)d_out);
+    BEVW_TRY(h->surf_stage.done(h->stream, slot));   // (whether or not the step failed, behind whatever was enqueued: the slot's table stays until then)
     return s;
 }
 
@@ -1715,7 +1679,7 @@ int bevw_run(bevw_handle *h, const uint8_t *frames, int batch, const uint8_t *ca
         HIP_TRY(hipMemcpyAsync(h->car.p, car, bev, hipMemcpyHostToDevice, h->stream));
         d_car = h->car.as<uint8_t>();
     }
-    BEVW_TRY(run_device(h, h->in.as<uint8_t>(), batch, d_car, h->out.as<uint8_t>()));
+    BEVW_TRY(run_device(h, h->source(h->in.as<uint8_t>(), nullptr), batch, d_car, h->out.as<uint8_t>()));
     BEVW_TRY(download_images(h, out, h->out.p, (size_t)batch * c.bev_height));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return BEVW_OK;
@@ -1742,7 +1706,7 @@ int bevw_run_cameras(bevw_handle *h, const uint8_t *front, const uint8_t *back, 
         HIP_TRY(hipMemcpyAsync(h->car.p, car, bev, hipMemcpyHostToDevice, h->stream));
         d_car = h->car.as<uint8_t>();
     }
-    BEVW_TRY(run_device(h, h->in.as<uint8_t>(), 1, d_car, h->out.as<uint8_t>()));
+    BEVW_TRY(run_device(h, h->source(h->in.as<uint8_t>(), nullptr), 1, d_car, h->out.as<uint8_t>()));
     BEVW_TRY(download_images(h, out, h->out.p, (size_t)c.bev_height));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return BEVW_OK;
@@ -1755,7 +1719,8 @@ static int camera_remap(bevw_handle *h, const uint8_t *src, int sw, int sh, cons
     BEVW_TRY(h->in.reserve(nin));
     BEVW_TRY(h->out.reserve(nout));
     HIP_TRY(hipMemcpyAsync(h->in.p, src, nin, hipMemcpyHostToDevice, h->stream));
-    BEVW_TRY(remap_launch(h->stream, h->in.as<uint8_t>(), sw, sh, m1, m2, dw, dh, batch, h->out.as<uint8_t>(), h->compat[BEVW_COMPAT_REMAP]));
+    const FrameSource frames{h->in.as<uint8_t>(), nullptr, 0, false, 1};   // BGR images, one by one
+    BEVW_TRY(remap_launch(h->stream, frames, sw, sh, m1, m2, dw, dh, batch, h->out.as<uint8_t>(), h->compat[BEVW_COMPAT_REMAP], false));
     HIP_TRY(hipMemcpyAsync(dst, h->out.p, nout, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return BEVW_OK;
@@ -1830,10 +1795,9 @@ int bevw_shard_vsums_device(bevw_handle *h, const void *d_frames, int batch, voi
     if (!d_frames || !d_vsums || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
     if (batch == 0) return BEVW_OK;
     const bevw_config &c = h->cfg;
-    const size_t frame_bytes = (size_t)c.frame_width * c.frame_height * 3;
     const int nframes = batch * h->shard_n;
     HIP_TRY(hipMemsetAsync(d_vsums, 0, sizeof(unsigned long long) * (size_t)nframes, h->stream));
-    vsum_launch(h->stream, (const uint8_t *)d_frames, nframes, frame_bytes, (unsigned long long *)d_vsums, 0);   // one entry per frame
+    vsum_launch(h->stream, h->source((const uint8_t *)d_frames, nullptr), nframes, c.frame_width, c.frame_height, (unsigned long long *)d_vsums, 0);   // one entry per frame
     return launch_check("k_vsum");
 }
 
@@ -1845,9 +1809,9 @@ int bevw_shard_run_device(bevw_handle *h, const void *d_frames, int batch, const
     if (c.balance && !d_all_vsums) return fail(BEVW_E_INVALID, "balance needs the V sums of all four cameras");
     if ((((uintptr_t)d_out | (uintptr_t)d_frames) & 3u) != 0) return fail(BEVW_E_INVALID, "device buffers must be 4-byte aligned");
     if (batch == 0) return BEVW_OK;
-    const uint8_t *frames = (const uint8_t *)d_frames;
-    if (!c.balance) return plan_stitch(h->plan, h->stream, frames, batch, c.blend != 0, false, nullptr, nullptr, nullptr, nullptr,
-                                       (uint8_t *)d_out);
+    PlanStep step;
+    step.src = h->source((const uint8_t *)d_frames, nullptr); step.batch = batch; step.blend = c.blend != 0; step.out = (uint8_t *)d_out;
+    if (!c.balance) return plan_stitch(h->plan, h->stream, step);
     // luminance_balance (surroundBEV.py:57-79) with the means of ALL four cameras, applied to the owned ones
     BEVW_TRY(ensure_stats(h, batch));
     BEVW_TRY(h->sdeltas.reserve(sizeof(int) * 4 * (size_t)batch));
@@ -1859,16 +1823,17 @@ int bevw_shard_run_device(bevw_handle *h, const void *d_frames, int batch, const
     hipLaunchKernelGGL(k_delta_select, dim3((batch * 4 + 255) / 256), dim3(256), 0, h->stream, h->deltas.as<int>(), sc, batch,
                        h->sdeltas.as<int>());
     BEVW_TRY(launch_check("k_lum_delta/k_delta_select"));
+    step.deltas = h->sdeltas.as<int>(); step.tab = h->hsv.as<HsvTables>();
     static const int bal_mode = [] { const char *s = getenv("BEVW_BAL_MODE"); return s ? atoi(s) : 1; }();
     if (bal_mode == 1 && h->plan.compact_stride != 0) {
         BEVW_TRY(h->tmp.reserve(h->plan.compact_stride * (size_t)batch));
-        BEVW_TRY(plan_lum_groups(h->plan, h->stream, frames, h->tmp.as<uint8_t>(), batch, h->sdeltas.as<int>(), h->hsv.as<HsvTables>()));
-        return plan_stitch(h->plan, h->stream, frames, batch, c.blend != 0, false, h->sdeltas.as<int>(), h->hsv.as<HsvTables>(), nullptr, nullptr,
-                           (uint8_t *)d_out, false, 0, 0, h->tmp.as<uint8_t>());
+        BEVW_TRY(plan_lum_groups(h->plan, h->stream, step.src, h->tmp.as<uint8_t>(), batch, step.deltas, step.tab));
+        step.scratch = h->tmp.as<uint8_t>();
+        return plan_stitch(h->plan, h->stream, step);
     }
     HIP_TRY(hipMemsetAsync(h->chsums.p, 0, sizeof(unsigned long long) * 3 * (size_t)batch, h->stream));
-    return plan_stitch(h->plan, h->stream, frames, batch, c.blend != 0, true, h->sdeltas.as<int>(), h->hsv.as<HsvTables>(), nullptr,
-                       h->chsums.as<unsigned long long>(), (uint8_t *)d_out);
+    step.balance = true; step.chsums = h->chsums.as<unsigned long long>();
+    return plan_stitch(h->plan, h->stream, step);
 }
 
 // ---- the exchange step over RCCL (bevw_comm.h) -------------------------------------------------------------------
@@ -2078,7 +2043,7 @@ int bevw_luminance_balance(int device, const uint8_t *frames, int batch, int wid
     HsvTables tab = make_hsv_tables();
     if (hipMemcpy(in.p, frames, n, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(tb.p, &tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess)
         return fail(BEVW_E_HIP, "H2D failed");
-    BEVW_TRY(luminance_stats(0, in.as<uint8_t>(), batch, width, height, vs.as<unsigned long long>(), dl.as<int>()));
+    BEVW_TRY(luminance_stats(0, FrameSource{in.as<uint8_t>()}, batch, width, height, vs.as<unsigned long long>(), dl.as<int>()));
     for_each_chunk(batch * 4, [&](int f0, int nf) {
         hipLaunchKernelGGL(k_lum_shift, dim3(64, nf), dim3(256), 0, 0, in.as<uint8_t>() + (size_t)f0 * fpx * 3, fpx,
                            dl.as<int>() + f0, tb.as<HsvTables>(), o.as<uint8_t>() + (size_t)f0 * fpx * 3);

@@ -73,27 +73,26 @@ int plan_build(Plan &p, hipStream_t st, const StitchTables &T, int fw, int fh, i
     return BEVW_OK;
 }
 
-int plan_stitch(Plan &p, hipStream_t st, const uint8_t *d_frames, int batch, bool blend, bool balance, const int *d_deltas, const HsvTables *d_tab,
-                const uint8_t *d_car, unsigned long long *d_chsums, uint8_t *d_out, bool sums, int psums_frames, int psums_first, const uint8_t *d_scratch,
-                const Nv12Surface *d_surf)
+int plan_stitch(Plan &p, hipStream_t st, const PlanStep &step)
 {
-    hipError_t e = plan_stitch_impl(p, st, d_frames, batch, blend, balance, d_deltas, d_tab, d_car, d_chsums, d_out, plan_tuning(), sums, psums_frames,
-                                    psums_first, d_scratch, d_surf);
+    hipError_t e = plan_stitch_impl(p, st, step, plan_tuning());
     if (e != hipSuccess) return fail(BEVW_E_HIP, "tile-plan stitch launch failed: %s", hipGetErrorString(e));
     return BEVW_OK;
 }
 
-int plan_set_src_pitch(Plan &p, int pitch)
+int plan_set_format(Plan &p, bool nv12, bool out_nv12, int src_pitch)
 {
-    hipError_t e = plan_src_pitch_impl(p, pitch);
+    p.nv12 = nv12; p.out_nv12 = out_nv12;
+    if (src_pitch == p.src_pitch) return BEVW_OK;   // (the group lists are the ones of this pitch; none after plan_build, for pitch 0)
+    p.src_pitch = src_pitch;
+    hipError_t e = plan_src_pitch_impl(p, src_pitch);
     if (e != hipSuccess) return fail(BEVW_E_HIP, "uploading the surface group lists failed: %s", hipGetErrorString(e));
     return BEVW_OK;
 }
 
-int plan_lum_groups(const Plan &p, hipStream_t st, const uint8_t *d_frames, uint8_t *d_scratch, int batch, const int *d_deltas, const HsvTables *d_tab,
-                    const Nv12Surface *d_surf)
+int plan_lum_groups(const Plan &p, hipStream_t st, const FrameSource &src, uint8_t *d_scratch, int batch, const int *d_deltas, const HsvTables *d_tab)
 {
-    hipError_t e = plan_lum_band(p, st, d_frames, d_scratch, batch, d_deltas, d_tab, d_surf);
+    hipError_t e = plan_lum_band(p, st, src, d_scratch, batch, d_deltas, d_tab);
     if (e != hipSuccess) return fail(BEVW_E_HIP, "k_lum_groups launch failed: %s", hipGetErrorString(e));
     return BEVW_OK;
 }
