@@ -360,7 +360,8 @@ __device__ __forceinline__ void nv12_store_px(uint8_t *img, int pitch, int bh, i
 // Linear block id of a 1-D grid -> (frame, block inside the frame) such that XCD id % 8 owns WHOLE frames: the rows a kernel
 // writes are then completed inside one L2 (tools/store_pattern.hip: 4.7 TB/s with such a map, 2.9 TB/s when the blocks of a
 // frame are dealt round-robin to the XCDs).  Grid = blocks_per_frame * 8 * ceil(nframes / 8) blocks.
-__device__ __forceinline__ bool xcd_frame_map(uint32_t id, uint32_t blocks_per_frame, uint32_t nframes, uint32_t &frame, uint32_t &blk)
+// (__host__ too: tests/native/batch_map_exhaustive.cpp enumerates the map on the CPU)
+__host__ __device__ __forceinline__ bool xcd_frame_map(uint32_t id, uint32_t blocks_per_frame, uint32_t nframes, uint32_t &frame, uint32_t &blk)
 {
     const uint32_t xcd = id & 7u, k = id >> 3;
     frame = xcd + 8u * (k / blocks_per_frame);

@@ -365,7 +365,8 @@ struct PlanArgs {
 //   xcd_affine 1: an XCD owns whole batch chunks (all tiles of frames b0..b0+nb), neighbouring tiles share its L2
 //   xcd_affine 2: as 1, the chunks of an XCD interleaved unit by unit (BEVW_PLAN_XCDMAP=2)
 //   xcd_affine 0: plain chunk-major order (few chunks)
-__device__ __forceinline__ bool plan_block_map(const PlanArgs &a, uint32_t id, uint32_t &chunk, uint32_t &group)
+// (__host__ too: tests/native/batch_map_exhaustive.cpp enumerates the maps for every batch size on the CPU)
+__host__ __device__ __forceinline__ bool plan_block_map(const PlanArgs &a, uint32_t id, uint32_t &chunk, uint32_t &group)
 {
     const uint32_t ng = (uint32_t)a.ngroups;
     if (a.xcd_affine == 1) {

@@ -59,9 +59,9 @@ def test_units_with_the_16_byte_store_format(tmp_path, pitch):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
-def _run(exe, tmp_path, luts, masks, frames, car, fw, fh, bw, bh, blend=False, fracs=None):
+def _run(exe, tmp_path, luts, masks, frames, car, fw, fh, bw, bh, blend=False, fracs=None, env=None):
     """luts: [(int16 [bh,bw,2], uint16 [bh,bw])], masks: [uint8 [bh,bw]], frames: uint8 [n, ncams, fh, fw, 3];
-    fracs: [uint32 [bh,bw,2]] 21-bit fractions -> a wide plan (the analytic projection mode)"""
+    fracs: [uint32 [bh,bw,2]] 21-bit fractions -> a wide plan (the analytic projection mode); env: the emulator's environment"""
     inp, outp = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
     with open(inp, "wb") as f:
         f.write(struct.pack("<8i", fw, fh, bw, bh, len(luts), frames.shape[0], int(car is not None), int(blend) | (2 if fracs is not None else 0)))
@@ -74,7 +74,7 @@ def _run(exe, tmp_path, luts, masks, frames, car, fw, fh, bw, bh, blend=False, f
         f.write(np.ascontiguousarray(frames, np.uint8).tobytes())
         if car is not None:
             f.write(np.ascontiguousarray(car, np.uint8).tobytes())
-    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     raw = open(outp, "rb").read()
     nunits, claimed, lines, sectors = struct.unpack("<4i", raw[:16])
@@ -114,6 +114,46 @@ def test_units_on_bench_rigs_match_the_oracle(exe, tmp_path, name, cfg, rig, ble
     if max_requests is not None:
         assert got["lines"] + got["sectors"] <= max_requests, got["log"]
     print(got["log"].strip())
+
+
+@pytest.mark.parametrize("pitch", [None, "aligned"])
+@pytest.mark.parametrize("blend", [False, True])
+def test_small_rig_holds_both_kinds_of_frame_loop(exe, tmp_path, blend, pitch):
+    """The small rig of the GPU batch tests (tests/test_batch_chunks_gpu.py: 320 x 256 frames -> 248 x 250 BEV) compiles to units of all four
+    forms of the frame loop of plan_unit_run: classes with at most two rounds of groups alternate two LDS patch halves, the classes with four
+    rounds use one patch and a barrier more, each for one and for two contributors per pixel.  A change to the plan compiler that empties
+    one of the four would leave those tests passing on one kernel path less; this says so.  (dense rows and rows of whole sectors: the two
+    device layouts the batch tests run.)"""
+    import re
+
+    from tests.test_nv12_gpu import SMALL_CFG as cfg, random_car, small_rig
+
+    O.build()
+    gen = O.RefBevGenerator(small_rig(), cfg, blend=blend, balance=False)
+    fw, fh, bw, bh = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"], cfg["BEV_WIDTH"], cfg["BEV_HEIGHT"]
+    rng = np.random.default_rng(13)
+    frames = rng.integers(0, 256, (1, 4, fh, fw, 3), dtype=np.uint8)
+    car = random_car(rng, cfg)
+    env = dict(os.environ)
+    env.pop("BEVW_EMU_PITCH", None)
+    if pitch:
+        env["BEVW_EMU_PITCH"] = pitch
+    got = _run(exe, tmp_path, [cam.bev_maps for cam in gen.cameras], [_mask2d(m) for m in gen.masks], frames, car, fw, fh, bw, bh, blend, env=env)
+    line = [l for l in got["log"].splitlines() if l.startswith("unit schedule ok:")]
+    assert len(line) == 1, got["log"]
+    census = {(int(gr), con == "d"): 0 for gr in (1, 2, 4) for con in ("", "d")}
+    found = re.findall(r" (\d)x(\d)(d?):(\d+)\[", line[0])
+    assert len(found) == 8, line[0]   # the eight unit classes
+    for nq, gr, con, count in found:
+        census[(int(gr), con == "d")] += int(count)
+    assert sum(census.values()) == got["units"], line[0]
+    groups = {"GR <= 2, one contributor": census[(1, False)] + census[(2, False)], "GR == 4, one contributor": census[(4, False)],
+              "GR <= 2, two contributors": census[(1, True)] + census[(2, True)], "GR == 4, two contributors": census[(4, True)]}
+    assert all(n >= 1 for n in groups.values()), "%s\n%s" % (groups, line[0])
+    # the units' pixels are the oracle's
+    w = got["written"] == 1
+    assert w.any() and np.array_equal(got["img"][0][w], gen(*frames[0], car)[w])
+    print(line[0].strip())
 
 
 def test_units_on_the_undistort_map_match_the_oracle(exe, tmp_path):
