@@ -312,6 +312,9 @@ class BevGenerator:
         over: [FH*3//2, FW] uint8, the Y plane followed by the interleaved U / V plane).  An 'nv12' generator returns, byte for byte, what
         a 'bgr' one returns for the frames cv2.cvtColor(f, cv2.COLOR_YUV2BGR_NV12) makes: the conversion is fused into the stitch (see
         bevw_set_input_format in include/bevwarp.h).  Needs even FW and FH and the 'lut' projection; jpeg() / jpeg_stream() take BGR only.
+        'yuyv' / 'uyvy': what a live camera hands over uncompressed (UVC / V4L2: YUYV, "YUY2"; SerDes cameras: UYVY) -- [FH, FW, 2] uint8,
+        the array cv2.cvtColor takes; the generator returns what a 'bgr' one returns for cv2.cvtColor(f, cv2.COLOR_YUV2BGR_YUY2) (or
+        cv2.COLOR_YUV2BGR_UYVY).  Needs an even FW (FH is free) and the 'lut' projection; no input_pitch, no surfaces, no jpeg().
         output_format -- 'bgr' (default: BEV images [BH, BW, 3]) or 'nv12' (what a video encoder takes: [BH*3//2, BW] uint8 per image, the
         Y plane followed by the interleaved U / V plane; on the device rows of ``out_pitch`` bytes for both planes).  An 'nv12' generator
         returns, byte for byte, the NV12 form of what a 'bgr' one returns: cv2.cvtColor(bev, cv2.COLOR_BGR2YUV_I420) with U and V
@@ -321,6 +324,8 @@ class BevGenerator:
         place (None: FW; else a multiple of 4 >= FW; see bevw_set_input_pitch in include/bevwarp.h).  With a pitch other than FW the
         packed entry points (__call__, batch, run_device) are refused."""
         self.init_args()
+        formats = _ffi.INPUT_FORMATS
+        _ffi.input_format(input_format)   # (an unknown keyword is refused before any device call)
         in_pitch = _ffi.check_input_pitch(input_pitch, args.FRAME_WIDTH, input_format == 'nv12')
         if rig is None:
             self.cameras = [Camera('front'), Camera('back'), Camera('left'), Camera('right')]
@@ -335,9 +340,6 @@ class BevGenerator:
         pitch = {'dense': _ffi.PITCH_DENSE, 'aligned': _ffi.PITCH_ALIGNED}.get(output_pitch, output_pitch)
         if not isinstance(pitch, int):
             raise Exception("output_pitch should be auto/dense/aligned or a number of pixels")
-        formats = {'bgr': _ffi.INPUT_BGR, 'nv12': _ffi.INPUT_NV12}
-        if input_format not in formats:
-            raise Exception("input_format should be bgr/nv12")
         out_formats = {'bgr': _ffi.OUTPUT_BGR, 'nv12': _ffi.OUTPUT_NV12}
         if output_format not in out_formats:
             raise Exception("output_format should be bgr/nv12")
@@ -381,11 +383,9 @@ class BevGenerator:
         SIZE_SCALE = args.SIZE_SCALE
 
     def _frame_shape(self):
-        """Shape of one camera frame this generator takes: (FH, FW, 3) for 'bgr', (FH*3//2, FW) for 'nv12'."""
+        """Shape of one camera frame this generator takes: (FH, FW, 3) for 'bgr', (FH*3//2, FW) for 'nv12', (FH, FW, 2) for 'yuyv' / 'uyvy'."""
         c = self._engine.cfg
-        if self.input_format == 'nv12':
-            return (c.frame_height * 3 // 2, c.frame_width)
-        return (c.frame_height, c.frame_width, 3)
+        return _ffi.frame_shape(self.input_format, c.frame_height, c.frame_width)
 
     def _image_shape(self):
         """Shape of one host-side BEV image this generator returns: (BH, BW, 3) for 'bgr', (BH*3//2, BW) for 'nv12'."""
@@ -403,6 +403,12 @@ class BevGenerator:
                 if img.dtype != np.uint8 or img.shape != self._frame_shape():
                     raise Exception("NV12 camera frame must be uint8 {} (FH*3//2, FW), got {} {}".format(self._frame_shape(), img.dtype,
                                                                                                          img.shape))
+        elif self.input_format in ('yuyv', 'uyvy'):
+            images = [np.ascontiguousarray(i) for i in (front, back, left, right)]
+            for img in images:
+                if img.dtype != np.uint8 or img.shape != self._frame_shape():
+                    raise Exception("{} camera frame must be uint8 {} (FH, FW, 2), got {} {}".format(self.input_format.upper(), self._frame_shape(),
+                                                                                                     img.dtype, img.shape))
         else:
             images = [_ffi.as_u8_image(i, "camera frame") for i in (front, back, left, right)]
         for img in images:
@@ -423,7 +429,7 @@ class BevGenerator:
     # ---- additive: batches ---------------------------------------------------------------------------------
     def batch(self, frames, car=None):
         """frames uint8 [B, 4, FH, FW, 3] (front, back, left, right) -> uint8 [B, BH, BW, 3].  An 'nv12' generator takes
-        [B, 4, FH*3//2, FW]; one with output_format='nv12' returns [B, BH*3//2, BW]."""
+        [B, 4, FH*3//2, FW], a 'yuyv' / 'uyvy' one [B, 4, FH, FW, 2]; one with output_format='nv12' returns [B, BH*3//2, BW]."""
         c = self._engine.cfg
         frames = np.ascontiguousarray(frames)
         want = (4,) + self._frame_shape()
@@ -615,12 +621,13 @@ class BevGenerator:
 
     @property
     def in_set_bytes(self) -> int:
-        """Bytes of ONE camera frame set as run_device() reads it: 4 frames of FH x FW x 3 ('bgr') or FH x FW x 3 / 2 ('nv12')."""
+        """Bytes of ONE camera frame set as run_device() reads it: 4 frames of FH x FW x 3 ('bgr'), FH x FW x 3 / 2 ('nv12') or
+        FH x FW x 2 ('yuyv' / 'uyvy')."""
         return 4 * int(np.prod(self._frame_shape()))
 
     def run_device(self, d_frames: int, batch: int, d_car, d_out: int, out_bytes: int = None) -> None:
         """Asynchronous launch on device-resident buffers (raw pointers from DeviceBuffer).  ``d_frames`` holds ``batch`` frame sets of
-        ``in_set_bytes`` each (BGR or NV12 as the generator's input_format says).
+        ``in_set_bytes`` each (in the generator's input_format).
 
         out_bytes: the size of the buffer behind ``d_out``.  The library sees raw pointers and cannot check it, so a handle whose
         device images are pitched (``out_pitch != BEV_WIDTH``: the 'auto' / 'aligned' layouts) REQUIRES it -- a caller that sized its

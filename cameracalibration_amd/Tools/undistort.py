@@ -51,15 +51,15 @@ class Undistorter:
     def __init__(self, K, D, width, height, focalscale=1.0, sizescale=1.0, offset_h=0.0, offset_v=0.0, device=0, input_format='bgr',
                  output_format='bgr', input_pitch=None):
         """input_format: 'bgr' (images [height, width, 3]) or 'nv12' ([height*3//2, width]: Y plane, then the interleaved U / V plane; the
-        result is what cv2.remap gives for cv2.cvtColor(img, cv2.COLOR_YUV2BGR_NV12) -- bevw_remapper_set_input_format in include/bevwarp.h).
+        result is what cv2.remap gives for cv2.cvtColor(img, cv2.COLOR_YUV2BGR_NV12) -- bevw_remapper_set_input_format in include/bevwarp.h),
+        'yuyv' / 'uyvy' ([height, width, 2]: packed 4:2:2 as a live camera delivers it; cv2.COLOR_YUV2BGR_YUY2 / _UYVY; an even width).
         output_format: 'bgr' (results [out_h, out_w, 3]) or 'nv12' ([out_h*3//2, out_w]: the NV12 form of the BGR result, chroma of each 2 x 2
         block from its top-left pixel -- bevw_set_output_format in include/bevwarp.h; needs an even output size).
         input_pitch: with input_format='nv12', bytes between the rows of the decoder surfaces run_surfaces() reads in place (None: width;
         else a multiple of 4 >= width -- bevw_remapper_set_input_pitch); with a pitch other than width __call__ is refused."""
         self._r = None
-        formats = {'bgr': _ffi.INPUT_BGR, 'nv12': _ffi.INPUT_NV12}
-        if input_format not in formats:
-            raise Exception("input_format should be bgr/nv12")
+        formats = _ffi.INPUT_FORMATS
+        _ffi.input_format(input_format)
         out_formats = {'bgr': _ffi.OUTPUT_BGR, 'nv12': _ffi.OUTPUT_NV12}
         if output_format not in out_formats:
             raise Exception("output_format should be bgr/nv12")
@@ -126,9 +126,9 @@ class Undistorter:
 
     def __call__(self, images):
         """uint8 [B, height, width, 3] (or one [height, width, 3]) -> undistorted images of the map size.  'nv12': [B, height*3//2, width]
-        (or one [height*3//2, width]).  output_format 'nv12': [B, out_h*3//2, out_w] (or one [out_h*3//2, out_w])."""
+        (or one [height*3//2, width]); 'yuyv' / 'uyvy': [B, height, width, 2] (or one [height, width, 2]).  output_format 'nv12': [B, out_h*3//2, out_w] (or one [out_h*3//2, out_w])."""
         imgs = np.ascontiguousarray(images)
-        frame = (self.height * 3 // 2, self.width) if self.input_format == 'nv12' else (self.height, self.width, 3)
+        frame = _ffi.frame_shape(self.input_format, self.height, self.width)
         single = imgs.ndim == len(frame)
         if single:
             imgs = imgs[np.newaxis]

@@ -18,6 +18,22 @@ SCHED_AUTO, SCHED_PER_PIXEL, SCHED_TILE_PLAN = 0, 1, 2
 PROJ_LUT, PROJ_ANALYTIC, PROJ_ANALYTIC_F32 = 0, 1, 2   # bevw_set_projection
 PITCH_DENSE, PITCH_ALIGNED = 0, -1                    # bevw_set_output_pitch
 INPUT_BGR, INPUT_NV12 = 0, 1                         # bevw_set_input_format, bevw_remapper_set_input_format
+INPUT_YUYV, INPUT_UYVY = 4, 5                        # packed 4:2:2: Y0 U Y1 V / U Y0 V Y1 per texel pair
+INPUT_FORMATS = {'bgr': INPUT_BGR, 'nv12': INPUT_NV12, 'yuyv': INPUT_YUYV, 'uyvy': INPUT_UYVY}
+
+
+def input_format(name) -> int:
+    """The BEVW_INPUT_* value of an input_format keyword."""
+    if name not in INPUT_FORMATS:
+        raise Exception("input_format should be bgr/nv12/yuyv/uyvy")
+    return INPUT_FORMATS[name]
+
+
+def frame_shape(name, height: int, width: int):
+    """Shape of one camera frame of a format: (H, W, 3) 'bgr', (H*3//2, W) 'nv12', (H, W, 2) 'yuyv' / 'uyvy'."""
+    if name == 'nv12':
+        return (height * 3 // 2, width)
+    return (height, width, 2 if name in ('yuyv', 'uyvy') else 3)
 OUTPUT_BGR, OUTPUT_NV12 = 0, 1                       # bevw_set_output_format, bevw_remapper_set_output_format
 COMPAT_FILLPOLY, COMPAT_ADDWEIGHTED, COMPAT_WARP, COMPAT_REMAP = 0, 1, 2, 3   # bevw_set_compat keys (include/bevwarp.h)
 

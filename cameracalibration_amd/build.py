@@ -2,8 +2,9 @@
 
     python -m cameracalibration_amd.build [--force]
 
-Three translation units -- bevwarp.hip (handles, table builders, tools, the camera-per-GPU exchange), bevwarp_plan.hip (the tile plan
-and its per-frame kernels) and bevwarp_jpeg.hip (the JPEG codec) -- are compiled in parallel into objects under csrc/build/ and linked;
+Four translation units -- bevwarp.hip (handles, table builders, tools, the camera-per-GPU exchange), bevwarp_plan.hip (the tile plan
+and its per-frame kernels), bevwarp_jpeg.hip (the JPEG codec) and bevwarp_yuv422.hip (every kernel that reads packed 4:2:2 camera frames:
+FORMAT_UNITS) -- are compiled in parallel into objects under csrc/build/ and linked;
 a unit is recompiled when its source, ANY header under csrc/ or the flag set changed.  The shared object is written next to this file (in-tree: it travels
 to the GPU box with the repo snapshot and is git-ignored).  -ffp-contract=off is REQUIRED: the arithmetic being reproduced has no fused
 multiply-add.
@@ -22,6 +23,9 @@ LIB = os.path.join(HERE, "libbevwarp.so")
 # translation units; every header under csrc/ (and the public header) is a dependency of every unit: a header edit can never leave a
 # stale object behind (round 4's explicit lists had missed bevw_jpeg_walk.h and bevw_device.h for the JPEG unit)
 UNITS = ["bevwarp.hip", "bevwarp_plan.hip", "bevwarp_jpeg.hip"]
+# units that hold the kernels of one input format and nothing else: the shared device functions of the headers instantiated for that
+# format, under kernel names of their own (no kernel of UNITS is compiled a second time)
+FORMAT_UNITS = ["bevwarp_yuv422.hip"]
 
 
 def _headers():
@@ -58,12 +62,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
         force = True
     jobs = []
     hdrs = _headers()
-    for src in UNITS:
+    for src in UNITS + FORMAT_UNITS:
         obj = os.path.join(OBJ, src.replace(".hip", ".o"))
         deps = [os.path.join(CSRC, src)] + hdrs + [me]
         if force or _newer(obj, deps):
             jobs.append([hipcc] + CFLAGS + EXTRA + ["-c", os.path.join(CSRC, src), "-o", obj])
-    objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in UNITS]
+    objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in UNITS + FORMAT_UNITS]
     if not jobs and not _newer(LIB, objs):
         return LIB
 
@@ -72,7 +76,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)
 
-    with ThreadPoolExecutor(max_workers=len(UNITS)) as pool:
+    with ThreadPoolExecutor(max_workers=len(UNITS + FORMAT_UNITS)) as pool:
         list(pool.map(run, jobs))
     with open(stamp, "w") as f:
         f.write(flags)

@@ -296,6 +296,40 @@ __device__ __forceinline__ uint32_t nv12_texel_planes(const uint8_t *__restrict_
 // bytes of one frame set: BGR 3 per texel, NV12 1.5
 __host__ __device__ __forceinline__ size_t frame_bytes_of(int fw, int fh, bool nv12) { return nv12 ? (size_t)fw * fh * 3 / 2 : (size_t)fw * fh * 3; }
 
+// ---- packed 4:2:2 camera frames (bevw_set_input_format: YUYV, UYVY) ------------------------------------------
+// A frame of fw x fh texels (fw even) is fh rows of fw / 2 texel pairs of 4 bytes: Y0 U Y1 V (YUYV, "YUY2") or U Y0 V Y1 (UYVY).  Texel
+// (x, y) takes Y from its own two bytes and U, V from the pair x / 2 of its own row -- chroma is shared horizontally only, so fh is free.
+// The arithmetic is NV12's (nv12_bgr): cv2.cvtColor(COLOR_YUV2BGR_YUY2 / COLOR_YUV2BGR_UYVY).
+// The format of the camera frames of a step; the values are the BEVW_INPUT_* constants of include/bevwarp.h.
+enum class SrcFormat : int { BGR = 0, NV12 = 1, YUYV = 4, UYVY = 5 };
+__host__ __device__ __forceinline__ bool src_is_yuv422(SrcFormat f) { return f == SrcFormat::YUYV || f == SrcFormat::UYVY; }
+// bytes of one frame: BGR 3 per texel, NV12 1.5, packed 4:2:2 2
+__host__ __device__ __forceinline__ size_t frame_bytes_of(int fw, int fh, SrcFormat f)
+{
+    return src_is_yuv422(f) ? (size_t)fw * fh * 2 : frame_bytes_of(fw, fh, f == SrcFormat::NV12);
+}
+// The byte order as the kernels take it: the v_perm_b32 selectors that pick, from the 8 bytes of four texels {hi, lo}, their four Y bytes
+// and their U V U V bytes -- a wave-uniform kernel argument, so UYVY is no kernel of its own.  Bit 0 of the Y selector is the position of
+// a texel's Y byte inside its two bytes (0: YUYV, 1: UYVY), which is all the per-tap fetch needs.
+constexpr uint32_t kYuv422SelEven = 0x06040200u, kYuv422SelOdd = 0x07050301u;
+struct Yuv422Order { uint32_t ysel, csel; };
+__host__ __device__ __forceinline__ Yuv422Order yuv422_order(SrcFormat f)
+{
+    return f == SrcFormat::UYVY ? Yuv422Order{kYuv422SelOdd, kYuv422SelEven} : Yuv422Order{kYuv422SelEven, kYuv422SelOdd};
+}
+// 8 bytes = texels x .. x+3 of one row (x even) -> their Y bytes and their U V U V bytes: what nv12_row_bgr takes
+__host__ __device__ __forceinline__ void yuv422_split(uint32_t lo, uint32_t hi, Yuv422Order o, uint32_t &y, uint32_t &uv)
+{
+    y = px_perm(hi, lo, o.ysel);
+    uv = px_perm(hi, lo, o.csel);
+}
+// texel (x, y), inside the frame, of the packed 4:2:2 frame at `src` as B | G << 8 | R << 16 (the per-tap kernels); ypos: bit 0 of the Y selector
+__device__ __forceinline__ uint32_t yuv422_texel(const uint8_t *__restrict__ src, int fw, int x, int y, uint32_t ypos)
+{
+    const uint8_t *p = src + ((size_t)y * fw + (x & ~1)) * 2;   // the texel's pair
+    return nv12_bgr(p[2 * (x & 1) + ypos], nv12_chroma(p[1 - ypos], p[3 - ypos]));
+}
+
 // ---- NV12 BEV images (bevw_set_output_format) -------------------------------------------------------------
 // An NV12 image of BW x BH pixels (both even) with a row pitch of `pitch` bytes is a Y plane of BH rows followed by a U / V plane of BH / 2
 // rows, U first, both with the same pitch: pitch * BH * 3 / 2 bytes.  It is cv2.cvtColor(bgr, cv2.COLOR_BGR2YUV_I420) with the U and V
@@ -384,17 +418,19 @@ __device__ __forceinline__ int remap_round10(int S, int ties_even)
 }
 // NV12: `src` is an NV12 frame (nv12_texel), the texels are converted before the balance step
 // SURF (with NV12): `src` is the Y plane and `uvp` the U / V plane of a surface with rows of `pitch` bytes (nv12_texel_planes)
-template <bool LUM, bool NV12 = false, bool SURF = false>
+// P422 (not with NV12): `src` is a packed 4:2:2 frame (yuv422_texel) and `ypos` bit 0 of its Y selector (Yuv422Order)
+template <bool LUM, bool NV12 = false, bool SURF = false, bool P422 = false>
 __device__ __forceinline__ void remap_u8c3_px(const uint8_t *__restrict__ src, int sw, int sh, int sx, int sy,
                                               unsigned code, int out[3], int delta, const HsvTables *hsv, int ties_even = 0,
-                                              const uint8_t *__restrict__ uvp = nullptr, int pitch = 0)
+                                              const uint8_t *__restrict__ uvp = nullptr, int pitch = 0, uint32_t ypos = 0)
 {
     static_assert(!SURF || NV12, "surfaces are NV12");
+    static_assert(!(P422 && NV12), "one source format");
     const int fx = code & 31, fy = (code >> 5) & 31;
     const int ax = kQOne - fx, ay = kQOne - fy;
     const int w00 = ax * ay, w01 = fx * ay, w10 = ax * fy, w11 = fx * fy;
     const unsigned xlim = sw > 1 ? sw - 1 : 0, ylim = sh > 1 ? sh - 1 : 0;
-    if constexpr (NV12) {
+    if constexpr (NV12 || P422) {
         // one path for interior and border footprints: a tap outside the frame is 0 (BORDER_CONSTANT, after the balance step)
         if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) { out[0] = out[1] = out[2] = 0; return; }
         int t[4][3];
@@ -402,7 +438,7 @@ __device__ __forceinline__ void remap_u8c3_px(const uint8_t *__restrict__ src, i
         for (int q = 0; q < 4; ++q) {
             const int x = sx + (q & 1), y = sy + (q >> 1);
             if ((unsigned)x < (unsigned)sw && (unsigned)y < (unsigned)sh) {
-                const uint32_t p = SURF ? nv12_texel_planes(src, uvp, pitch, x, y) : nv12_texel(src, sw, sh, x, y);
+                const uint32_t p = P422 ? yuv422_texel(src, sw, x, y, ypos) : SURF ? nv12_texel_planes(src, uvp, pitch, x, y) : nv12_texel(src, sw, sh, x, y);
                 t[q][0] = (int)(p & 255u); t[q][1] = (int)((p >> 8) & 255u); t[q][2] = (int)(p >> 16);
                 if (LUM) luminance_shift_px(t[q][0], t[q][1], t[q][2], delta, *hsv);
             } else {

@@ -1,5 +1,6 @@
 // bevw_host.h -- host-side plumbing shared by the translation units of libbevwarp.so (bevwarp.hip: handles, tables, tools, the
-// camera-per-GPU exchange; bevwarp_plan.hip: the tile plan and its kernels; bevwarp_jpeg.hip: the JPEG codec): the thread-local
+// camera-per-GPU exchange; bevwarp_plan.hip: the tile plan and its kernels; bevwarp_jpeg.hip: the JPEG codec; bevwarp_yuv422.hip: the kernels
+// that read packed 4:2:2 frames): the thread-local
 // error string behind bevw_last_error(), the HIP_TRY / BEVW_TRY early-return macros, device / pinned buffers, the lap timer, and the
 // launch helpers (batch chunks, compile-time flags, compile-time pixel formats).
 #pragma once

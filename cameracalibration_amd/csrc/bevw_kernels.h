@@ -255,33 +255,16 @@ static __global__ void k_blend_weights(uint8_t *__restrict__ maskA, const uint8_
 // grid = (ceil(dw / 256), dh, batch).  NV12: the sources are NV12 frames (bevw_remapper_set_input_format), converted per tap.
 // OUT_NV12: dst holds dense NV12 images (bevw_remapper_set_output_format, dw and dh even): the pixel's Y, and U / V on even rows and columns
 // SURF: the sources are NV12 surfaces (bevw_remap_surfaces_device): surf[image] with rows of src_pitch bytes, `src` is not read
+// P422: the sources are packed 4:2:2 frames (YUYV / UYVY; ypos: bit 0 of the byte order's Y selector), converted per tap (k_remap_lut_yuv422)
 template <bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
 static __global__ void k_remap_lut(const uint8_t *__restrict__ src, int sw, int sh, const int16_t *__restrict__ map1,
                             const uint16_t *__restrict__ map2, int dw, int dh, uint8_t *__restrict__ dst, int ties_even = 0,
                             const Nv12Surface *__restrict__ surf = nullptr, int src_pitch = 0)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= dw) return;
-    const size_t o = (size_t)y * dw + x;
-    const uint8_t *s = src + (NV12 ? (size_t)blockIdx.z * frame_bytes_of(sw, sh, true) : (size_t)blockIdx.z * sw * sh * 3);
-    const int sx = map1[o * 2], sy = map1[o * 2 + 1];
-    int out[3];
-    if constexpr (SURF) {
-        const Nv12Surface sf = surf[blockIdx.z];
-        remap_u8c3_px<false, true, true>(sf.y, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even, sf.uv, src_pitch);
-    } else {
-        remap_u8c3_px<false, NV12>(s, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even);
-    }
-    if (OUT_NV12) {
-        nv12_store_px(dst + (size_t)blockIdx.z * image_bytes_of(dw, dh, true), dw, dh, x, y,
-                      (uint32_t)out[0] | ((uint32_t)out[1] << 8) | ((uint32_t)out[2] << 16));
-        return;
-    }
-    uint8_t *d = dst + ((size_t)blockIdx.z * dw * dh + o) * 3;
-    d[0] = (uint8_t)out[0]; d[1] = (uint8_t)out[1]; d[2] = (uint8_t)out[2];
+    constexpr bool P422 = false;
+    constexpr uint32_t ypos = 0;
+#include "bevw_body_remap_lut.h"
 }
-
 // cv2.warpPerspective(src_8UC3, H, dsize): coordinates made on the fly (extrinsicCalib.py:166-169).
 // warp_mode (BEVW_COMPAT_WARP): 0 = the classic fixed-point kernels, else member `warp_mode` of the float32 family (bevw_device.h)
 static __global__ void k_warp_perspective(const uint8_t *__restrict__ src, int sw, int sh, Mat3 Minv, int bw0, int dw, int dh,
@@ -424,73 +407,17 @@ static __global__ void k_lum_shift(const uint8_t *__restrict__ frames, size_t fr
 // NV12: NV12 frame sets (bevw_set_input_format), every tap converted where it is fetched (remap_u8c3_px)
 // OUT_NV12 (not with BAL, whose pre-gain image is BGR): dense NV12 BEV images (bevw_set_output_format), converted after the car
 // SURF: NV12 surfaces (bevw_run_surfaces_device) -- surf[frame set][camera] with rows of src_pitch bytes, `frames` is not read
+// P422: packed 4:2:2 frame sets (YUYV / UYVY; ypos: bit 0 of the byte order's Y selector), every tap converted where it is fetched (k_stitch_pp_yuv422)
 template <bool BLEND, bool BAL, bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
 static __global__ void k_stitch_pp(const uint8_t *__restrict__ frames, int fw, int fh, StitchTables T, int bw, int bh,
                             const int *__restrict__ deltas, const HsvTables *__restrict__ tab,
                             const uint8_t *__restrict__ car, unsigned long long *__restrict__ chsums,
                             uint8_t *__restrict__ out, int ties_even = 0, const Nv12Surface *__restrict__ surf = nullptr, int src_pitch = 0)
 {
-    __shared__ HsvTables hsv;
-    __shared__ unsigned long long part[3][4];
-    if (BAL) {
-        hsv_tables_to_lds(hsv, tab);
-        __syncthreads();
-    }
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    const int b = blockIdx.z;
-    const size_t frame_bytes = NV12 ? frame_bytes_of(fw, fh, true) : (size_t)fw * fh * 3;
-    int acc[3] = {0, 0, 0};
-    if (x < bw) {
-        const size_t o = (size_t)y * bw + x;
-#pragma unroll 1
-        for (int c = 0; c < 4; ++c) {
-            const int m = T.mask[c][o];
-            if (m == 0) continue;
-            const uint8_t *src = frames + ((size_t)b * 4 + c) * frame_bytes;
-            const int sx = T.lut1[c][o * 2], sy = T.lut1[c][o * 2 + 1];
-            int v[3];
-            if constexpr (SURF) {
-                const Nv12Surface sf = surf[(size_t)b * 4 + c];
-                remap_u8c3_px<BAL, true, true>(sf.y, fw, fh, sx, sy, T.lut2[c][o] & (kQTab2 - 1), v, BAL ? deltas[b * 4 + c] : 0, &hsv, ties_even, sf.uv,
-                                               src_pitch);
-            } else
-            remap_u8c3_px<BAL, NV12>(src, fw, fh, sx, sy, T.lut2[c][o] & (kQTab2 - 1), v, BAL ? deltas[b * 4 + c] : 0, &hsv, ties_even);
-            if (BLEND) {
-                const float wgt = blend_weight_f32(m);
-                v[0] = blend_mul(v[0], wgt); v[1] = blend_mul(v[1], wgt); v[2] = blend_mul(v[2], wgt);
-            }
-            acc[0] = min(255, acc[0] + v[0]); acc[1] = min(255, acc[1] + v[1]); acc[2] = min(255, acc[2] + v[2]);
-        }
-        uint8_t *d = out + ((size_t)b * bw * bh + o) * 3;
-        if (!BAL && car != nullptr) {
-            acc[0] = min(255, acc[0] + car[o * 3]); acc[1] = min(255, acc[1] + car[o * 3 + 1]);
-            acc[2] = min(255, acc[2] + car[o * 3 + 2]);
-        }
-        if (OUT_NV12) {
-            static_assert(!(OUT_NV12 && BAL), "balance: the pre-gain image is BGR, the gain pass writes NV12");
-            nv12_store_px(out + (size_t)b * image_bytes_of(bw, bh, true), bw, bh, x, y,
-                          (uint32_t)acc[0] | ((uint32_t)acc[1] << 8) | ((uint32_t)acc[2] << 16));
-        } else {
-            d[0] = (uint8_t)acc[0]; d[1] = (uint8_t)acc[1]; d[2] = (uint8_t)acc[2];
-        }
-    }
-    if (BAL) {
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            unsigned s = wave_sum_u32((unsigned)acc[k]);
-            if (lane == 0) part[k][wv] = s;
-        }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            unsigned long long t = 0;
-            for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += part[threadIdx.x][i];
-            atomicAdd(&chsums[b * 3 + threadIdx.x], t);
-        }
-    }
+    constexpr bool P422 = false;
+    constexpr uint32_t ypos = 0;
+#include "bevw_body_stitch_pp.h"
 }
-
 // ---------------------------------------------------------------------------------------------------------------
 // Analytic projection (BASELINE north star): the same stitch WITHOUT look-up tables.  Per frame and
 // BEV pixel: inverse homography -> undistorted pixel -> fisheye model (the formulas of cv2.fisheye.initUndistortRectifyMap,

@@ -62,6 +62,17 @@ __host__ __device__ __forceinline__ void pair_convert_nv12(uint32_t y0, uint32_t
     pair_convert(has ? d0 : 0u, has ? d1 : 0u, has ? d2 : 0u, has ? P[4] : 0u, A, B);
 }
 
+// Packed 4:2:2 frames (bevw_set_input_format: YUYV, UYVY): the group is ONE 16-byte load at 2 * (texel index) -- texels x .. x+7 of the
+// row, of which x .. x+4 are used.  Four v_perm_b32 with the byte order's two selectors (Yuv422Order, bevw_device.h: wave-uniform) split
+// it into the 8 Y bytes and the 8 U / V bytes, which are exactly the two words pair_convert_nv12 takes.
+__host__ __device__ __forceinline__ void pair_convert_yuv422(uint32_t dx, uint32_t dy, uint32_t dz, uint32_t dw, Yuv422Order o, bool has, uint4 &A, uint4 &B)
+{
+    uint32_t y0, y1, c0, c1;
+    yuv422_split(dx, dy, o, y0, c0);
+    yuv422_split(dz, dw, o, y1, c1);
+    pair_convert_nv12(y0, y1, c0, c1, has, A, B);
+}
+
 // one pixel from its two pair entries: accumulators with the result byte in bits 16..23.  The y weights come pre-scaled by 64:
 // (S * 64 + 512 * 64) >> 16 == (S + 512) >> 10, so the 12 output bytes of a lane are assembled with v_perm_b32 instead of shifts.
 __host__ __device__ __forceinline__ void bilinear_pairs(uint2 q0, uint2 q1, uint32_t wxa, uint32_t wxb, uint32_t wy64, uint32_t acc[3])

@@ -25,6 +25,7 @@
 
 #include "bevw_device.h"
 #include "bevw_planapi.h"
+#include "bevw_yuv422.h"
 
 namespace bevw {
 
@@ -68,6 +69,10 @@ __host__ __device__ __forceinline__ void add_car(uint32_t P[4], uint32_t c0, uin
     }
 }
 
+// BEVW_PLAN_SHARED_ONLY (bevwarp_yuv422.hip): this header without the plan's own kernels and host code -- PlanArgs, the shared device functions
+// and the kernel templates only.  A non-template kernel is emitted by every unit that sees it, and the host dispatch instantiates every
+// kernel it names; a unit that adds kernels of its own must see neither.
+#ifndef BEVW_PLAN_SHARED_ONLY
 // ---------------------------------------------------------------------------------------------------------------
 // plan compiler: one wave per base tile
 // ---------------------------------------------------------------------------------------------------------------
@@ -153,6 +158,8 @@ static __global__ void k_plan_touch(const uint2 *__restrict__ plan, int ntiles, 
         }
 }
 
+#endif   // BEVW_PLAN_SHARED_ONLY
+
 // luminance_balance (surroundBEV.py:57-79) applied to the sampled texel groups of every raw frame, into the COMPACT scratch (bevw_unit.h:
 // unit_gsrc_compact): slot i of a frame set's scratch = HSV2BGR(sat(V + delta)) of group groups[i].  One lane = one group = 4 texels
 // (12 bytes, one dwordx3 each way); groups[] holds byte offsets inside the frame set in ascending order, so neighbouring lanes read
@@ -166,6 +173,8 @@ static __global__ void k_plan_touch(const uint2 *__restrict__ plan, int ntiles, 
 // The scratch is BGR either way.
 // SURF: NV12 surfaces (bevw_run_surfaces_device): surf[frame set][4], `groups` holds the offsets inside the camera's own planes and the camera
 // in the low bits of the second one (unit_gsrc_surf); `frames` is not read.
+// P422: packed 4:2:2 frame sets (YUYV / UYVY), `groups` holds one offset per group (unit_gsrc_yuv422) and frame_bytes is a 4:2:2 frame's; a
+// lane loads the 8 bytes of its 4 texels and splits them by the byte order's selectors (`order`) into the Y and U / V words of the NV12 path.
 constexpr int kLumTrips = 8;
 template <bool NV12 = false, bool SURF = false>
 static __global__ void __launch_bounds__(256) k_lum_groups(const uint8_t *__restrict__ frames, uint8_t *__restrict__ scratch, size_t set_bytes,
@@ -173,63 +182,10 @@ static __global__ void __launch_bounds__(256) k_lum_groups(const uint8_t *__rest
                                                             const int *__restrict__ deltas, const HsvTables *__restrict__ tab,
                                                             uint32_t blocks_per_frame, uint32_t nframes, const Nv12Surface *__restrict__ surf = nullptr)
 {
-    static_assert(!SURF || NV12, "surfaces are NV12");
-    __shared__ HsvTables hsv;
-    __shared__ int cam_delta[4];
-    uint32_t frame, blk;
-    if (!xcd_frame_map(blockIdx.x, blocks_per_frame, nframes, frame, blk)) return;   // grid: xcd_frame_grid()
-    hsv_tables_to_lds(hsv, tab);
-    if (threadIdx.x < 4) cam_delta[threadIdx.x] = deltas[frame * 4 + threadIdx.x];   // k_lum_delta's (a kernel of its own: bevwarp.hip luminance_stats)
-    const uint8_t *fin = frames + (size_t)frame * set_bytes;
-    uint8_t *fout = scratch + (size_t)frame * scratch_stride;
-    const int g0 = (int)blk * (kLumTrips * 256) + (int)threadIdx.x;
-    uint32_t goff[kLumTrips], coff[kLumTrips];
-    AlignedU3 v[kLumTrips];
-    if (NV12) {
-#pragma unroll
-        for (int t = 0; t < kLumTrips; ++t) {
-            const bool in = g0 + t * 256 < ngroups;
-            goff[t] = in ? groups[2 * (g0 + t * 256)] : 0u;
-            coff[t] = in ? groups[2 * (g0 + t * 256) + 1] : 0u;
-        }
-#pragma unroll
-        for (int t = 0; t < kLumTrips; ++t) {   // v.x = Y bytes, v.y = U / V bytes of texels x .. x+3
-            if constexpr (SURF) {   // (past the list: texels 0 .. 3 of camera 0 once more, not stored)
-                const Nv12Surface sf = surf[(size_t)frame * 4 + unit_surf_cam(coff[t])];
-                v[t].x = *reinterpret_cast<const uint32_t *>(sf.y + goff[t]);
-                v[t].y = *reinterpret_cast<const uint32_t *>(sf.uv + unit_surf_uv(coff[t]));
-            } else {
-                v[t].x = *reinterpret_cast<const uint32_t *>(fin + goff[t]);
-                v[t].y = *reinterpret_cast<const uint32_t *>(fin + coff[t]);
-            }
-            v[t].z = 0u;
-        }
-    } else {
-#pragma unroll
-        for (int t = 0; t < kLumTrips; ++t) goff[t] = g0 + t * 256 < ngroups ? groups[g0 + t * 256] : 0u;
-#pragma unroll
-        for (int t = 0; t < kLumTrips; ++t) v[t] = *reinterpret_cast<const AlignedU3 *>(fin + goff[t]);   // (past the list: group 0 once more, not stored)
-    }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < kLumTrips; ++t) {
-        const int gi = g0 + t * 256;
-        if (gi >= ngroups) break;
-        const uint32_t w[3] = {v[t].x, v[t].y, v[t].z};
-        const int cam = SURF ? (int)unit_surf_cam(coff[t]) : (int)(goff[t] >= frame_bytes) + (int)(goff[t] >= 2u * frame_bytes) + (int)(goff[t] >= 3u * frame_bytes);
-        const int delta = cam_delta[cam];
-        // the 4 texels of the group as dwords (byte 3 is ignored), shifted, and packed back into the 12 bytes
-        uint32_t P[4] = {w[0], __builtin_amdgcn_alignbyte(w[1], w[0], 3), __builtin_amdgcn_alignbyte(w[2], w[1], 2), w[2] >> 8};
-        if (NV12) nv12_row_bgr<4>(w[0], w[1], P);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) P[k] = luminance_shift_bgr(P[k], delta, hsv);
-        uint32_t o[3];
-        pack_pixels(P, o[0], o[1], o[2]);
-        AlignedU3 ov; ov.x = o[0]; ov.y = o[1]; ov.z = o[2];
-        *reinterpret_cast<AlignedU3 *>(fout + (size_t)gi * 12) = ov;
-    }
+    constexpr bool P422 = false;
+    constexpr Yuv422Order order = {};
+#include "bevw_body_lum_groups.h"
 }
-
 // ---------------------------------------------------------------------------------------------------------------
 // per-entry evaluation (the per-tap tile kernel)
 // ---------------------------------------------------------------------------------------------------------------
@@ -287,16 +243,19 @@ __device__ __forceinline__ void entry_to_taps(EntryRegs &e, int fw, uint32_t fra
 // NV12: `fb` is an NV12 frame set, frame_bytes an NV12 frame's, every valid entry on the per-tap path (entry_to_taps) with the conversion per
 // fetched texel (remap_u8c3_px); an entry without a contributor adds 0
 // SURF: `fs` holds the surfaces of the frame set's cameras (rows of src_pitch bytes), `fb` is not read
-template <bool BLEND, bool BAL, bool NV12 = false, bool SURF = false>
+// P422: `fb` is a packed 4:2:2 frame set, frame_bytes a 4:2:2 frame's, ypos bit 0 of the byte order's Y selector; evaluated as NV12 is
+template <bool BLEND, bool BAL, bool NV12 = false, bool SURF = false, bool P422 = false>
 __device__ __forceinline__ void eval_entry(const uint8_t *__restrict__ fb, const EntryRegs &e, uint32_t row_bytes, int fw,
                                            int fh, uint32_t frame_bytes, bool tile_slow, const int *__restrict__ fdeltas,
-                                           const HsvTables &hsv, int v[3], const Nv12Surface *__restrict__ fs = nullptr, int src_pitch = 0)
+                                           const HsvTables &hsv, int v[3], const Nv12Surface *__restrict__ fs = nullptr, int src_pitch = 0, uint32_t ypos = 0)
 {
     const int cam = (e.meta >> 18) & 3;
-    if (NV12) {
+    if (NV12 || P422) {
         if (e.meta & kMetaValid) {
             const int sx = (int)(int16_t)(e.off & 0xffffu), sy = (int)(int16_t)(e.off >> 16);
-            if constexpr (SURF) {
+            if constexpr (P422) {
+                remap_u8c3_px<BAL, false, false, true>(fb + (size_t)cam * frame_bytes, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv, 0, nullptr, 0, ypos);
+            } else if constexpr (SURF) {
                 const Nv12Surface sf = fs[cam];
                 remap_u8c3_px<BAL, true, true>(sf.y, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv, 0, sf.uv, src_pitch);
             } else
@@ -358,6 +317,8 @@ struct PlanArgs {
     // un_gsrc then holds the units' group lists relative to the camera's own planes (unit_gsrc_surf)
     const Nv12Surface *surf;
     int src_pitch;
+    // packed 4:2:2 frame sets (the P422 instantiations): the byte order of `frames` (YUYV / UYVY); un_gsrc then holds unit_gsrc_yuv422's list
+    Yuv422Order yuv422;
 };
 
 // Block index -> (batch chunk, tile group).  Blocks are dealt to the 8 XCDs round-robin (block id % 8), and each XCD has
@@ -386,6 +347,13 @@ __host__ __device__ __forceinline__ bool plan_block_map(const PlanArgs &a, uint3
     return (int)chunk < a.nchunks;
 }
 
+// blocks of a launch over a.ngroups groups per batch chunk: the XCD maps deal the chunks in whole rounds of 8 (plan_block_map)
+static inline unsigned plan_grid(const PlanArgs &a)
+{
+    if (a.xcd_affine >= 1) return (unsigned)(a.ngroups * (((a.nchunks + 7) / 8) * 8));
+    return (unsigned)(a.ngroups * a.nchunks);
+}
+
 // The per-tap tile kernel.  grid: blocks of 4 waves = 4 base tiles of the list; one tile per wave.
 // LUM: luminance round trip per fetched texel (raw frames); SUMS: emit per-tile channel sums and leave the car to the gain pass
 // (two waves per SIMD: the 128-VGPR budget of rounds 1 - 3 spilled 0.5 - 1.2 KB per lane to scratch -- tools/kernel_resources.sh)
@@ -393,111 +361,19 @@ __host__ __device__ __forceinline__ bool plan_block_map(const PlanArgs &a, uint3
 // OUT_NV12: NV12 BEV images (bevw_set_output_format; a.pitch % 4 == 0, no SUMS: the balance modes store BGR for the gain pass) -- a lane's
 // quad as one Y dword and, on even rows, one U / V dword (nv12_quad), after the car
 // SURF: NV12 surfaces (a.surf, a.src_pitch) instead of a.frames
+// P422: packed 4:2:2 frame sets (a.yuv422), on the per-tap path as NV12 is (k_stitch_plan_yuv422)
 template <bool BLEND, bool LUM, bool SUMS = LUM, bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) k_stitch_plan(PlanArgs a)
 {
-    static_assert(!SURF || NV12, "surfaces are NV12");
-    constexpr bool BAL = LUM;
-    __shared__ __attribute__((aligned(16))) uint32_t hsv_words[BAL ? sizeof(HsvTables) / 4 : 1];   // (no LDS for the variants without the luminance round trip)
-    const HsvTables &hsv = *reinterpret_cast<const HsvTables *>(hsv_words);
-    if (BAL) {
-        hsv_tables_to_lds(*reinterpret_cast<HsvTables *>(hsv_words), a.tab);
-        __syncthreads();
-    }
-    uint32_t chunk, group;
-    if (!plan_block_map(a, blockIdx.x, chunk, group)) return;
-    const int lane = threadIdx.x & 63;
-    const int slot = (int)group * (int)(blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (slot >= a.nlist) return;
-    const int tile = a.tile_list ? (int)__builtin_amdgcn_readfirstlane(a.tile_list[slot]) : slot;
-
-    const uint32_t hdr = __builtin_amdgcn_readfirstlane(a.hdr[tile]);
-    const bool second = hdr & kHdrSecond, tile_slow = hdr & kHdrSlow;
-    const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
-    const int x0 = (tx * kPlanLX + lane % kPlanLX) * 4, y = ty * kPlanLY + lane / kPlanLX;
-    const bool inimg = x0 < a.bw && y < a.bh;
-    const uint32_t frame_bytes = (uint32_t)a.fw * a.fh * 3, row_bytes = (uint32_t)a.fw * 3;
-    const uint32_t src_frame = NV12 ? frame_bytes / 2 : frame_bytes;   // bytes of one camera frame as the kernel reads it (NV12: fw even)
-    const size_t set_bytes = (size_t)src_frame * a.ncams, img_bytes = (size_t)a.pitch * a.bh * 3;
-    const uint32_t ooff = ((uint32_t)y * a.pitch + x0) * 3;
-
-    EntryRegs e0[4], e1[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        e0[j] = decode_entry(a.plan[((size_t)tile * 8 + j) * 64 + lane], BLEND);
-        e1[j] = decode_entry(second ? a.plan[((size_t)tile * 8 + 4 + j) * 64 + lane] : make_uint2(0, 0), BLEND);
-        if (NV12) { entry_to_taps(e0[j], a.fw, frame_bytes); entry_to_taps(e1[j], a.fw, frame_bytes); }
-    }
-    uint32_t car0 = 0, car1 = 0, car2 = 0;
-    if (!SUMS && a.car != nullptr && inimg) {
-        const uint32_t *cp = reinterpret_cast<const uint32_t *>(a.car + ooff);
-        car0 = cp[0]; car1 = cp[1]; car2 = cp[2];
-    }
-    const bool car_any = __builtin_amdgcn_ballot_w64((car0 | car1 | car2) != 0) != 0;
-
-    const int b_begin = (int)chunk * a.nb, b_end = min(a.batch, b_begin + a.nb);
-#pragma unroll 1
-    for (int b = b_begin; b < b_end; ++b) {
-        const uint8_t *fb = SURF ? nullptr : a.frames + (size_t)b * set_bytes;
-        const Nv12Surface *fs = SURF ? a.surf + (size_t)b * a.ncams : nullptr;
-        const int *fdeltas = BAL ? a.deltas + b * 4 : nullptr;
-        int px[4][3];
-        if (hdr & kHdrEmpty) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) px[j][0] = px[j][1] = px[j][2] = 0;
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                eval_entry<BLEND, BAL, NV12, SURF>(fb, e0[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, px[j], fs, a.src_pitch);
-            }
-            if (second) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    int w[3];
-                    eval_entry<BLEND, BAL, NV12, SURF>(fb, e1[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, w, fs, a.src_pitch);
-                    px[j][0] = min(255, px[j][0] + w[0]); px[j][1] = min(255, px[j][1] + w[1]); px[j][2] = min(255, px[j][2] + w[2]);
-                }
-            }
-        }
-        if (SUMS) {
-            // per-tile channel sums of the pre-gain BEV (color_balance means, surroundBEV.py:44-47); pixels outside
-            // the image have no plan entry and contribute 0.  One entry per listed tile (PlanArgs::sum_base).
-            unsigned s0 = 0, s1 = 0, s2 = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { s0 += px[j][0]; s1 += px[j][1]; s2 += px[j][2]; }
-            s0 = wave_sum_u32(s0); s1 = wave_sum_u32(s1); s2 = wave_sum_u32(s2);
-            if (lane == 0) {
-                uint32_t *ps = a.psums + ((size_t)b * a.nsum + a.sum_base + slot) * 3;
-                ps[0] = s0; ps[1] = s1; ps[2] = s2;
-            }
-        }
-        uint32_t P[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) P[j] = (uint32_t)px[j][0] | ((uint32_t)px[j][1] << 8) | ((uint32_t)px[j][2] << 16);
-        if (!SUMS && car_any) add_car(P, car0, car1, car2);
-        if (OUT_NV12) {
-            static_assert(!(OUT_NV12 && SUMS), "balance: the pre-gain image is BGR, the gain pass writes NV12");
-            if (inimg) {
-                uint32_t yw, uvw;
-                nv12_quad(P, yw, uvw);
-                uint8_t *img = a.out + (size_t)b * image_bytes_of(a.pitch, a.bh, true);
-                *reinterpret_cast<uint32_t *>(img + nv12_y_offset(a.pitch, x0, y)) = yw;
-                if (!(y & 1)) *reinterpret_cast<uint32_t *>(img + nv12_uv_offset(a.pitch, a.bh, x0, y)) = uvw;
-            }
-        } else if (inimg) {
-            uint32_t d0, d1, d2;
-            pack_pixels(P, d0, d1, d2);
-            uint32_t *op = reinterpret_cast<uint32_t *>(a.out + (size_t)b * img_bytes + ooff);
-            op[0] = d0; op[1] = d1; op[2] = d2;
-        }
-    }
+    constexpr bool P422 = false;
+#include "bevw_body_stitch_plan.h"
 }
-
 }  // namespace bevw
 
 #include "bevw_pair.h"
 #include "bevw_unit.h"
 
+#ifndef BEVW_PLAN_SHARED_ONLY
 namespace bevw {
 
 // psums[b][tile][3] -> chsums[b][3] ; grid = batch, block = 256
@@ -698,6 +574,24 @@ static inline hipError_t plan_src_pitch_impl(Plan &p, int pitch)
     return hipSuccess;
 }
 
+// Packed 4:2:2 frame sets: the translation of the group lists for them (unit_gsrc_yuv422), once per plan -- the same lists serve both byte
+// orders.  From the host copies the plan keeps; no step of the plan may be queued.
+static inline hipError_t plan_yuv422_impl(Plan &p)
+{
+    hipError_t e;
+    std::vector<uint32_t> tr;
+    if (p.fw % 4 != 0) return hipSuccess;   // (no unit plan and no group list: the per-tap kernel serves every tile)
+    if (!p.un_gsrc_host.empty() && !p.un_gsrc_yuv422) {
+        unit_gsrc_yuv422(p.un_gsrc_host, p.fw, p.fh, tr);
+        if ((e = plan_upload_list(tr, &p.un_gsrc_yuv422)) != hipSuccess) return e;
+    }
+    if (!p.groups_host.empty() && !p.groups_yuv422) {
+        unit_gsrc_yuv422(p.groups_host, p.fw, p.fh, tr);
+        if ((e = plan_upload_list(tr, &p.groups_yuv422)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 // nb: frames per block (0 = default); xcd_map: 1 = an XCD owns whole batch chunks; units: 0 = the per-tap kernel over every tile (debug)
 struct PlanTuning { int nb = 0; int xcd_map = 1; int units = 1; };
 
@@ -706,7 +600,7 @@ struct PlanTuning { int nb = 0; int xcd_map = 1; int units = 1; };
 static inline PlanArgs plan_args(const Plan &p, const FrameSource &src, int batch, const uint8_t *d_car, uint8_t *d_out, const PlanTuning &tune)
 {
     PlanArgs a = {};
-    a.frames = src.packed; a.surf = src.surf; a.src_pitch = src.pitch;
+    a.frames = src.packed; a.surf = src.surf; a.src_pitch = src.pitch; a.yuv422 = yuv422_order(src.fmt);
     a.car = d_car; a.out = d_out;
     a.fw = p.fw; a.fh = p.fh; a.bw = p.bw; a.bh = p.bh; a.pitch = p.pitch;
     a.tiles_x = p.tiles_x; a.ntiles = p.ntiles; a.ncams = p.ncams;
@@ -729,17 +623,12 @@ static inline PlanArgs plan_args(const Plan &p, const FrameSource &src, int batc
     return a;
 }
 
-// blocks of a launch over a.ngroups groups per batch chunk: the XCD maps deal the chunks in whole rounds of 8 (plan_block_map)
-static inline unsigned plan_grid(const PlanArgs &a)
+// The unit kernel of a step.  Five names, so that k_plan_units stays the four BGR instantiations (bevw_unit.h), and two more behind
+// yuv422_launch_units.  nv12 / surf / yuv422: what the UNITS read -- the step's frames, or the BGR compact scratch of the balance schedule;
+// channel sums exist with BGR in and out only.
+static inline void plan_launch_units(const PlanArgs &a, hipStream_t st, bool blend, bool sums, bool nv12, bool surf, bool out_nv12, bool yuv422)
 {
-    if (a.xcd_affine >= 1) return (unsigned)(a.ngroups * (((a.nchunks + 7) / 8) * 8));
-    return (unsigned)(a.ngroups * a.nchunks);
-}
-
-// The unit kernel of a step.  Five names, so that k_plan_units stays the four BGR instantiations (bevw_unit.h).  nv12 / surf: what the UNITS
-// read -- the step's frames, or the BGR compact scratch of the balance schedule; channel sums exist with BGR in and out only.
-static inline void plan_launch_units(const PlanArgs &a, hipStream_t st, bool blend, bool sums, bool nv12, bool surf, bool out_nv12)
-{
+    if (yuv422) return yuv422_launch_units(a, st, blend, out_nv12);   // (k_units_yuv422 / k_units_out_yuv422: bevwarp_yuv422.hip)
     const dim3 grid(plan_grid(a)), block(256);
     with_formats(nv12, surf, out_nv12, [&](auto in, auto on) {
         constexpr bool NV12 = decltype(in)::nv12, SURF = decltype(in)::surf, OUT_NV12 = decltype(on)::value;
@@ -759,7 +648,7 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
     hipError_t e;
     const int batch = s.batch;
     const bool surf = s.src.is_surf();
-    if (s.src.nv12 != p.nv12 || s.src.cams != p.ncams || (surf && (s.src.pitch != p.src_pitch || p.src_pitch < p.fw || p.src_pitch % 4 != 0)))
+    if (s.src.fmt != p.fmt || s.src.cams != p.ncams || (surf && (s.src.pitch != p.src_pitch || p.src_pitch < p.fw || p.src_pitch % 4 != 0)))
         return hipErrorInvalidValue;   // (not the frames the plan's format was set for: plan_set_format)
     PlanArgs a = plan_args(p, s.src, batch, s.car, s.out, tune);
     a.plan = static_cast<const uint2 *>(p.entries); a.hdr = static_cast<const uint32_t *>(p.hdr);
@@ -787,10 +676,13 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
     // the units need 4-byte aligned frame sets (dword-addressed group loads) and are not combined with the per-tap luminance kernel
     const bool compact = s.scratch != nullptr;
     // NV12 frames: the units read them through the NV12 group lists unless they read the compact scratch (BGR)
-    const bool nv12_units = p.nv12 && !compact;
+    const bool nv12_units = p.nv12() && !compact;
+    // packed 4:2:2 frames: the same, through their own group lists
+    const bool yuv422_units = p.yuv422() && !compact;
     const bool use_units = !s.balance && tune.units && p.n_un_all > 0 && s.src.aligned4() &&
                            (!compact || (p.un_gsrc_compact != nullptr && (((uintptr_t)s.scratch) & 3u) == 0)) &&
-                           (!nv12_units || ((surf ? p.un_gsrc_surf : p.un_gsrc_nv12) != nullptr && !s.sums));
+                           (!nv12_units || ((surf ? p.un_gsrc_surf : p.un_gsrc_nv12) != nullptr && !s.sums)) &&
+                           (!yuv422_units || (p.un_gsrc_yuv422 != nullptr && !s.sums));
     const bool with_sums = s.balance || s.sums;
     // channel-sum entries per frame: one per unit + one per base tile left to the per-tap kernel (or one per tile without units).  Every
     // entry has exactly one writer per frame (no atomics, round 5: 2.4 M atomic adds per config-4 step cost 58 us of the 600), and every writer
@@ -820,7 +712,11 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
             a.set_stride = (uint32_t)(frame_bytes_of(p.fw, p.fh, true) * p.ncams);
             a.un_gsrc = static_cast<const uint32_t *>(surf ? p.un_gsrc_surf : p.un_gsrc_nv12);
         }
-        plan_launch_units(a, st, s.blend, s.sums, nv12_units, surf && nv12_units, out_nv12);
+        if (yuv422_units) {
+            a.set_stride = (uint32_t)(frame_bytes_of(p.fw, p.fh, p.fmt) * p.ncams);
+            a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_yuv422);
+        }
+        plan_launch_units(a, st, s.blend, s.sums, nv12_units, surf && nv12_units, out_nv12, yuv422_units);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const int n_tap = use_units ? p.n_slow : p.ntiles;
@@ -829,7 +725,9 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
         a.nlist = n_tap; a.ngroups = (n_tap + 3) / 4;
         if (s.sums) a.car = nullptr;
         a.frames = s.src.packed; a.set_stride = 0;   // the per-tap kernel reads whole frames: RAW ones in the balance modes
-        with_formats(p.nv12, surf, out_nv12, [&](auto in, auto on) {
+        // (packed 4:2:2: k_stitch_plan_yuv422, bevwarp_yuv422.hip)
+        if (p.yuv422()) yuv422_launch_stitch_plan(a, st, s.blend, s.balance || compact, s.balance || s.sums, out_nv12);
+        else with_formats(p.nv12(), surf, out_nv12, [&](auto in, auto on) {
             constexpr bool NV12 = decltype(in)::nv12, SURF = decltype(in)::surf, OUT_NV12 = decltype(on)::value;
             auto launch = [&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm, NV12, OUT_NV12, SURF>), dim3(plan_grid(a)), dim3(256), 0, st, a); };
             // LUM: luminance round trip per tap (the RAW frames of balance, or the tiles no unit owns beside the compact scratch); compact
@@ -872,13 +770,17 @@ static inline hipError_t plan_lum_band(const Plan &p, hipStream_t st, const Fram
 {
     if (p.n_groups == 0 || p.compact_stride == 0) return hipSuccess;
     // the sampled groups as this kind of source addresses them (surfaces: relative to the camera's own planes, plan_src_pitch_impl)
-    const void *groups = src.is_surf() ? p.groups_surf : (src.nv12 ? p.groups_nv12 : p.groups);
-    if (!groups || src.nv12 != p.nv12 || src.cams != p.ncams || (src.is_surf() && src.pitch != p.src_pitch)) return hipErrorInvalidValue;
-    const size_t frame_bytes = frame_bytes_of(p.fw, p.fh, src.nv12);
+    const void *groups = src.is_surf() ? p.groups_surf : (src.nv12() ? p.groups_nv12 : (src.yuv422() ? p.groups_yuv422 : p.groups));
+    if (!groups || src.fmt != p.fmt || src.cams != p.ncams || (src.is_surf() && src.pitch != p.src_pitch)) return hipErrorInvalidValue;
+    const size_t frame_bytes = frame_bytes_of(p.fw, p.fh, src.fmt);
     const unsigned bpf = (unsigned)(p.n_groups + 256 * kLumTrips - 1) / (256 * kLumTrips);
     for_each_chunk(batch, [&](int b0, int nb) {
         const FrameSource fr = src.from(b0, p.fw, p.fh);
-        with_input(src.nv12, src.is_surf(), [&](auto in) {
+        if (src.yuv422())   // (k_lum_groups_yuv422: bevwarp_yuv422.hip)
+            yuv422_launch_lum_groups(st, dim3(xcd_frame_grid(bpf, (unsigned)nb)), fr.packed, d_scratch + (size_t)b0 * p.compact_stride, src.set_bytes(p.fw, p.fh),
+                                     p.compact_stride, (uint32_t)frame_bytes, static_cast<const uint32_t *>(groups), p.n_groups, d_deltas + (size_t)b0 * 4,
+                                     d_tab, bpf, (uint32_t)nb, yuv422_order(src.fmt));
+        else with_input(src.nv12(), src.is_surf(), [&](auto in) {
             hipLaunchKernelGGL((k_lum_groups<decltype(in)::nv12, decltype(in)::surf>), dim3(xcd_frame_grid(bpf, (unsigned)nb)), dim3(256), 0, st, fr.packed,
                                d_scratch + (size_t)b0 * p.compact_stride, src.set_bytes(p.fw, p.fh), p.compact_stride, (uint32_t)frame_bytes,
                                static_cast<const uint32_t *>(groups), p.n_groups, d_deltas + (size_t)b0 * 4, d_tab, bpf, (uint32_t)nb, fr.surf);
@@ -888,3 +790,4 @@ static inline hipError_t plan_lum_band(const Plan &p, hipStream_t st, const Fram
 }
 
 }  // namespace bevw
+#endif   // BEVW_PLAN_SHARED_ONLY

@@ -2,7 +2,7 @@
 // entry points with their arguments (FrameSource, PlanStep).  No kernels: the plan kernels (bevw_plan.h, bevw_unit.h) are compiled in
 // bevwarp_plan.hip alone, which defines every function declared here.  Every plan_* function that returns an int returns a BEVW_* status and leaves its message in bevw_last_error().
 #pragma once
-#include "bevw_device.h"   // Nv12Surface, HsvTables, frame_bytes_of
+#include "bevw_device.h"   // Nv12Surface, HsvTables, SrcFormat, frame_bytes_of
 #include "bevw_host.h"
 
 namespace bevw {
@@ -14,17 +14,19 @@ struct StitchTables {
     const uint8_t *mask[4];
 };
 
-// Where the camera frames of a step are.  Packed: `packed` points at frame sets of `cams` dense frames, BGR or NV12.  Surfaces: `surf` is a
+// Where the camera frames of a step are.  Packed: `packed` points at frame sets of `cams` dense frames of format `fmt`.  Surfaces: `surf` is a
 // device table surf[frame set][cams] of NV12 surfaces with rows of `pitch` bytes, which every kernel reads in place; `packed` is then nullptr
 // and is never read.
 struct FrameSource {
     const uint8_t *packed = nullptr;
     const Nv12Surface *surf = nullptr;
     int pitch = 0;       // bytes between the rows of a surface
-    bool nv12 = false;
+    SrcFormat fmt = SrcFormat::BGR;
     int cams = 4;        // frames per set: 4 for a BevGenerator, 1 for a remapper or a list of single frames
     bool is_surf() const { return surf != nullptr; }
-    size_t set_bytes(int fw, int fh) const { return frame_bytes_of(fw, fh, nv12) * (size_t)cams; }
+    bool nv12() const { return fmt == SrcFormat::NV12; }
+    bool yuv422() const { return src_is_yuv422(fmt); }   // packed 4:2:2 (YUYV / UYVY): never surfaces
+    size_t set_bytes(int fw, int fh) const { return frame_bytes_of(fw, fh, fmt) * (size_t)cams; }
     bool aligned4() const { return (((uintptr_t)packed) & 3u) == 0; }   // dword loads (a surface's planes were checked when its table was staged)
     FrameSource from(int b0, int fw, int fh) const   // the source of frame set b0 onward
     {
@@ -72,8 +74,10 @@ struct Plan {
     int n_unit_tiles = 0;                    // base tiles the units own
     size_t un_lines = 0, un_sectors = 0;     // request arithmetic of the partition (per frame)
     int un_skew = 0;
-    // The formats of the plan's steps, written by plan_set_format alone (plan_build resets them).  nv12: they read NV12 frame sets (bevw_set_input_format).
-    bool nv12 = false;
+    // The formats of the plan's steps, written by plan_set_format alone (plan_build resets them).  fmt: what their frame sets hold (bevw_set_input_format).
+    SrcFormat fmt = SrcFormat::BGR;
+    bool nv12() const { return fmt == SrcFormat::NV12; }
+    bool yuv422() const { return src_is_yuv422(fmt); }
     // out_nv12: they write NV12 images of `pitch` bytes per row (bevw_set_output_format; needs pitch % 4 == 0 and no padded scratch).  Steps
     // with channel sums (balance) still write the BGR pre-gain image: their gain pass converts.
     bool out_nv12 = false;
@@ -83,6 +87,9 @@ struct Plan {
     int src_pitch = 0;
     void *un_gsrc_surf = nullptr;            // the units' group lists, two dwords per slot
     void *groups_surf = nullptr;             // the sampled groups of the balance schedule (k_lum_groups<true, true>), two dwords per group
+    // packed 4:2:2 frame sets (YUYV / UYVY): one dword per slot (unit_gsrc_yuv422), uploaded by plan_set_format when such a format is first set
+    void *un_gsrc_yuv422 = nullptr;          // the units' group lists
+    void *groups_yuv422 = nullptr;           // the sampled groups of the balance schedule (k_lum_groups_yuv422)
     std::vector<uint32_t> un_gsrc_host, groups_host, un_ranges_host;   // (un_ranges_host: first slot and slot count of every unit's list)
 };
 
@@ -117,7 +124,7 @@ int plan_lum_groups(const Plan &p, hipStream_t st, const FrameSource &src, uint8
 
 // The pixel formats of the plan's steps, and for NV12 surfaces the row pitch the group lists are translated for (0: none).  After plan_build,
 // with no step queued.
-int plan_set_format(Plan &p, bool nv12, bool out_nv12, int src_pitch);
+int plan_set_format(Plan &p, SrcFormat fmt, bool out_nv12, int src_pitch);
 
 // rows of bw pixels -> rows of pitch pixels (the car sprite of a pitched handle)
 int plan_pad_image(hipStream_t st, const uint8_t *d_src, int bw, int pitch, int bh, uint8_t *d_dst);

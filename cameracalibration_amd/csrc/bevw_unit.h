@@ -542,6 +542,19 @@ static inline void unit_gsrc_nv12(const std::vector<uint32_t> &gsrc, int fw, int
         out[2 * i + 1] = cam * nv_frame + y_bytes + (y >> 1) * (uint32_t)fw + x;
     }
 }
+// Packed 4:2:2 frame sets (bevw_set_input_format: YUYV, UYVY): the third translation -- ONE dword per slot, the byte offset of the group's
+// first texel inside a frame set of 2 bytes per texel: 2 * (cam * fw * fh + y * fw + x), a multiple of 8.  The same list for both byte
+// orders.  fw % 4 == 0; fh is free (no vertical chroma sharing).
+static inline void unit_gsrc_yuv422(const std::vector<uint32_t> &gsrc, int fw, int fh, std::vector<uint32_t> &out)
+{
+    out.assign(gsrc.size(), kPairNoGroup);
+    const uint32_t frame_bytes = (uint32_t)fw * fh * 3, row_bytes = (uint32_t)fw * 3, texels = (uint32_t)fw * fh;
+    for (size_t i = 0; i < gsrc.size(); ++i) {
+        if (gsrc[i] == kPairNoGroup) continue;
+        const uint32_t cam = gsrc[i] / frame_bytes, t = gsrc[i] % frame_bytes, y = t / row_bytes, x = t % row_bytes / 3;
+        out[i] = 2u * (cam * texels + y * (uint32_t)fw + x);
+    }
+}
 // NV12 surfaces (bevw_run_surfaces_device): the same list translated into offsets relative to the CAMERA'S OWN planes, whose rows are `pitch`
 // bytes apart (bevw_set_input_pitch; >= fw, a multiple of 4): out[2 i] = Y of texel (x, y) inside the Y plane, out[2 i + 1] = U of texel
 // (x, y) inside the U / V plane | the camera (0 .. 3) in the two low bits -- group offsets are multiples of 4 (x % 4 == 0, pitch % 4 == 0),
@@ -835,10 +848,14 @@ __device__ __forceinline__ void unit_store_dword(uint32_t v, __amdgpu_buffer_rsr
 // once; the one mixed instruction of a unit is issued twice, under the execution masks lane < split and lane >= split: the masked-off lanes
 // issue no request, so every group is requested exactly once, and nothing is kept per lane beyond the two offsets the packed NV12 kernel
 // keeps.  (Option (b) of the three in DESIGN.md "NV12 surfaces".)
-template <bool BLEND, bool SUMS, int NQ, int GR, int NCON, bool WIDE = false, bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
+// P422 (not with NV12): the frames are packed 4:2:2 frame sets (YUYV / UYVY) and a.un_gsrc holds one offset per group slot (unit_gsrc_yuv422):
+// the group is ONE 16-byte load through the frame set's range-checked descriptor, as for BGR, split by the byte order's selectors
+// (a.yuv422: a kernel argument, so both orders run the same kernel) and converted where it lands (pair_convert_yuv422).
+template <bool BLEND, bool SUMS, int NQ, int GR, int NCON, bool WIDE = false, bool NV12 = false, bool OUT_NV12 = false, bool SURF = false, bool P422 = false>
 __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk, uint32_t unit, uint8_t *lds, uint4 *wave_sums = nullptr)
 {
     static_assert(!SURF || NV12, "surfaces are NV12");
+    static_assert(!(P422 && (NV12 || SUMS || WIDE)), "4:2:2 units: table projection, raw frames");
     static_assert(NQ >= 1 && NQ <= kUnitMaxNQ && GR >= 1 && GR <= kUnitMaxGR && (NCON == 1 || NCON == 2), "unit class");
     static_assert(!(WIDE && SUMS), "wide plans carry no channel sums");
     static_assert(!(NV12 && (SUMS || WIDE)), "NV12 units: table projection, raw frames");
@@ -1065,6 +1082,9 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
                 const pair_u32x2 cv = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)gc[r], 0, kPairLoadAux);
                 pf[ring][r] = pair_u32x4{yv.x, yv.y, cv.x, cv.y};
             } else {
+                // (P422: texels x .. x+7, of which x .. x+4 are used.  A row's last group reaches 8 bytes into the next row, the last group of
+                // the set's last row 8 bytes past the set: two whole dwords outside the descriptor -- zeros, no memory touched -- and texel
+                // x+4 of such a group is never sampled, by the argument of the NV12 comment above.)
                 pf[ring][r] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)gs[r], 0, kPairLoadAux);
             }
         }
@@ -1074,6 +1094,7 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
         for (int r = 0; r < GR; ++r) {
             uint4 A, B;
             if (NV12) pair_convert_nv12(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, gs[r] != kPairNoGroup, A, B);
+            else if (P422) pair_convert_yuv422(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, a.yuv422, gs[r] != kPairNoGroup, A, B);
             else pair_convert(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, A, B);
             uint4 *sp = reinterpret_cast<uint4 *>(lds + (DB ? (ring & 1) * kPatch : 0)) + (r * kUnitThreads + (int)threadIdx.x) * 2;
             sp[0] = A;
@@ -1211,14 +1232,14 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
 
 // block -> (chunk, unit) of the list of ALL units in the partition's own (spatial) order, class in bits 28..31: neighbouring units run
 // at the same time on the same XCD, whatever their class, so the two halves of a sector that two units share meet in the L2
-template <bool BLEND, bool SUMS, bool NV12, bool OUT_NV12 = false, bool SURF = false>
+template <bool BLEND, bool SUMS, bool NV12, bool OUT_NV12 = false, bool SURF = false, bool P422 = false>
 __device__ __forceinline__ void plan_unit_any(const PlanArgs &a, uint32_t block_id, uint8_t *lds, uint4 *wave_sums)
 {
     uint32_t chunk, group;
     if (!plan_block_map(a, block_id, chunk, group)) return;
     if ((int)group >= a.nlist) return;
     const uint32_t e = __builtin_amdgcn_readfirstlane(a.tile_list[group]), unit = e & 0x0fffffffu;
-#define BEVW_UNIT_CASE(C) case C: plan_unit_run<BLEND, SUMS, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C], false, NV12, OUT_NV12, SURF>(a, chunk, unit, lds, wave_sums); break;
+#define BEVW_UNIT_CASE(C) case C: plan_unit_run<BLEND, SUMS, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C], false, NV12, OUT_NV12, SURF, P422>(a, chunk, unit, lds, wave_sums); break;
     switch (e >> 28) {
         BEVW_UNIT_CASE(0) BEVW_UNIT_CASE(1) BEVW_UNIT_CASE(2) BEVW_UNIT_CASE(3)
         // class 4 (two quads per lane, two contributors): with float blend weights (rounds 3 - 5) its blend variant needed 177 .. 197 VGPRs and
@@ -1228,7 +1249,7 @@ __device__ __forceinline__ void plan_unit_any(const PlanArgs &a, uint32_t block_
 #if !BEVW_UNIT_NO_BIG   // (experiment builds without the (4, 4) class: every other class fits 128 VGPRs = 4 waves per SIMD; plans then need BEVW_UNIT_BIG=0)
         BEVW_UNIT_CASE(7)
 #endif
-        default: plan_unit_run<BLEND, SUMS, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6], false, NV12, OUT_NV12, SURF>(a, chunk, unit, lds, wave_sums); break;
+        default: plan_unit_run<BLEND, SUMS, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6], false, NV12, OUT_NV12, SURF, P422>(a, chunk, unit, lds, wave_sums); break;
     }
 #undef BEVW_UNIT_CASE
 }

@@ -17,6 +17,7 @@
 
 #include "bevw_kernels.h"
 #include "bevw_planapi.h"
+#include "bevw_yuv422.h"
 #include "bevw_comm.h"
 
 using namespace bevw;
@@ -314,6 +315,12 @@ struct SurfStage {
     }
 };
 
+// the input formats of a handle or a remapper (BEVW_INPUT_*; SrcFormat carries the same values)
+static bool input_format_known(int f) { return f == BEVW_INPUT_BGR || f == BEVW_INPUT_NV12 || f == BEVW_INPUT_YUYV || f == BEVW_INPUT_UYVY; }
+static const char *input_format_name(int f) { return f == BEVW_INPUT_NV12 ? "NV12" : f == BEVW_INPUT_YUYV ? "YUYV" : f == BEVW_INPUT_UYVY ? "UYVY" : "BGR"; }
+static_assert((int)SrcFormat::BGR == BEVW_INPUT_BGR && (int)SrcFormat::NV12 == BEVW_INPUT_NV12 && (int)SrcFormat::YUYV == BEVW_INPUT_YUYV &&
+              (int)SrcFormat::UYVY == BEVW_INPUT_UYVY, "SrcFormat holds the BEVW_INPUT_* values");
+
 // the rules of an input pitch (bevw_set_input_pitch, bevw_remapper_set_input_pitch): 0 = the frame width
 static int check_input_pitch(int pitch_bytes, int fw, int fh, bool nv12)
 {
@@ -340,14 +347,15 @@ struct bevw_remapper {
     int ties_even = 0;    // BEVW_COMPAT_REMAP at creation: half-to-even ties -> the per-pixel kernel (the plan's arithmetic rounds half up)
     int input_format = BEVW_INPUT_BGR;   // bevw_remapper_set_input_format
     bool nv12() const { return input_format == BEVW_INPUT_NV12; }
+    SrcFormat fmt() const { return (SrcFormat)input_format; }
     int output_format = BEVW_OUTPUT_BGR; // bevw_remapper_set_output_format
     bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
     int in_pitch_request = 0;            // bevw_remapper_set_input_pitch (0: the source width)
     int in_pitch() const { return in_pitch_request ? in_pitch_request : sw; }
     SurfStage surf_stage;                // bevw_remap_surfaces_device
     // the sources of a step: packed images behind d_src, or (d_surf) a device table of NV12 surfaces with rows of in_pitch() bytes
-    FrameSource source(const uint8_t *d_src, const Nv12Surface *d_surf) const { return {d_surf ? nullptr : d_src, d_surf, d_surf ? in_pitch() : 0, nv12(), 1}; }
-    int apply_format() { return plan_set_format(plan, nv12(), out_nv12(), nv12() ? in_pitch() : 0); }
+    FrameSource source(const uint8_t *d_src, const Nv12Surface *d_surf) const { return {d_surf ? nullptr : d_src, d_surf, d_surf ? in_pitch() : 0, fmt(), 1}; }
+    int apply_format() { return plan_set_format(plan, fmt(), out_nv12(), nv12() ? in_pitch() : 0); }
 };
 
 // cv2.remap as a 1-camera stitch: every destination pixel has exactly one contributor with mask 255.
@@ -395,7 +403,10 @@ static int remap_launch(hipStream_t st, const FrameSource &src, int sw, int sh, 
 {
     for_each_chunk(batch, [&](int b0, int nb) {
         const FrameSource fr = src.from(b0, sw, sh);
-        with_formats(src.nv12, src.is_surf(), out_nv12, [&](auto in, auto on) {
+        if (src.yuv422())   // (k_remap_lut_yuv422: bevwarp_yuv422.hip)
+            yuv422_launch_remap_lut(st, dim3((dw + 255) / 256, dh, nb), out_nv12, fr.packed, sw, sh, m1, m2, dw, dh,
+                                    d_dst + (size_t)b0 * image_bytes_of(dw, dh, out_nv12), ties_even, yuv422_order(src.fmt));
+        else with_formats(src.nv12(), src.is_surf(), out_nv12, [&](auto in, auto on) {
             hipLaunchKernelGGL((k_remap_lut<decltype(in)::nv12, on, decltype(in)::surf>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, fr.packed, sw, sh,
                                m1, m2, dw, dh, d_dst + (size_t)b0 * image_bytes_of(dw, dh, on), ties_even, fr.surf, fr.pitch);
         });
@@ -596,7 +607,7 @@ int bevw_remapper_set_input_pitch(bevw_remapper *r, int pitch_bytes)
 static int remap_need_surfaces(bevw_remapper *r, const void *table, int batch, void *d_dst)
 {
     if (!r || !table || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
-    if (!r->nv12()) return fail(BEVW_E_INVALID, "surfaces are NV12: the remapper's input format is BGR (bevw_remapper_set_input_format)");
+    if (!r->nv12()) return fail(BEVW_E_INVALID, "surfaces are NV12: the remapper's input format is %s (bevw_remapper_set_input_format)", input_format_name(r->input_format));
     if (r->in_pitch() % 4 != 0)
         return fail(BEVW_E_INVALID, "the source width %d is not a multiple of 4: surfaces need an input pitch that is (bevw_remapper_set_input_pitch)", r->sw);
     return BEVW_OK;
@@ -664,9 +675,11 @@ int bevw_remapper_set_output_format(bevw_remapper *r, int format)
 int bevw_remapper_set_input_format(bevw_remapper *r, int format)
 {
     if (!r) return fail(BEVW_E_INVALID, "null remapper");
-    if (format != BEVW_INPUT_BGR && format != BEVW_INPUT_NV12) return fail(BEVW_E_INVALID, "unknown input format %d", format);
+    if (!input_format_known(format)) return fail(BEVW_E_INVALID, "unknown input format %d", format);
     if (format == BEVW_INPUT_NV12 && (r->sw % 2 || r->sh % 2))
         return fail(BEVW_E_INVALID, "NV12 needs an even source width and height, got %dx%d", r->sw, r->sh);
+    if (src_is_yuv422((SrcFormat)format) && r->sw % 2)
+        return fail(BEVW_E_INVALID, "%s needs an even source width, got %dx%d", input_format_name(format), r->sw, r->sh);
     BEVW_TRY(use_device(r->device));
     HIP_TRY(hipStreamSynchronize(r->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
     r->input_format = format;
@@ -683,7 +696,7 @@ int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst)
                     r->in_pitch(), r->sw);
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
-    const size_t nin = (size_t)batch * frame_bytes_of(r->sw, r->sh, r->nv12()), nout = (size_t)batch * image_bytes_of(r->dw, r->dh, r->out_nv12());
+    const size_t nin = (size_t)batch * frame_bytes_of(r->sw, r->sh, r->fmt()), nout = (size_t)batch * image_bytes_of(r->dw, r->dh, r->out_nv12());
     BEVW_TRY(r->in.reserve(nin));
     BEVW_TRY(r->out.reserve(nout));
     HIP_TRY(hipMemcpyAsync(r->in.p, src, nin, hipMemcpyHostToDevice, r->stream));
@@ -844,7 +857,9 @@ struct bevw_handle {
     int projection = BEVW_PROJ_LUT;   // bevw_set_projection
     int input_format = BEVW_INPUT_BGR;   // bevw_set_input_format
     bool nv12() const { return input_format == BEVW_INPUT_NV12; }
-    size_t set_bytes() const { return frame_bytes_of(cfg.frame_width, cfg.frame_height, nv12()) * 4; }   // one camera frame set as the handle reads it
+    SrcFormat fmt() const { return (SrcFormat)input_format; }
+    bool yuv422() const { return src_is_yuv422(fmt()); }   // packed 4:2:2: YUYV / UYVY
+    size_t set_bytes() const { return frame_bytes_of(cfg.frame_width, cfg.frame_height, fmt()) * 4; }   // one camera frame set as the handle reads it
     int in_pitch_request = 0;            // bevw_set_input_pitch (0: the frame width)
     int in_pitch() const { return in_pitch_request ? in_pitch_request : cfg.frame_width; }   // bytes between the rows of an NV12 surface
     SurfStage surf_stage;                // bevw_run_surfaces_device
@@ -855,9 +870,9 @@ struct bevw_handle {
     int pitch_px = 0;                 // pixels per row of the device-side BEV images (== bev_width unless a pitch was requested)
     size_t out_image_bytes() const { return image_bytes_of(pitch_px, cfg.bev_height, out_nv12()); }   // one device-side BEV image
     // the frames of a step: packed frame sets behind d_frames, or (d_surf) a device table surf[frame set][4] of NV12 surfaces, read in place
-    FrameSource source(const uint8_t *d_frames, const Nv12Surface *d_surf) const { return {d_surf ? nullptr : d_frames, d_surf, d_surf ? in_pitch() : 0, nv12(), shard_n ? shard_n : 4}; }
+    FrameSource source(const uint8_t *d_frames, const Nv12Surface *d_surf) const { return {d_surf ? nullptr : d_frames, d_surf, d_surf ? in_pitch() : 0, fmt(), shard_n ? shard_n : 4}; }
     // the plan follows the handle's formats (bevw_build behind plan_build; the setters of a built handle, with its streams idle)
-    int apply_format() { return plan_set_format(plan, nv12(), out_nv12(), nv12() ? in_pitch() : 0); }
+    int apply_format() { return plan_set_format(plan, fmt(), out_nv12(), nv12() ? in_pitch() : 0); }
     DevBuf car_pitched;               // the car sprite with rows of pitch_px pixels (gain pass of a pitched handle)
     AnalyticRig arig;                 // filled by bevw_build
     Plan aplan;                       // analytic modes: the WIDE unit schedule compiled from the projection (analytic_units_build)
@@ -929,7 +944,11 @@ static int stitch_per_pixel(bevw_handle *h, const FrameSource &src, int batch, c
         const dim3 grid((c.bev_width + 255) / 256, c.bev_height, nb), block(256);
         const FrameSource fr = src.from(b0, c.frame_width, c.frame_height);
         uint8_t *o = d_out + (size_t)b0 * image_bytes_of(c.bev_width, c.bev_height, out_nv12);
-        with_formats(src.nv12, src.is_surf(), out_nv12, [&](auto in, auto on) {
+        if (src.yuv422())   // (k_stitch_pp_yuv422: bevwarp_yuv422.hip)
+            yuv422_launch_stitch_pp(h->stream, grid, c.blend != 0, c.balance != 0, out_nv12, fr.packed, c.frame_width, c.frame_height, T, c.bev_width,
+                                    c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car, chs ? chs + b0 * 3 : nullptr, o,
+                                    h->compat[BEVW_COMPAT_REMAP], yuv422_order(src.fmt));
+        else with_formats(src.nv12(), src.is_surf(), out_nv12, [&](auto in, auto on) {
             auto launch = [&](auto bl, auto ba) {
                 hipLaunchKernelGGL((k_stitch_pp<bl, ba, decltype(in)::nv12, on, decltype(in)::surf>), grid, block, 0, h->stream, fr.packed, c.frame_width,
                                    c.frame_height, T, c.bev_width, c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car,
@@ -1041,9 +1060,12 @@ static int vsum_launch(hipStream_t st, FrameSource src, int nframes, int fw, int
     const size_t per_frame = part_stride > 0 ? (size_t)part_stride : 1;
     for_each_chunk(nframes, [&](int f0, int nf) {
         const FrameSource fr = src.from(f0, fw, fh);
-        with_input(src.nv12, src.is_surf(), [&](auto in) {
+        if (src.yuv422())   // (k_vsum_yuv422: bevwarp_yuv422.hip; its 16-byte loads)
+            yuv422_launch_vsum(st, dim3(bpf, nf), fr.packed, frame_bytes, (frame_bytes % 16 == 0 && (((uintptr_t)fr.packed) & 15u) == 0) ? 1 : 0,
+                               d_vsums + (size_t)f0 * per_frame, part_stride, yuv422_order(src.fmt));
+        else with_input(src.nv12(), src.is_surf(), [&](auto in) {
             hipLaunchKernelGGL((k_vsum<decltype(in)::nv12, decltype(in)::surf>), dim3(bpf, nf), dim3(256), 0, st, fr.packed, frame_bytes, vec_ok,
-                               d_vsums + (size_t)f0 * per_frame, part_stride, src.nv12 ? fw : 0, fr.surf, fr.pitch);
+                               d_vsums + (size_t)f0 * per_frame, part_stride, src.nv12() ? fw : 0, fr.surf, fr.pitch);
         });
     });
     return bpf;
@@ -1484,7 +1506,8 @@ int bevw_set_projection(bevw_handle *h, int mode)
     if (!h) return fail(BEVW_E_INVALID, "null handle");
     if (mode != BEVW_PROJ_LUT && mode != BEVW_PROJ_ANALYTIC && mode != BEVW_PROJ_ANALYTIC_F32) return fail(BEVW_E_INVALID, "unknown projection mode %d", mode);
     if (mode != BEVW_PROJ_LUT && h->shard_n) return fail(BEVW_E_INVALID, "analytic projection is not available on camera-shard handles");
-    if (mode != BEVW_PROJ_LUT && h->nv12()) return fail(BEVW_E_INVALID, "analytic projection is not available with NV12 input");
+    if (mode != BEVW_PROJ_LUT && (h->nv12() || h->yuv422()))
+        return fail(BEVW_E_INVALID, "analytic projection is not available with %s input", input_format_name(h->input_format));
     if (mode != BEVW_PROJ_LUT && h->out_nv12()) return fail(BEVW_E_INVALID, "analytic projection is not available with NV12 output");
     h->projection = mode;
     return BEVW_OK;
@@ -1527,13 +1550,16 @@ int bevw_output_pitch(bevw_handle *h)
 int bevw_set_input_format(bevw_handle *h, int format)
 {
     if (!h) return fail(BEVW_E_INVALID, "null handle");
-    if (format != BEVW_INPUT_BGR && format != BEVW_INPUT_NV12) return fail(BEVW_E_INVALID, "unknown input format %d", format);
-    if (format == BEVW_INPUT_NV12) {
+    if (!input_format_known(format)) return fail(BEVW_E_INVALID, "unknown input format %d", format);
+    if (format != BEVW_INPUT_BGR) {
         const bevw_config &c = h->cfg;
-        if (c.frame_width % 2 || c.frame_height % 2)
+        const char *name = input_format_name(format);
+        if (format == BEVW_INPUT_NV12 && (c.frame_width % 2 || c.frame_height % 2))
             return fail(BEVW_E_INVALID, "NV12 needs an even frame width and height, got %dx%d", c.frame_width, c.frame_height);
-        if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "NV12 input is not available with the analytic projection");
-        if (h->shard_n) return fail(BEVW_E_INVALID, "NV12 input is not available on camera-shard handles");
+        if (format != BEVW_INPUT_NV12 && c.frame_width % 2)   // (packed 4:2:2 shares chroma inside a row only: the height is free)
+            return fail(BEVW_E_INVALID, "%s needs an even frame width, got %dx%d", name, c.frame_width, c.frame_height);
+        if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "%s input is not available with the analytic projection", name);
+        if (h->shard_n) return fail(BEVW_E_INVALID, "%s input is not available on camera-shard handles", name);
     }
     BEVW_TRY(use_device(h->cfg.device));
     HIP_TRY(hipStreamSynchronize(h->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
@@ -1632,7 +1658,7 @@ static int need_surfaces(bevw_handle *h, const void *table, int batch, void *d_o
 {
     BEVW_TRY(need_built(h));
     if (h->shard_n) return fail(BEVW_E_INVALID, "NV12 surfaces are not available on camera-shard handles");
-    if (!h->nv12()) return fail(BEVW_E_INVALID, "surfaces are NV12: the handle's input format is BGR (bevw_set_input_format)");
+    if (!h->nv12()) return fail(BEVW_E_INVALID, "surfaces are NV12: the handle's input format is %s (bevw_set_input_format)", input_format_name(h->input_format));
     if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "NV12 surfaces are not available with the analytic projection");
     if (h->in_pitch() % 4 != 0)   // (a frame width that is even but not a multiple of 4: the default pitch, FRAME_WIDTH, does not serve)
         return fail(BEVW_E_INVALID, "FRAME_WIDTH %d is not a multiple of 4: surfaces need an input pitch that is (bevw_set_input_pitch)", h->cfg.frame_width);
@@ -1719,7 +1745,7 @@ static int camera_remap(bevw_handle *h, const uint8_t *src, int sw, int sh, cons
     BEVW_TRY(h->in.reserve(nin));
     BEVW_TRY(h->out.reserve(nout));
     HIP_TRY(hipMemcpyAsync(h->in.p, src, nin, hipMemcpyHostToDevice, h->stream));
-    const FrameSource frames{h->in.as<uint8_t>(), nullptr, 0, false, 1};   // BGR images, one by one
+    const FrameSource frames{h->in.as<uint8_t>(), nullptr, 0, SrcFormat::BGR, 1};   // BGR images, one by one
     BEVW_TRY(remap_launch(h->stream, frames, sw, sh, m1, m2, dw, dh, batch, h->out.as<uint8_t>(), h->compat[BEVW_COMPAT_REMAP], false));
     HIP_TRY(hipMemcpyAsync(dst, h->out.p, nout, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1766,7 +1792,7 @@ int bevw_set_camera_shard(bevw_handle *h, const int32_t *cams, int ncams)
         if (cams[k] < 0 || cams[k] > 3) return fail(BEVW_E_INVALID, "name should be front/back/left/right");
         if (k && cams[k] <= cams[k - 1]) return fail(BEVW_E_INVALID, "shard cameras must be distinct and ascending");
     }
-    if (h->nv12()) return fail(BEVW_E_INVALID, "camera-shard handles take BGR frames only (NV12 input is set)");
+    if (h->input_format != BEVW_INPUT_BGR) return fail(BEVW_E_INVALID, "camera-shard handles take BGR frames only (%s input is set)", input_format_name(h->input_format));
     if (h->out_nv12()) return fail(BEVW_E_INVALID, "camera-shard handles write BGR images only (NV12 output is set)");
     h->shard_n = ncams;
     for (int k = 0; k < 4; ++k) h->shard_cams[k] = k < ncams ? cams[k] : cams[0];

@@ -7,7 +7,7 @@ namespace bevw {
 
 void plan_release(Plan &p)
 {
-    void *ptrs[] = {p.un_desc, p.un_entries, p.un_gsrc, p.un_gsrc_compact, p.un_gsrc_nv12, p.list_un_all, p.entries, p.hdr, p.groups, p.groups_nv12, p.un_gsrc_surf, p.groups_surf, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
+    void *ptrs[] = {p.un_desc, p.un_entries, p.un_gsrc, p.un_gsrc_compact, p.un_gsrc_nv12, p.list_un_all, p.entries, p.hdr, p.groups, p.groups_nv12, p.un_gsrc_surf, p.groups_surf, p.un_gsrc_yuv422, p.groups_yuv422, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     p = Plan();
@@ -80,9 +80,13 @@ int plan_stitch(Plan &p, hipStream_t st, const PlanStep &step)
     return BEVW_OK;
 }
 
-int plan_set_format(Plan &p, bool nv12, bool out_nv12, int src_pitch)
+int plan_set_format(Plan &p, SrcFormat fmt, bool out_nv12, int src_pitch)
 {
-    p.nv12 = nv12; p.out_nv12 = out_nv12;
+    p.fmt = fmt; p.out_nv12 = out_nv12;
+    if (p.yuv422()) {
+        hipError_t e = plan_yuv422_impl(p);
+        if (e != hipSuccess) return fail(BEVW_E_HIP, "uploading the 4:2:2 group lists failed: %s", hipGetErrorString(e));
+    }
     if (src_pitch == p.src_pitch) return BEVW_OK;   // (the group lists are the ones of this pitch; none after plan_build, for pitch 0)
     p.src_pitch = src_pitch;
     hipError_t e = plan_src_pitch_impl(p, src_pitch);

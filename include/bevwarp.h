@@ -170,12 +170,25 @@ int bevw_output_pitch(bevw_handle *h);   /* pixels per row of the handle's devic
  *   - together with BEVW_PROJ_ANALYTIC / BEVW_PROJ_ANALYTIC_F32 (in either order);
  *   - on camera-shard handles (in either order with bevw_set_camera_shard).
  * Decoder surfaces (a row pitch, every frame at an address of its own): bevw_set_input_pitch / bevw_run_surfaces_device below.
- * Not provided: BT.709 or full-range matrices, NV21, I420, YUYV / UYVY, a standalone converter.
- * The per-camera tools (bevw_camera_undistort, ...) and the JPEG entry points keep taking BGR. */
+ * Not provided: BT.709 or full-range matrices, NV21, I420, a standalone converter.
+ * The per-camera tools (bevw_camera_undistort, ...) and the JPEG entry points keep taking BGR.
+ *
+ * Camera frames as packed 4:2:2 (what a live camera hands over uncompressed: UVC / V4L2 cameras deliver YUYV, "YUY2"; SerDes cameras --
+ * GMSL, FPD-Link -- deliver UYVY; the reference opens such cameras through cv2.VideoCapture, whose backend converts on the host): FH rows
+ * of FW / 2 texel pairs of 4 bytes, Y0 U Y1 V (BEVW_INPUT_YUYV) or U Y0 V Y1 (BEVW_INPUT_UYVY), dense -- FW * FH * 2 bytes per frame, a
+ * host array of shape (FH, FW, 2), the array cv2.cvtColor takes.  Frame sets and batches as for BGR.  Texel (x, y) takes Y from its own two
+ * bytes and U, V from the pair x / 2 of its own row (no vertical sharing); the arithmetic is NV12's.  With one of these formats the entry
+ * points above return, byte for byte, what the BGR handle returns for [cv2.cvtColor(f, cv2.COLOR_YUV2BGR_YUY2) for f in frames]
+ * (BEVW_INPUT_UYVY: cv2.COLOR_YUV2BGR_UYVY), with either output format.  Refused with BEVW_E_INVALID: an odd FW (FH is free); the analytic
+ * projection and camera-shard handles, in either order, as for NV12; an input pitch and the surface entry points (surfaces stay NV12).
+ * Not provided: YVYU, planar 4:2:2, BT.709 or full range, 4:2:2 surfaces with a row pitch or per-camera pointers, 4:2:2 output.
+ * Values 2 and 3 are not formats (BEVW_E_INVALID). */
 #define BEVW_INPUT_BGR 0
 #define BEVW_INPUT_NV12 1
+#define BEVW_INPUT_YUYV 4
+#define BEVW_INPUT_UYVY 5
 int bevw_set_input_format(bevw_handle *h, int format);
-int bevw_input_format(bevw_handle *h);   /* BEVW_INPUT_BGR or BEVW_INPUT_NV12 */
+int bevw_input_format(bevw_handle *h);   /* BEVW_INPUT_BGR, BEVW_INPUT_NV12, BEVW_INPUT_YUYV or BEVW_INPUT_UYVY */
 /* NV12 decoder surfaces, read where they lie.  Four cameras are four decode sessions, each with its own pool of surfaces: a surface has a
  * row pitch (padded to an alignment of the decoder's choosing), its U / V plane need not follow its Y plane, and the four frames of a frame
  * set live at four unrelated addresses.  A surface is a pair of DEVICE pointers; a table holds one per (frame set, camera), camera order
@@ -230,7 +243,7 @@ int bevw_run_surface_table_device(bevw_handle *h, const void *d_surfaces, int ba
  *   - an odd BW or BH;
  *   - together with BEVW_PROJ_ANALYTIC / BEVW_PROJ_ANALYTIC_F32 (in either order);
  *   - on camera-shard handles (in either order with bevw_set_camera_shard), and by bevw_combine_device.
- * Not provided: I420, NV21, YUYV, BT.709 or full range, averaged chroma, separate plane pointers, JPEG encoding from NV12.  The per-camera
+ * Not provided: I420, NV21, packed 4:2:2 output, BT.709 or full range, averaged chroma, separate plane pointers, JPEG encoding from NV12.  The per-camera
  * tools (bevw_camera_undistort, ...) keep writing BGR. */
 #define BEVW_OUTPUT_BGR 0
 #define BEVW_OUTPUT_NV12 1
@@ -342,7 +355,9 @@ int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst);
 int bevw_remap_device(bevw_remapper *r, const void *d_src, int batch, void *d_dst);
 /* BEVW_INPUT_NV12 (bevw_set_input_format has the layout and the arithmetic): bevw_remap and bevw_remap_device read src as
  * [batch][src_h*3/2][src_w] NV12 frames and write what cv2.remap writes for cv2.cvtColor(src, cv2.COLOR_YUV2BGR_NV12), in either
- * BEVW_COMPAT_REMAP mode.  Refused (BEVW_E_INVALID) for an odd src_w or src_h. */
+ * BEVW_COMPAT_REMAP mode.  Refused (BEVW_E_INVALID) for an odd src_w or src_h.
+ * BEVW_INPUT_YUYV / BEVW_INPUT_UYVY: src is [batch][src_h][src_w][2] packed 4:2:2 frames, the result what cv2.remap writes for
+ * cv2.cvtColor(src, cv2.COLOR_YUV2BGR_YUY2 / cv2.COLOR_YUV2BGR_UYVY); refused for an odd src_w, and with an input pitch or surfaces. */
 int bevw_remapper_set_input_format(bevw_remapper *r, int format);
 /* NV12 surfaces as sources (bevw_set_input_pitch has the contract): one pitch for the remapper, `surfaces` a HOST array [batch] of plane
  * pairs, copied before the call returns; bevw_remap_surface_table_device takes the same table already in DEVICE memory (8-byte aligned; its
