@@ -687,11 +687,14 @@ class BevGenerator:
         return float(ms.value)
 
     def plan_info(self) -> dict:
+        """The plan of the handle.  ``analytic_tiles_left`` (analytic projections; 0 on table handles): base tiles the wide unit plan
+        leaves to the per-pixel analytic kernel, or -1 when no wide unit plan is in use -- balance handles, odd geometry, units
+        switched off -- or none has been compiled yet (the first run compiles it)."""
         info = np.zeros(8, np.int32)
         check(lib().bevw_plan_info(self._engine.h, ptr(info)))
         return {"max_contributors": int(info[0]), "plan_usable": bool(info[1]), "schedule": int(info[2]),
                 "tiles_x": int(info[3]), "tiles_y": int(info[4]), "tiles_staged": int(info[5]),
-                "tiles_gather": int(info[6]), "tiles_border": int(info[7])}
+                "tiles_gather": 0, "analytic_tiles_left": int(info[6]), "tiles_border": int(info[7])}
 
 
 def main():

@@ -439,8 +439,9 @@ struct AnalyticRig {
     float fMinv[4][9], ffx[4], ffy[4], fcx[4], fcy[4], fd[4][4], finv_nfx[4], finv_nfy[4], fncx[4], fncy[4];
 };
 
-// F = double: the specification's arithmetic (oracle/np_analytic.py).  F = float: the same formulas in fp32 (atanf, sqrtf; positions good
-// to ~1e-4 pixel), faster; held against the fp64 result by PSNR, not byte for byte.
+// F = double: the specification's arithmetic (oracle/np_analytic.py).  F = float: the same formulas in fp32 (atanf, sqrtf; raw-frame
+// positions within 2.5e-3 pixel of the fp64 ones and undistorted positions within 4.8e-3 on the sample rig, 1.2e-3 / 4.1e-3 on the small
+// test rigs: tests/_analytic_common.py f32_position_error), faster; held against the fp64 result by PSNR, not byte for byte.
 template <typename F>
 struct AnalyticTap { int sx, sy; F ax, ay; };   // raw-frame footprint of one (pixel, camera): top-left texel and the fractions
 

@@ -1524,7 +1524,9 @@ int bevw_plan_info(bevw_handle *h, int32_t info[8])
     info[3] = h->plan.tiles_x;
     info[4] = h->plan.tiles_y;
     info[5] = h->plan.n_unit_tiles;   // base tiles on the unit schedule (bevw_unit.h)
-    info[6] = 0;                      // (rounds 1 - 3: tiles on the L1-gather kernels; retired)
+    // analytic modes: base tiles the wide unit plan leaves to k_stitch_analytic; -1: no wide unit plan in use (or none compiled yet: the
+    // first run compiles it).  Table handles: 0 (rounds 1 - 3: tiles on the L1-gather kernels; retired)
+    if (h->projection != BEVW_PROJ_LUT) info[6] = (h->aplan_mode == h->projection && h->aplan.n_un_all) ? h->aplan.n_slow : -1;
     info[7] = h->plan.n_slow;
     return BEVW_OK;
 }

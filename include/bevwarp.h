@@ -137,9 +137,14 @@ int bevw_get_mask(bevw_handle *h, int cam, uint8_t *mask);  /* Mask.mask / Blend
  * are unchanged.  Call before or after bevw_build; not available on camera-shard handles or with an output pitch. */
 #define BEVW_PROJ_LUT 0
 #define BEVW_PROJ_ANALYTIC 1       /* fp64 projection: equals its NumPy specification (oracle/np_analytic.py) to <= 1 LSB, >= 99.9 % of the bytes */
-#define BEVW_PROJ_ANALYTIC_F32 2   /* the same formulas in fp32 (positions good to ~1e-4 pixel): held against the fp64 mode by PSNR */
+#define BEVW_PROJ_ANALYTIC_F32 2   /* the same formulas in fp32 (measured on the sample rig: raw-frame positions within ~3e-3 pixel of the fp64 ones, undistorted positions within ~5e-3): held against the fp64 mode by PSNR */
 int bevw_set_projection(bevw_handle *h, int mode);
-int bevw_plan_info(bevw_handle *h, int32_t info[8]);        /* [0] max contributors/pixel, [1] plan usable, [2] schedule in use */
+/* info: [0] max contributors/pixel, [1] plan usable, [2] schedule in use, [3] [4] base tiles along x / y, [5] base tiles on the unit
+ * schedule, [7] base tiles left to the per-tap kernel -- all of the table plan.  [6]: 0 on table handles; in an analytic mode the
+ * number of base tiles the wide unit plan leaves to the per-pixel analytic kernel (frame-border footprints), or -1 when no wide unit
+ * plan is in use (balance handles, BEV or frame widths that are not a multiple of 4, units switched off) or none has been compiled
+ * yet -- the first bevw_run* of a handle in the mode compiles it. */
+int bevw_plan_info(bevw_handle *h, int32_t info[8]);
 
 /* ---- BevGenerator.__call__ (surroundBEV.py:312-325) ------------------------------------------------------ */
 /* frames: [batch][4][FH][FW][3]; car: [BH][BW][3] or NULL (already padded, surroundBEV.py:28-41); out: [batch][BH][BW][3] */

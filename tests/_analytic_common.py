@@ -1,0 +1,212 @@
+"""Shared by tests/test_analytic.py (CPU conditions), tests/test_analytic_gpu.py and its worker: the rigs, the frames, the cached
+specifications (oracle/np_analytic.py) and the bars the HIP analytic modes are held to.  Everything here runs on the CPU.
+
+Bars (HIP against AnalyticBevGenerator, per image):
+  fp64, no balance   every byte within 1 LSB, >= 99.9 % identical (include/bevwarp.h: BEVW_PROJ_ANALYTIC).
+  fp64, balance      the pre-gain images are within 1 LSB, so the bytes after the gain are within ceil(kmax), kmax the largest gain of
+                     the frame set; share of identical bytes >= 1 - 2 * BALANCE_FLIP_SHARE (measured below: a +-1 disturbance of 0.1 %
+                     of the covered pre-gain bytes changes that share of the balanced image; the factor 2 because HIP's differences
+                     are not independent of the image content).
+  fp32               outside the edge band (np_analytic.edge_band at F32_EPS): <= 2 LSB, > 97 % identical, PSNR > 55 dB (the bars of
+                     tests/test_analytic.py); inside it nothing is bounded, but the band holds <= BAND_CAP of any camera's masked,
+                     valid pixels.
+Measured values (test_analytic.py prints them and asserts they have not moved past the recorded ones):
+  F32_POSITION_ERROR 4.06e-3 pixel: largest |u, v, px, py| difference of a NumPy float32 evaluation of the projection from the
+                     fp64 one over the masked pixels of the small and the shifted rig (u, v: 4.06e-3 / 2.43e-3; px, py: 1.17e-3 /
+                     6.6e-4; the small rig alone 8.5e-4).  F32_EPS is 4 x that: the kernel's 1-ulp reciprocal and square root.
+  BALANCE_FLIP_SHARE 3.93e-3: the worst of 12 pre-gain specification images (small and shifted rig, blend off / on, the three cast
+                     frame sets of make_frames) x 10 seeds x the three disturbances; largest change 2 LSB.  Most images give 6e-4 ... 9e-4
+                     (the disturbed bytes themselves); where the disturbance moves a gain across a rounding tie of one of the 3 x 256
+                     (channel, value) products, every byte of that value flips: 1.9e-3 ... 3.9e-3.
+"""
+import os
+import sys
+
+import numpy as np
+
+from cameracalibration_amd import workloads as W
+from oracle import np_analytic, oracle as O
+
+TESTS = os.path.dirname(os.path.abspath(__file__))
+if TESTS not in sys.path:
+    sys.path.insert(0, TESTS)
+from test_gpu_parity import SMALL_CFG, small_rig  # noqa: E402
+
+F32_POSITION_ERROR = 4.1e-3      # measured 4.06e-3 (see above)
+F32_EPS = 4 * F32_POSITION_ERROR
+BAND_CAP = 0.005
+BALANCE_FLIP_SHARE = 4.0e-3      # measured 3.93e-3 (see above): the balance bar is 1 - 2 x this = 99.2 % identical bytes
+
+
+def shifted_rig():
+    """the rig of test_lut_border_entries_are_exercised: K scaled by 0.55 at the principal point, the BEV shifted by (-90, +60) --
+    partial footprints on the frame border, whole-footprint misses, pixels outside the undistorted image"""
+    shift = np.array([[1.0, 0, -90.0], [0, 1.0, 60.0], [0, 0, 1.0]])
+    return {n: (K * [[1.0, 1, 0.55], [1, 1.0, 0.55], [1, 1, 1]], D, shift @ H) for n, (K, D, H) in small_rig().items()}
+
+
+RIGS = {"small": small_rig, "shifted": shifted_rig}
+
+
+def make_frames(n, cfg=SMALL_CFG, seed=13, cast=False):
+    """random frames, camera 1 at half brightness (non-trivial luminance deltas); cast: B channel x 3/4, so that the gains are far
+    from 1 (about 1.23, 0.91, 0.91) and a wrong channel sum shows"""
+    fr = W.synthetic_frames(n, cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"], seed=seed, kind="random")
+    fr[:, 1] //= 2
+    if cast:
+        fr[..., 0] = (fr[..., 0].astype(np.uint16) * 3 // 4).astype(np.uint8)
+    return fr
+
+
+def make_car(cfg=SMALL_CFG, seed=3):
+    """a random sprite on the car rectangle, padded to the BEV"""
+    bw, bh, cw, ch = cfg["BEV_WIDTH"], cfg["BEV_HEIGHT"], cfg["CAR_WIDTH"], cfg["CAR_HEIGHT"]
+    car = np.zeros((bh, bw, 3), np.uint8)
+    t, l = (bh - ch) // 2, (bw - cw) // 2
+    car[t:t + ch, l:l + cw] = np.random.default_rng(seed).integers(0, 256, (ch, cw, 3), dtype=np.uint8)
+    return car
+
+
+_specs = {}
+
+
+def spec(rig, cfg=SMALL_CFG, blend=False, balance=False):
+    """AnalyticBevGenerator of a named rig, built once per (rig, cfg, blend)"""
+    O.build()
+    key = (rig, tuple(sorted(cfg.items())), bool(blend))
+    if key not in _specs:
+        _specs[key] = np_analytic.AnalyticBevGenerator(RIGS[rig](), cfg, blend=blend)
+    return _specs[key].with_balance(balance)
+
+
+def masks(cfg, blend):
+    geo = (cfg["BEV_WIDTH"], cfg["BEV_HEIGHT"], cfg["CAR_WIDTH"], cfg["CAR_HEIGHT"])
+    return [(O.blend_mask_for(n, *geo) if blend else O.direct_mask(n, *geo)) != 0 for n in O.CAMERAS]
+
+
+def footprint_census(rig, cfg=SMALL_CFG, blend=False):
+    """per camera: masked pixels with a partial footprint / masked pixels that sample nothing"""
+    O.build()
+    r, out = RIGS[rig](), []
+    for n, m in zip(O.CAMERAS, masks(cfg, blend)):
+        px, py, valid = np_analytic.project(*r[n], cfg)
+        out.append((int((np_analytic.partial_footprints(px, py, valid, cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"]) & m).sum()),
+                    int((m & ~valid).sum())))
+    return out
+
+
+def band(rig, cfg=SMALL_CFG, blend=False, eps=F32_EPS):
+    """(pixels of any camera's edge band [BH, BW], the largest share of a camera's masked, valid pixels its band holds)"""
+    O.build()
+    r = RIGS[rig]()
+    any_band, worst = np.zeros((cfg["BEV_HEIGHT"], cfg["BEV_WIDTH"]), bool), 0.0
+    for n, m in zip(O.CAMERAS, masks(cfg, blend)):
+        b = np_analytic.edge_band(*r[n], cfg, eps) & m
+        valid = np_analytic.project(*r[n], cfg)[2] & m
+        any_band |= b
+        worst = max(worst, b.sum() / max(1, int(valid.sum())))
+    return any_band, worst
+
+
+def f32_position_error(rig, cfg=SMALL_CFG):
+    """largest |u, v| and |px, py| difference of the float32 evaluation from the float64 one, and the number of masked pixels whose
+    validity the float32 evaluation decides the other way.  u, v over the masked pixels within a pixel of the undistorted image, px, py over the
+    masked, valid ones (blend masks: the larger ones)."""
+    O.build()
+    r = RIGS[rig]()
+    fw, fh, ss = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"], cfg["SIZE_SCALE"]
+    uw, uh = int(fw * ss), int(fh * ss)
+    e_uv = e_p = 0.0
+    flips = 0
+    for n, m in zip(O.CAMERAS, masks(cfg, True)):
+        u, v, px, py, wd = np_analytic.positions(*r[n], cfg)
+        u32, v32, px32, py32, wd32 = (a.astype(np.float64) for a in np_analytic.positions(*r[n], cfg, np.float32))
+        with np.errstate(invalid="ignore"):
+            near = m & (u >= -1) & (u <= uw) & (v >= -1) & (v <= uh)
+            valid = (wd != 0) & (u >= 0) & (u <= uw - 1) & (v >= 0) & (v <= uh - 1) & (px > -1) & (px < fw) & (py > -1) & (py < fh)
+            valid32 = (wd32 != 0) & (u32 >= 0) & (u32 <= uw - 1) & (v32 >= 0) & (v32 <= uh - 1) & (px32 > -1) & (px32 < fw) & (py32 > -1) & (py32 < fh)
+        if near.any():
+            e_uv = max(e_uv, float(np.abs(u32 - u)[near].max()), float(np.abs(v32 - v)[near].max()))
+        if (m & valid).any():
+            e_p = max(e_p, float(np.abs(px32 - px)[m & valid].max()), float(np.abs(py32 - py)[m & valid].max()))
+        flips += int((m & (valid != valid32)).sum())
+    return e_uv, e_p, flips
+
+
+def balance_flip_share(pre, seeds=10):
+    """(worst share of bytes of color_balance(pre) that change, largest change) when `pre` -- a pre-gain specification image -- is
+    disturbed the way a HIP pre-gain image may differ from it: 0.1 % of its covered bytes moved by +1, by -1, or by +-1"""
+    covered = np.flatnonzero(np.repeat(pre.max(axis=2) > 0, 3))
+    want = O.color_balance(pre).astype(np.int32)
+    worst, big = 0.0, 0
+    for seed in range(seeds):
+        rng = np.random.default_rng(seed)
+        at = rng.choice(covered, max(1, covered.size // 1000), replace=False)
+        for step in (np.ones(at.size, np.int32), -np.ones(at.size, np.int32), rng.choice(np.array([-1, 1], np.int32), at.size)):
+            p = pre.astype(np.int32).ravel()
+            p[at] = np.clip(p[at] + step, 0, 255)
+            d = np.abs(O.color_balance(p.astype(np.uint8).reshape(pre.shape)).astype(np.int32) - want)
+            worst, big = max(worst, float((d != 0).mean())), max(big, int(d.max()))
+    return worst, big
+
+
+def stitch_filled(ffi, bev, frames, car):
+    """bev.batch(frames, car) through run_device into an output buffer filled with 0x5A first, a guard of 64 bytes behind the images: a
+    pixel the kernels skip shows the fill (never what an earlier run left in the handle's own buffers), the guard stays untouched"""
+    batch, c = frames.shape[0], bev._engine.cfg
+    nbytes = batch * c.bev_height * c.bev_width * 3
+    bufs = [ffi.DeviceBuffer(frames.nbytes), ffi.DeviceBuffer(nbytes + 64)]
+    try:
+        bufs[0].upload(frames)
+        if car is not None:
+            bufs.append(ffi.DeviceBuffer(car.nbytes).upload(car))
+        bufs[1].fill(0x5A)
+        bev.run_device(bufs[0].ptr, batch, bufs[2].ptr if car is not None else None, bufs[1].ptr, out_bytes=nbytes)
+        bev.sync()
+        raw = bufs[1].download((nbytes + 64,))
+    finally:
+        for b in bufs:
+            b.free()
+    assert (raw[nbytes:] == 0x5A).all(), "bytes behind the images were written"
+    return raw[:nbytes].reshape(batch, c.bev_height, c.bev_width, 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the bars
+# ---------------------------------------------------------------------------------------------------------------
+def diff(got, want):
+    return np.abs(got.astype(np.int32) - want.astype(np.int32))
+
+
+def check_f64(got, want, what=""):
+    d = diff(got, want)
+    assert got.shape == want.shape, what
+    assert d.max() <= 1, "%s: max %d LSB at %s" % (what, int(d.max()), np.argwhere(d == d.max())[0].tolist())
+    assert (d == 0).mean() >= 0.999, "%s: %.4f %% identical" % (what, 100 * float((d == 0).mean()))
+
+
+def check_balance(got, want, kmax, what=""):
+    d = diff(got, want)
+    assert got.shape == want.shape, what
+    assert kmax > 1.15, "%s: the largest gain %.3f is too close to 1 for the bound to tell anything" % (what, kmax)
+    assert d.max() <= int(np.ceil(kmax)), "%s: max %d LSB (kmax %.3f) at %s" % (what, int(d.max()), kmax, np.argwhere(d == d.max())[0].tolist())
+    # BALANCE_FLIP_SHARE: measured on the CPU (test_balance_flip_share_is_the_recorded_one)
+    assert (d == 0).mean() >= 1 - 2 * BALANCE_FLIP_SHARE, "%s: %.4f %% identical" % (what, 100 * float((d == 0).mean()))
+
+
+def psnr(a, b, sel=None):
+    d = (a.astype(np.float64) - b.astype(np.float64)) ** 2
+    if sel is not None:
+        d = d[sel]
+    m = d.mean()
+    return 99.0 if m == 0 else 10.0 * np.log10(255.0 ** 2 / m)
+
+
+def check_f32(got, want, band_px, what=""):
+    """outside the edge band: the fp32 bars of tests/test_analytic.py"""
+    keep = ~band_px
+    d = diff(got, want)[keep]
+    p = psnr(got, want, keep)
+    print("%s: fp32 vs fp64 specification outside the band (%d px inside): PSNR %.1f dB, %.2f %% identical, max %d LSB" % (
+        what, int(band_px.sum()), p, 100 * float((d == 0).mean()), int(d.max())))
+    assert d.max() <= 2 and (d == 0).mean() > 0.97 and p > 55.0, (what, int(d.max()), float((d == 0).mean()), p)

@@ -1,0 +1,300 @@
+"""Every kernel path of the analytic projection (stitch_analytic in csrc/bevwarp.hip) against its specification, oracle/np_analytic.py:
+
+  1. the wide unit plan (k_plan_unit_wide)                         -- plan_info()["analytic_tiles_left"] >= 0
+  2. k_stitch_analytic on the tiles the wide plan leaves over       -- ... > 0: frame-border footprints (the shifted rig)
+  3. k_stitch_analytic on the full grid                             -- ... == -1: balance, BW % 4, FW % 4, misaligned buffers, units off
+     byte stores (BW % 4, a misaligned output), per-byte fetches (frames that are no dword multiple, misaligned frames), the balance
+     branch (per-tap luminance shift, per-block channel sums), runtime chunk sizes fpt of 1 and 5 with a partial last chunk
+  4. k_stitch_perpixel (BEVW_ANALYTIC_FRAMES=1, units off)           -- its frame-border branch, in fp64
+
+Every comparison is HIP against AnalyticBevGenerator at the bars of tests/_analytic_common.py -- fp64: <= 1 LSB, >= 99.9 % of the bytes
+identical per image; balance: <= ceil(largest gain) LSB, >= 1 - 2 x 0.40 % = 99.2 % identical (BALANCE_FLIP_SHARE, measured 3.93e-3 on
+the CPU: tests/test_analytic.py); fp32: the bars of tests/test_analytic.py outside an edge band of 4 x the measured fp32 position error
+(4.06e-3 pixel).  Each path-specific test asserts through plan_info() that the path it names was taken.  Frames: 320 x 256, random,
+camera 1 at half brightness, for balance with a colour cast (gains about 1.23, 0.91, 0.91); BEV 248 x 250; batches of at most 7.
+The switches BEVW_ANALYTIC_UNITS / BEVW_ANALYTIC_FRAMES are read once per process: those cases run in a child (tests/_analytic_worker.py).
+"""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import _analytic_common as AC
+from _analytic_common import SMALL_CFG
+from test_gpu_parity import random_rig_case, set_args
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SWITCHES = ("BEVW_ANALYTIC_UNITS", "BEVW_ANALYTIC_FRAMES")
+CHILD_TIMEOUT = 120
+
+
+@pytest.fixture(scope="module")
+def ffi():
+    from cameracalibration_amd import _ffi
+
+    _ffi.require_device()
+    assert not [k for k in SWITCHES if k in os.environ], "the in-process tests need the library's default switches"
+    return _ffi
+
+
+@pytest.fixture(scope="module")
+def SB():
+    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV
+
+    return surroundBEV
+
+
+def generator(SB, rig, cfg, blend, balance=False, projection="analytic"):
+    set_args(SB, cfg)
+    return SB.BevGenerator(blend=blend, balance=balance, rig=AC.RIGS[rig](), projection=projection)
+
+
+def tiles_left(bev):
+    return bev.plan_info()["analytic_tiles_left"]
+
+
+def check_batch(got, gen, frames, car, balance, what):
+    """every image of a batch against the specification of its own frame set"""
+    assert got.shape[0] == frames.shape[0]
+    for b in range(frames.shape[0]):
+        want = gen(*frames[b], car)
+        if balance:
+            AC.check_balance(got[b], want, float(gen.gains(*frames[b]).max()), "%s, image %d" % (what, b))
+        else:
+            AC.check_f64(got[b], want, "%s, image %d" % (what, b))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 3. the full-grid kernel, in process
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("with_car", [False, True])
+@pytest.mark.parametrize("blend", [False, True])
+@pytest.mark.parametrize("bw", [250, 249])
+def test_bev_width_not_a_multiple_of_4_full_grid_byte_stores(ffi, SB, oracle, bw, blend, with_car):
+    """BW % 4 != 0: no unit plan, k_stitch_analytic on the full grid with one byte store per channel (quad_store false); on the small rig
+    and on the shifted one (border footprints through the same kernel)"""
+    cfg = dict(SMALL_CFG, BEV_WIDTH=bw, BEV_HEIGHT=251)
+    frames = AC.make_frames(3)
+    car = AC.make_car(cfg) if with_car else None
+    for rig in ("small", "shifted"):
+        bev = generator(SB, rig, cfg, blend)
+        assert tiles_left(bev) == -1
+        got = bev.batch(frames, car)
+        assert tiles_left(bev) == -1
+        check_batch(got, AC.spec(rig, cfg, blend), frames, car, False, "BW %d, %s rig" % (bw, rig))
+
+
+@pytest.mark.parametrize("blend", [False, True])
+def test_frame_width_not_a_multiple_of_4_switches_the_units_off(ffi, SB, oracle, blend):
+    """FW = 322: frames are still dword multiples (window loads, 12-byte stores), but the unit plan is not built"""
+    cfg = dict(SMALL_CFG, FRAME_WIDTH=322)
+    frames, car = AC.make_frames(3, cfg), AC.make_car(cfg)
+    bev = generator(SB, "shifted", cfg, blend)
+    got = bev.batch(frames, car)
+    assert tiles_left(bev) == -1
+    check_batch(got, AC.spec("shifted", cfg, blend), frames, car, False, "FW 322")
+
+
+@pytest.mark.parametrize("blend", [False, True])
+def test_frames_that_are_not_dword_multiples_are_fetched_per_byte(ffi, SB, oracle, blend):
+    """321 x 255 x 3 bytes per frame: frames of a set start off 4-byte boundaries, analytic_sample fetches byte by byte (aligned false)"""
+    cfg = dict(SMALL_CFG, FRAME_WIDTH=321, FRAME_HEIGHT=255)
+    frames, car = AC.make_frames(3, cfg), AC.make_car(cfg)
+    for rig in ("small", "shifted"):
+        bev = generator(SB, rig, cfg, blend)
+        got = bev.batch(frames, car)
+        assert tiles_left(bev) == -1
+        check_batch(got, AC.spec(rig, cfg, blend), frames, car, False, "321 x 255 frames, %s rig" % rig)
+
+
+@pytest.mark.parametrize("which", ["frames", "out", "car"])
+def test_misaligned_device_buffers_take_the_full_grid_kernel(ffi, SB, oracle, which):
+    """run_device with d_frames, d_out or d_car 1 to 3 bytes off a 4-byte boundary (BW = 248: only the pointer keeps the units away): the
+    handle never compiles a unit plan, every image is the specification's, the bytes around the images stay untouched"""
+    cfg, blend, batch = SMALL_CFG, True, 3
+    bw, bh = cfg["BEV_WIDTH"], cfg["BEV_HEIGHT"]
+    frames, car = AC.make_frames(batch), AC.make_car(cfg)
+    gen = AC.spec("shifted", cfg, blend)
+    want = [gen(*frames[b], car) for b in range(batch)]
+    bev = generator(SB, "shifted", cfg, blend)
+    d_in, d_car, d_out = ffi.DeviceBuffer(frames.nbytes + 4), ffi.DeviceBuffer(car.nbytes + 4), ffi.DeviceBuffer(batch * bw * bh * 3 + 4)
+    try:
+        for off in (1, 2, 3):
+            o_in, o_out, o_car = (off if which == w else 0 for w in ("frames", "out", "car"))
+            d_in.upload(frames, offset=o_in)
+            d_car.upload(car, offset=o_car)
+            d_out.fill(0x5A)
+            bev.run_device(d_in.ptr + o_in, batch, d_car.ptr + o_car, d_out.ptr + o_out, out_bytes=batch * bw * bh * 3)
+            bev.sync()
+            assert tiles_left(bev) == -1, "a unit plan was compiled"
+            raw = d_out.download((d_out.nbytes,))
+            assert (raw[:o_out] == 0x5A).all() and (raw[o_out + batch * bw * bh * 3:] == 0x5A).all(), "bytes around the images were written"
+            got = raw[o_out:o_out + batch * bw * bh * 3].reshape(batch, bh, bw, 3)
+            for b in range(batch):
+                AC.check_f64(got[b], want[b], "%s + %d, image %d" % (which, off, b))
+    finally:
+        for d in (d_in, d_car, d_out):
+            d.free()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# 1. + 2. the wide unit plan and the tiles it leaves over
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("blend", [False, True])
+def test_border_footprints_are_left_to_the_per_pixel_kernel(ffi, SB, oracle, blend):
+    """the shifted rig on the default path: units in use and at least one base tile left over (frame-border footprints); the small rig
+    beside it: units in use, nothing left over"""
+    frames, car = AC.make_frames(3), AC.make_car()
+    left = {}
+    for rig in ("shifted", "small"):
+        bev = generator(SB, rig, SMALL_CFG, blend)
+        assert tiles_left(bev) == -1   # (nothing compiled before the first run)
+        got = AC.stitch_filled(ffi, bev, frames, car)   # (a tile nobody writes shows the fill)
+        left[rig] = tiles_left(bev)
+        check_batch(got, AC.spec(rig, SMALL_CFG, blend), frames, car, False, "%s rig, units" % rig)
+        check_batch(bev.batch(frames[:1]), AC.spec(rig, SMALL_CFG, blend), frames[:1], None, False, "%s rig, units, no car" % rig)
+    print("base tiles left to k_stitch_analytic:", left)
+    assert left["shifted"] >= 1 and left["small"] >= 0
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# balance
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("blend", [False, True])
+@pytest.mark.parametrize("rig", ["small", "shifted"])
+def test_balance_against_the_specification(ffi, SB, oracle, rig, blend):
+    """luminance balance per tap, channel sums per block, gains, car: three distinct frame sets with a colour cast in a batch of 3 (the last
+    set sits last in an odd batch), each image against the specification of its own set"""
+    frames, car = AC.make_frames(3, cast=True), AC.make_car()
+    bev = generator(SB, rig, SMALL_CFG, blend, balance=True)
+    got = AC.stitch_filled(ffi, bev, frames, car)
+    assert tiles_left(bev) == -1
+    check_batch(got, AC.spec(rig, SMALL_CFG, blend, balance=True), frames, car, True, "balance, %s rig" % rig)
+    # a single set, no car: the sums of one image alone
+    check_batch(bev.batch(frames[2:]), AC.spec(rig, SMALL_CFG, blend, balance=True), frames[2:], None, True, "balance, %s rig, one set" % rig)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# random rigs
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", range(12))
+def test_random_rigs_analytic(ffi, SB, oracle, seed):
+    """the geometry fuzz of test_random_rigs_modes_and_batches through the analytic projection: whatever path the sizes select"""
+    from oracle import np_analytic
+
+    c = random_rig_case(seed)
+    cfg, blend, balance, frames, car = c["cfg"], c["blend"], c["balance"], c["frames"], c["car"]
+    if balance:   # (the colour cast of make_frames: gains far from 1)
+        frames[..., 0] = (frames[..., 0].astype(np.uint16) * 3 // 4).astype(np.uint8)
+    set_args(SB, cfg)
+    bev = SB.BevGenerator(blend=blend, balance=balance, rig=c["rig"], projection="analytic")
+    got = bev.batch(frames, car)
+    units = not balance and cfg["BEV_WIDTH"] % 4 == 0 and cfg["FRAME_WIDTH"] % 4 == 0
+    print("seed %d: %s blend %d balance %d batch %d car %d -> tiles left %d" % (seed, cfg, blend, balance, c["batch"], car is not None, tiles_left(bev)))
+    assert units or tiles_left(bev) == -1
+    check_batch(got, np_analytic.AnalyticBevGenerator(c["rig"], cfg, blend=blend, balance=balance), frames, car, balance, "seed %d" % seed)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# fp32
+# ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("blend", [False, True])
+@pytest.mark.parametrize("bw", [248, 250])
+@pytest.mark.parametrize("rig", ["small", "shifted"])
+def test_f32_against_the_fp64_specification_outside_the_edge_band(ffi, SB, oracle, rig, bw, blend):
+    """analytic_f32 on the unit plan (BW 248) and on the full-grid kernel (BW 250): bounded outside the edge band, the band is small"""
+    cfg = dict(SMALL_CFG, BEV_WIDTH=bw)
+    frames, car = AC.make_frames(2), AC.make_car(cfg)
+    band_px, share = AC.band(rig, cfg, blend)
+    assert share <= AC.BAND_CAP
+    bev = generator(SB, rig, cfg, blend, projection="analytic_f32")
+    got = bev.batch(frames, car)
+    assert (tiles_left(bev) >= (1 if rig == "shifted" else 0)) if bw == 248 else tiles_left(bev) == -1
+    gen = AC.spec(rig, cfg, blend)
+    for b in range(2):
+        AC.check_f32(got[b], gen(*frames[b], car), band_px, "%s rig, BW %d, blend %d, image %d" % (rig, bw, blend, b))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the switches, one child each
+# ---------------------------------------------------------------------------------------------------------------
+def run_worker(tmp_path, env, jobs, frame_sets):
+    """-> {job name: (images, plan_info)} from a fresh process with `env` set"""
+    d = str(tmp_path)
+    for name, fr in frame_sets.items():
+        np.save(os.path.join(d, name), fr)
+    json.dump(jobs, open(os.path.join(d, "jobs.json"), "w"))
+    e = {k: v for k, v in os.environ.items() if k not in SWITCHES}
+    e.update(env)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_analytic_worker.py"), d], env=e, cwd=ROOT, capture_output=True, text=True,
+                       timeout=CHILD_TIMEOUT)
+    print(p.stdout)
+    assert p.returncode == 0 and "worker OK" in p.stdout, "worker exit %d\n%s\n%s" % (p.returncode, p.stdout[-4000:], p.stderr[-4000:])
+    info = json.load(open(os.path.join(d, "info.json")))
+    return {j["name"]: (np.load(os.path.join(d, "got_%s.npy" % j["name"])), info[j["name"]]) for j in jobs}
+
+
+def job(name, rig, blend, balance=False, frames="plain.npy", car=True, projection="analytic", cfg=SMALL_CFG):
+    return dict(name=name, rig=rig, cfg=cfg, blend=blend, balance=balance, projection=projection, frames=frames, car=car)
+
+
+def seven_of_three(sets):
+    """a batch of 7 from three distinct frame sets"""
+    return sets[[0, 1, 2, 0, 1, 2, 0]]
+
+
+def check_jobs(jobs, out, frame_sets):
+    for j in jobs:
+        got, _ = out[j["name"]]
+        frames = frame_sets[j["frames"]]
+        car = AC.make_car(j["cfg"]) if j["car"] else None
+        check_batch(got, AC.spec(j["rig"], j["cfg"], j["blend"], j["balance"]), frames, car, j["balance"], j["name"])
+
+
+def test_units_switched_off_full_grid_on_the_shifted_rig(ffi, oracle, tmp_path):
+    """BEVW_ANALYTIC_UNITS=0: border footprints, whole-footprint misses and interior pixels all through k_stitch_analytic on the full grid,
+    12-byte stores and window loads"""
+    sets = {"plain.npy": AC.make_frames(3)}
+    jobs = [job("units_off_direct", "shifted", False), job("units_off_blend", "shifted", True)]
+    out = run_worker(tmp_path, {"BEVW_ANALYTIC_UNITS": "0"}, jobs, sets)
+    assert all(info["analytic_tiles_left"] == -1 for _, info in out.values())
+    check_jobs(jobs, out, sets)
+
+
+def test_chunks_of_5_frames_with_a_partial_last_chunk(ffi, oracle, tmp_path):
+    """BEVW_ANALYTIC_FRAMES=5, batch 7 (chunks of 5 and 2), seven images from three distinct frame sets: the left-over tiles of the shifted rig
+    beside the units, and the balance kernel (channel sums of the partial chunk's frames)"""
+    sets = {"plain.npy": seven_of_three(AC.make_frames(3)), "cast.npy": seven_of_three(AC.make_frames(3, cast=True))}
+    jobs = [job("fpt5_left_tiles", "shifted", True), job("fpt5_balance", "shifted", True, balance=True, frames="cast.npy"),
+            job("fpt5_balance_direct", "small", False, balance=True, frames="cast.npy")]
+    out = run_worker(tmp_path, {"BEVW_ANALYTIC_FRAMES": "5"}, jobs, sets)
+    assert out["fpt5_left_tiles"][1]["analytic_tiles_left"] >= 1
+    assert out["fpt5_balance"][1]["analytic_tiles_left"] == -1 and out["fpt5_balance_direct"][1]["analytic_tiles_left"] == -1
+    check_jobs(jobs, out, sets)
+
+
+def test_one_frame_per_thread_with_balance_and_on_left_over_tiles(ffi, oracle, tmp_path):
+    """BEVW_ANALYTIC_FRAMES=1: k_stitch_analytic at fpt 1 -- the balance kernel (a block's sums of every frame on their own), and the
+    left-over tiles beside the units"""
+    sets = {"plain.npy": AC.make_frames(3), "cast.npy": AC.make_frames(3, cast=True)}
+    jobs = [job("fpt1_balance", "shifted", False, balance=True, frames="cast.npy"), job("fpt1_balance_blend", "small", True, balance=True, frames="cast.npy"),
+            job("fpt1_left_tiles", "shifted", False)]
+    out = run_worker(tmp_path, {"BEVW_ANALYTIC_FRAMES": "1"}, jobs, sets)
+    assert out["fpt1_left_tiles"][1]["analytic_tiles_left"] >= 1
+    assert out["fpt1_balance"][1]["analytic_tiles_left"] == -1 and out["fpt1_balance_blend"][1]["analytic_tiles_left"] == -1
+    check_jobs(jobs, out, sets)
+
+
+def test_per_pixel_kernel_fp64_on_the_shifted_rig(ffi, oracle, tmp_path):
+    """BEVW_ANALYTIC_FRAMES=1, BEVW_ANALYTIC_UNITS=0, no balance: k_stitch_perpixel, whose frame-border branch only the shifted rig reaches;
+    fp64 at the fp64 bar, seven images from three distinct frame sets, with and without the car"""
+    sets = {"plain.npy": seven_of_three(AC.make_frames(3))}
+    jobs = [job("perpixel_direct", "shifted", False), job("perpixel_blend", "shifted", True, car=False)]
+    out = run_worker(tmp_path, {"BEVW_ANALYTIC_FRAMES": "1", "BEVW_ANALYTIC_UNITS": "0"}, jobs, sets)
+    assert all(info["analytic_tiles_left"] == -1 for _, info in out.values())
+    check_jobs(jobs, out, sets)

@@ -508,10 +508,9 @@ def test_scale_image_mirror(ffi, oracle, repo_rig, square):
     assert got.shape == img.shape and np.array_equal(got, want)
 
 
-@pytest.mark.parametrize("seed", range(48))
-def test_random_rigs_modes_and_batches(ffi, SB, oracle, seed):
-    """Seeded fuzz over the geometry: frame / BEV / car sizes (odd ones included, so every schedule and every alignment
-    fallback is hit), focal and size scales, modes, batch sizes, with and without the car -- always bit-exact."""
+def random_rig_case(seed):
+    """The seeded geometry fuzz of test_random_rigs_modes_and_batches (shared with tests/test_analytic_gpu.py): frame / BEV / car sizes
+    (odd ones included), focal and size scales, modes, batch size, frames, an optional car and a schedule."""
     rng = np.random.default_rng(1000 + seed)
     fw = int(rng.choice([160, 200, 236, 320, 322, 400]))
     fh = int(rng.choice([128, 150, 256, 258]))
@@ -534,7 +533,17 @@ def test_random_rigs_modes_and_batches(ffi, SB, oracle, seed):
         car = np.zeros((bh, bw, 3), np.uint8)
         t, l = (bh - ch) // 2, (bw - cw) // 2
         car[t:t + ch, l:l + cw] = rng.integers(0, 256, (ch, cw, 3), dtype=np.uint8)
-    bev, ref = make_pair(SB, oracle, rig, cfg, blend, balance, schedule=int(rng.choice([0, 0, 1])))
+    schedule = int(rng.choice([0, 0, 1]))
+    return dict(cfg=cfg, rig=rig, blend=blend, balance=balance, batch=batch, frames=frames, car=car, schedule=schedule)
+
+
+@pytest.mark.parametrize("seed", range(48))
+def test_random_rigs_modes_and_batches(ffi, SB, oracle, seed):
+    """Seeded fuzz over the geometry: frame / BEV / car sizes (odd ones included, so every schedule and every alignment
+    fallback is hit), focal and size scales, modes, batch sizes, with and without the car -- always bit-exact."""
+    c = random_rig_case(seed)
+    cfg, blend, balance, batch, frames, car = c["cfg"], c["blend"], c["balance"], c["batch"], c["frames"], c["car"]
+    bev, ref = make_pair(SB, oracle, c["rig"], cfg, blend, balance, schedule=c["schedule"])
     got = bev.batch(frames, car)
     for b in range(batch):
         want = ref(*frames[b], car=car)
