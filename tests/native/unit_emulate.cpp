@@ -12,6 +12,8 @@
 //   in : int32 fw fh bw bh ncams nframes has_car blend | per camera: int16 lut1[bh][bw][2], uint16 lut2[bh][bw], uint8 mask[bh][bw]
 //        | uint8 frames[nframes][ncams][fh][fw][3] | uint8 car[bh][bw][3] if has_car
 //   out: int32 nunits claimed_tiles lines sectors | uint8 written[bh][bw] | uint8 image[nframes][bh][bw][3] (unwritten pixels 0)
+//        a rig for which the compiler makes no unit gives 0 0 0 0, an empty `written` plane and black images; without an input file
+//        (the synthetic rig) that is a failure, under BEVW_EMU_FUZZ it is accepted
 #include <cmath>
 #include <ctime>
 #include <cstdio>
@@ -65,6 +67,7 @@ static int expected_px(const Rig &r, int b, int x, int y, int out[3])
 }
 
 static bool g_allow_no_units = false;   // fuzz mode: a rig whose every base tile has a border footprint compiles nothing -- fine
+static bool g_file_mode = false;        // file mode: such a rig is reported as it is -- 0 units, nothing claimed, nothing written; the caller judges
 
 static int run(const Rig &r, const char *out_path)
 {
@@ -110,6 +113,19 @@ static int run(const Rig &r, const char *out_path)
     }();
     if (getenv("BEVW_EMU_TIME")) printf("unit_compile: %.1f ms (one host thread)\n", t_compile);
     if (up.desc.empty() && g_allow_no_units) { printf("unit schedule ok: no unit (every base tile left to the other classes)\n"); return 0; }
+    if (up.desc.empty() && g_file_mode) {
+        printf("unit schedule ok: no unit (every base tile left to the other classes)\n");
+        if (out_path) {
+            FILE *f = fopen(out_path, "wb");
+            CHECK(f, "cannot write %s", out_path);
+            const int32_t head[4] = {0, 0, 0, 0};
+            const std::vector<uint8_t> zeros((size_t)r.bw * r.bh * (1 + 3 * (size_t)r.nframes), 0);   // the written plane and the images
+            fwrite(head, 4, 4, f);
+            fwrite(zeros.data(), 1, zeros.size(), f);
+            fclose(f);
+        }
+        return 0;
+    }
     CHECK(!up.desc.empty(), "no unit compiled");
     if (getenv("BEVW_EMU_HIST")) {   // owned pixels by unit width (diagnostics: narrow units write short row runs)
         size_t hist[9] = {}, tot = 0;
@@ -278,6 +294,7 @@ int main(int argc, char **argv)
         CHECK(fread(r.frames.data(), 1, r.frames.size(), f) == r.frames.size(), "short frames");
         if (head[6]) { r.car.resize(npx * 3); CHECK(fread(r.car.data(), 1, r.car.size(), f) == r.car.size(), "short car"); }
         fclose(f);
+        g_file_mode = true;
         return run(r, argc >= 3 ? argv[2] : nullptr);
     }
     if (argc >= 1 && getenv("BEVW_EMU_FUZZ")) {
