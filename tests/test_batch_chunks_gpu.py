@@ -123,15 +123,19 @@ def expected(oracle, pool):
 
 
 class Inputs:
-    """The pool resident on the device once per input kind: packed BGR, packed NV12, NV12 surfaces at pitch FW + 4 with their table."""
+    """The pool resident on the device once per input kind: packed BGR, packed NV12, NV12 surfaces at pitch FW + 4 with their table, and
+    (yuv422: {'yuyv': frames, 'uyvy': frames}) the packed 4:2:2 forms of a pool that has them."""
 
-    def __init__(self, ffi, nv, bgr, car, cams=4):
-        self.ffi, self.nv, self.bgr, self.cams, self.bufs, self.surf = ffi, nv, bgr, cams, {}, None
+    def __init__(self, ffi, nv, bgr, car, cams=4, yuv422=None):
+        self.ffi, self.nv, self.bgr, self.cams, self.bufs, self.surf, self.yuv422 = ffi, nv, bgr, cams, {}, None, yuv422 or {}
         self.car = ffi.DeviceBuffer(car.nbytes).upload(car) if car is not None else None
+
+    def host(self, kind):
+        return self.bgr if kind == "bgr" else self.yuv422[kind] if kind in self.yuv422 else self.nv
 
     def packed(self, kind):
         if kind not in self.bufs:
-            host = self.bgr if kind == "bgr" else self.nv
+            host = self.host(kind)
             self.bufs[kind] = self.ffi.DeviceBuffer(host.nbytes).upload(host)
         return self.bufs[kind]
 
@@ -204,11 +208,13 @@ def run_batches(ffi, launch, sync, image_bytes, nv12, bw, bh, pitch, batches, wa
         d_out.free()
 
 
-def stitch_handle(ffi, SB, inputs, want, inp, out, blend, balance, batches=BATCHES, cfg=CFG, nb_env=0, host_entry=True, **kw):
-    """One BevGenerator over `batches` through the device-resident entry, then (packed handles) the host entry on 17 sets in reversed order."""
+def stitch_handle(ffi, SB, inputs, want, inp, out, blend, balance, batches=BATCHES, cfg=CFG, nb_env=0, host_entry=True, one_slice=False, **kw):
+    """One BevGenerator over `batches` through the device-resident entry, then (packed handles) the host entry on 17 sets in reversed order.
+    inp: 'bgr', 'nv12', 'surfaces', or 'yuyv' / 'uyvy' where `inputs` has those forms.  one_slice: a balance handle that does not cut its
+    step into slices (the plan's padded scratch), for the position a failure names."""
     fw = cfg["FRAME_WIDTH"]
     what = "%s -> %s, blend %d balance %d" % (inp, out, blend, balance)
-    kw = dict(dict(blend=blend, balance=balance, input_format="bgr" if inp == "bgr" else "nv12", output_format=out), **kw)
+    kw = dict(dict(blend=blend, balance=balance, input_format=inp if inp in ("bgr",) + tuple(inputs.yuv422) else "nv12", output_format=out), **kw)
     if inp == "surfaces":
         kw["input_pitch"] = fw + 4
     bev = TI.generator(SB, TI.small_rig(), cfg, **kw)
@@ -224,14 +230,14 @@ def stitch_handle(ffi, SB, inputs, want, inp, out, blend, balance, batches=BATCH
         launch = lambda B, d_out: bev.run_device(d_in.ptr, B, car, d_out.ptr, out_bytes=d_out.nbytes)
     nv12 = out == "nv12"
     run_batches(ffi, launch, bev.sync, bev.out_image_bytes, nv12, cfg["BEV_WIDTH"], cfg["BEV_HEIGHT"], bev.out_pitch, batches, want, what,
-                balance=balance, nb_env=nb_env)
+                balance=balance and not one_slice, nb_env=nb_env)
     if host_entry and inp != "surfaces":
-        host = inputs.bgr if inp == "bgr" else inputs.nv
+        host = inputs.host(inp)
         car_host = inputs.car.download(want[0][0].shape)
         got = bev.batch(host[:17][::-1], car_host)
         for i in range(17):
             check_image(got[i], want[0][16 - i], want[1][16 - i] if nv12 else None, want[2], nv12,
-                        "%s, host entry, reversed: position %d = set %d; %s" % (what, i, 16 - i, where(17, i, balance, nb_env)))
+                        "%s, host entry, reversed: position %d = set %d; %s" % (what, i, 16 - i, where(17, i, balance and not one_slice, nb_env)))
     return bev
 
 
