@@ -1,7 +1,7 @@
 // bevw_host.h -- host-side plumbing shared by the translation units of libbevwarp.so (bevwarp.hip: handles, tables, tools, the
 // camera-per-GPU exchange; bevwarp_plan.hip: the tile plan and its kernels; bevwarp_jpeg.hip: the JPEG codec; bevwarp_yuv422.hip: the kernels
 // that read packed 4:2:2 frames): the thread-local
-// error string behind bevw_last_error(), the HIP_TRY / BEVW_TRY early-return macros, device / pinned buffers, the lap timer, and the
+// error string behind bevw_last_error(), the HIP_TRY / BEVW_TRY early-return macros, env_int, device / pinned buffers, the lap timer, and the
 // launch helpers (batch chunks, compile-time flags, compile-time pixel formats).
 #pragma once
 #include "../../include/bevwarp.h"
@@ -57,6 +57,13 @@ static inline int launch_check(const char *what)
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(BEVW_E_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
     return BEVW_OK;
+}
+
+// an integer switch of the environment (BEVW_*): callers keep the value in a function-local static, so a switch is read once per process
+static inline int env_int(const char *name, int dflt)
+{
+    const char *s = getenv(name);
+    return s ? atoi(s) : dflt;
 }
 
 // f(first, count) over [0, n) in spans of at most `max`: a batch rides in grid.y or grid.z, which hold at most 65535 blocks

@@ -435,7 +435,7 @@ static inline hipError_t plan_upload_units(Plan &p, const UnitPlanHost &up)
     if ((e = hipMemcpy(p.un_desc, up.desc.data(), up.desc.size() * sizeof(UnitDesc), hipMemcpyHostToDevice)) != hipSuccess) return e;
     if ((e = hipMalloc(&p.un_entries, up.entries.size() * sizeof(uint32_t))) != hipSuccess) return e;
     if ((e = hipMemcpy(p.un_entries, up.entries.data(), up.entries.size() * sizeof(uint32_t), hipMemcpyHostToDevice)) != hipSuccess) return e;
-    if ((e = plan_upload_list(up.gsrc, &p.un_gsrc)) != hipSuccess) return e;
+    if ((e = plan_upload_list(up.gsrc, &p.units[kLayoutBGR])) != hipSuccess) return e;
     if ((e = plan_upload_list(up.all, &p.list_un_all)) != hipSuccess) return e;
     p.n_un_all = (int)up.all.size();
     for (int c = 0; c < kUnitClasses; ++c) p.n_un[c] = (int)up.list[c].size();
@@ -446,6 +446,35 @@ static inline hipError_t plan_upload_units(Plan &p, const UnitPlanHost &up)
 
 // pixels per output row the plan kernels write: the caller's pitch (bevw_set_output_pitch), else bw rounded up to 4 (12-byte stores)
 static inline int plan_pitch(int bw, int out_pitch) { return out_pitch > 0 ? out_pitch : (bw + 3) & ~3; }
+
+// The pair of group lists of one layout (SrcLayout, bevw_planapi.h), made from the host copies of the BGR lists the plan keeps and replacing
+// what the plan held for that layout.  A list that does not exist for the plan's geometry stays nullptr.  No step of the plan may be queued.
+static inline hipError_t plan_make_lists(Plan &p, SrcLayout lay)
+{
+    for (void **q : {&p.units[lay], &p.sampled[lay]}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    // translate(list, as the units' list) -> whether `tr` holds a list to upload; both BGR lists are empty when FW % 4 != 0
+    std::vector<uint32_t> tr;
+    auto translate = [&](const std::vector<uint32_t> &bgr, bool units) {
+        if (bgr.empty()) return false;
+        switch (lay) {
+        case kLayoutBGR: tr = bgr; return true;
+        case kLayoutNV12: if (p.fh % 2 != 0) return false; unit_gsrc_nv12(bgr, p.fw, p.fh, tr); return true;
+        case kLayoutSurf:   // (a units' list with a unit of more than two cameras is not used: the per-tap kernel then serves every tile)
+            return p.src_pitch > 0 && p.fh % 2 == 0 && unit_gsrc_surf(bgr, p.fw, p.fh, p.src_pitch, tr, units ? &p.un_ranges_host : nullptr);
+        case kLayoutYuv422: unit_gsrc_yuv422(bgr, p.fw, p.fh, tr); return true;   // (the same list serves both byte orders)
+        default:   // kLayoutCompact: the units alone, and only where the scratch stays below 2^31 bytes per frame set
+            return units && unit_gsrc_compact(bgr, p.groups_host, tr) && unit_compact_stride(p.groups_host.size()) < (1ull << 31);
+        }
+    };
+    hipError_t e;
+    if (translate(p.un_gsrc_host, true) && (e = plan_upload_list(tr, &p.units[lay])) != hipSuccess) return e;
+    if (translate(p.groups_host, false) && (e = plan_upload_list(tr, &p.sampled[lay])) != hipSuccess) return e;
+    if (lay == kLayoutCompact) p.compact_stride = p.units[lay] ? unit_compact_stride(p.groups_host.size()) : 0;
+    return hipSuccess;
+}
 
 static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTables &T, int fw, int fh, int bw, int bh, int ncams = 4,
                                          bool units = true, const UnitTuning &unit_tune = UnitTuning(), int out_pitch = 0)
@@ -466,7 +495,6 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = hipMemcpyAsync(&p.max_contrib, p.d_max, sizeof(int), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
     p.band_ok = false;
-    std::vector<uint32_t> groups_host;   // the sampled 4-texel groups, ascending (what Plan::groups holds on the device)
     if (fw % 4 == 0) {
         const size_t nbits = (size_t)ncams * fh * (fw / 4), nwords = (nbits + 31) / 32;
         uint32_t *d_bits = nullptr;
@@ -476,7 +504,7 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
         hipLaunchKernelGGL(k_plan_touch, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, st, static_cast<const uint2 *>(p.entries),
                            p.ntiles, fw, fh, d_bits);
         if ((e = hipGetLastError()) != hipSuccess) return e;
-        std::vector<uint32_t> bits(nwords), list;
+        std::vector<uint32_t> bits(nwords), &list = p.groups_host;   // the sampled 4-texel groups, ascending (kept for plan_set_format)
         if ((e = hipMemcpyAsync(bits.data(), d_bits, nwords * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(st)) != hipSuccess) return e;
         (void)hipFree(d_bits);
@@ -490,15 +518,8 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
             }
         }
         p.n_groups = (int)list.size();
-        if ((e = plan_upload_list(list, &p.groups)) != hipSuccess) return e;
-        if (fh % 2 == 0) {   // the same groups in NV12 frame sets (k_lum_groups<true>)
-            std::vector<uint32_t> nv;
-            unit_gsrc_nv12(list, fw, fh, nv);
-            if ((e = plan_upload_list(nv, &p.groups_nv12)) != hipSuccess) return e;
-        }
+        if ((e = plan_upload_list(list, &p.sampled[kLayoutBGR])) != hipSuccess) return e;
         p.band_ok = true;
-        groups_host.swap(list);
-        p.groups_host = groups_host;   // (kept for plan_set_format)
     }
     std::vector<uint32_t> hdr((size_t)p.ntiles);
     if ((e = hipMemcpyAsync(hdr.data(), p.hdr, hdr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
@@ -528,16 +549,7 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
             if ((e = plan_upload_units(p, up)) != hipSuccess) return e;
             p.un_gsrc_host = up.gsrc;   // (kept for plan_set_format)
             p.un_ranges_host = unit_slot_ranges(up);
-            if (fh % 2 == 0) {   // the units' group lists for NV12 frame sets (k_plan_units<.., true>)
-                std::vector<uint32_t> nv;
-                unit_gsrc_nv12(up.gsrc, fw, fh, nv);
-                if ((e = plan_upload_list(nv, &p.un_gsrc_nv12)) != hipSuccess) return e;
-            }
-            std::vector<uint32_t> gc;
-            if (p.band_ok && unit_gsrc_compact(up.gsrc, groups_host, gc) && unit_compact_stride(groups_host.size()) < (1ull << 31)) {
-                if ((e = plan_upload_list(gc, &p.un_gsrc_compact)) != hipSuccess) return e;
-                p.compact_stride = unit_compact_stride(groups_host.size());
-            }
+            if (p.band_ok && (e = plan_make_lists(p, kLayoutCompact)) != hipSuccess) return e;   // (the frame layouts: plan_set_format)
         }
     }
     // what no unit owns stays on the per-tap kernel
@@ -549,46 +561,6 @@ static inline hipError_t plan_build_impl(Plan &p, hipStream_t st, const StitchTa
     // 12-byte stores need 4-byte aligned pixel quads: rows of `pitch` pixels (bw % 4 != 0: padded scratch + k_plan_unpad)
     p.pitch = plan_pitch(bw, out_pitch);
     p.out_pitched = out_pitch > 0 && out_pitch != bw;
-    return hipSuccess;
-}
-
-// NV12 surfaces: the third translation of the group lists (unit_gsrc_surf) -- the units' and the sampled-group list of the balance schedule --
-// for surfaces whose rows are `pitch` bytes apart (plan_set_format).  The plan itself does not change; no step of the plan may be queued.
-static inline hipError_t plan_src_pitch_impl(Plan &p, int pitch)
-{
-    for (void **q : {&p.un_gsrc_surf, &p.groups_surf}) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    if (pitch <= 0 || p.fh % 2 != 0 || p.fw % 4 != 0) return hipSuccess;
-    hipError_t e;
-    std::vector<uint32_t> nv;
-    if (!p.un_gsrc_host.empty()) {
-        // (a list with a unit of more than two cameras is not used: the per-tap kernel then serves every tile)
-        if (unit_gsrc_surf(p.un_gsrc_host, p.fw, p.fh, pitch, nv, &p.un_ranges_host) && (e = plan_upload_list(nv, &p.un_gsrc_surf)) != hipSuccess) return e;
-    }
-    if (!p.groups_host.empty()) {
-        unit_gsrc_surf(p.groups_host, p.fw, p.fh, pitch, nv);
-        if ((e = plan_upload_list(nv, &p.groups_surf)) != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// Packed 4:2:2 frame sets: the translation of the group lists for them (unit_gsrc_yuv422), once per plan -- the same lists serve both byte
-// orders.  From the host copies the plan keeps; no step of the plan may be queued.
-static inline hipError_t plan_yuv422_impl(Plan &p)
-{
-    hipError_t e;
-    std::vector<uint32_t> tr;
-    if (p.fw % 4 != 0) return hipSuccess;   // (no unit plan and no group list: the per-tap kernel serves every tile)
-    if (!p.un_gsrc_host.empty() && !p.un_gsrc_yuv422) {
-        unit_gsrc_yuv422(p.un_gsrc_host, p.fw, p.fh, tr);
-        if ((e = plan_upload_list(tr, &p.un_gsrc_yuv422)) != hipSuccess) return e;
-    }
-    if (!p.groups_host.empty() && !p.groups_yuv422) {
-        unit_gsrc_yuv422(p.groups_host, p.fw, p.fh, tr);
-        if ((e = plan_upload_list(tr, &p.groups_yuv422)) != hipSuccess) return e;
-    }
     return hipSuccess;
 }
 
@@ -606,7 +578,7 @@ static inline PlanArgs plan_args(const Plan &p, const FrameSource &src, int batc
     a.tiles_x = p.tiles_x; a.ntiles = p.ntiles; a.ncams = p.ncams;
     a.un_desc = static_cast<const UnitDesc *>(p.un_desc);
     a.un_entries = static_cast<const uint4 *>(p.un_entries);
-    a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc);
+    a.un_gsrc = static_cast<const uint32_t *>(p.units[kLayoutBGR]);
     a.un_skew = p.un_skew;
     a.batch = batch;
     // frames per block: enough chunks to give each of the 8 XCDs whole chunks, otherwise one frame per chunk.  A block reads its plan
@@ -624,13 +596,13 @@ static inline PlanArgs plan_args(const Plan &p, const FrameSource &src, int batc
 }
 
 // The unit kernel of a step.  Five names, so that k_plan_units stays the four BGR instantiations (bevw_unit.h), and two more behind
-// yuv422_launch_units.  nv12 / surf / yuv422: what the UNITS read -- the step's frames, or the BGR compact scratch of the balance schedule;
+// yuv422_launch_units.  lay: what the UNITS read -- the step's frames, or the BGR compact scratch of the balance schedule (Route::units);
 // channel sums exist with BGR in and out only.
-static inline void plan_launch_units(const PlanArgs &a, hipStream_t st, bool blend, bool sums, bool nv12, bool surf, bool out_nv12, bool yuv422)
+static inline void plan_launch_units(const PlanArgs &a, hipStream_t st, bool blend, bool sums, SrcLayout lay, bool out_nv12)
 {
-    if (yuv422) return yuv422_launch_units(a, st, blend, out_nv12);   // (k_units_yuv422 / k_units_out_yuv422: bevwarp_yuv422.hip)
+    if (lay == kLayoutYuv422) return yuv422_launch_units(a, st, blend, out_nv12);   // (k_units_yuv422 / k_units_out_yuv422: bevwarp_yuv422.hip)
     const dim3 grid(plan_grid(a)), block(256);
-    with_formats(nv12, surf, out_nv12, [&](auto in, auto on) {
+    with_formats(lay == kLayoutNV12 || lay == kLayoutSurf, lay == kLayoutSurf, out_nv12, [&](auto in, auto on) {
         constexpr bool NV12 = decltype(in)::nv12, SURF = decltype(in)::surf, OUT_NV12 = decltype(on)::value;
         with_flags([&](auto bl) {
             if constexpr (SURF && OUT_NV12) hipLaunchKernelGGL((k_units_out_surf<bl>), grid, block, 0, st, a);
@@ -654,8 +626,15 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
     a.plan = static_cast<const uint2 *>(p.entries); a.hdr = static_cast<const uint32_t *>(p.hdr);
     a.deltas = s.deltas; a.tab = s.tab;
     const bool padded = p.pitch != p.bw, scratch = padded && !p.out_pitched;
-    // NV12 images (p.out_nv12) unless the step leaves a pre-gain BGR image for a gain pass (channel sums) or serves a shard (compact scratch)
-    const bool out_nv12 = p.out_nv12 && !s.balance && !s.sums && s.scratch == nullptr;
+    RouteIn ri;
+    ri.fmt = p.fmt; ri.surf = surf; ri.out_nv12 = p.out_nv12;
+    ri.balance = s.balance; ri.sums = s.sums; ri.scratch = s.scratch != nullptr;
+    ri.units_on = tune.units && p.n_un_all > 0;
+    ri.src_aligned = s.src.aligned4(); ri.scratch_aligned = (((uintptr_t)s.scratch) & 3u) == 0;
+    for (int l = 0; l < kSrcLayouts; ++l) ri.have[l] = p.units[l] != nullptr;
+    ri.set_bytes = (uint32_t)(frame_bytes_of(p.fw, p.fh, p.fmt) * p.ncams); ri.compact_stride = (uint32_t)p.compact_stride;
+    const Route rt = plan_route(ri);
+    const bool out_nv12 = rt.out_nv12, use_units = rt.use_units;
     if (out_nv12 && (scratch || p.pitch % 4 != 0)) return hipErrorInvalidValue;   // (the caller runs the per-pixel kernel instead)
     if (padded) {
         const size_t img = (size_t)p.pitch * p.bh * 3, need = scratch ? img * (size_t)batch : 0;
@@ -673,16 +652,6 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
         }
         if (scratch) a.out = static_cast<uint8_t *>(p.pad_out);
     }
-    // the units need 4-byte aligned frame sets (dword-addressed group loads) and are not combined with the per-tap luminance kernel
-    const bool compact = s.scratch != nullptr;
-    // NV12 frames: the units read them through the NV12 group lists unless they read the compact scratch (BGR)
-    const bool nv12_units = p.nv12() && !compact;
-    // packed 4:2:2 frames: the same, through their own group lists
-    const bool yuv422_units = p.yuv422() && !compact;
-    const bool use_units = !s.balance && tune.units && p.n_un_all > 0 && s.src.aligned4() &&
-                           (!compact || (p.un_gsrc_compact != nullptr && (((uintptr_t)s.scratch) & 3u) == 0)) &&
-                           (!nv12_units || ((surf ? p.un_gsrc_surf : p.un_gsrc_nv12) != nullptr && !s.sums)) &&
-                           (!yuv422_units || (p.un_gsrc_yuv422 != nullptr && !s.sums));
     const bool with_sums = s.balance || s.sums;
     // channel-sum entries per frame: one per unit + one per base tile left to the per-tap kernel (or one per tile without units).  Every
     // entry has exactly one writer per frame (no atomics, round 5: 2.4 M atomic adds per config-4 step cost 58 us of the 600), and every writer
@@ -707,16 +676,10 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
     if (use_units) {
         if (s.sums) a.car = nullptr;   // the car is added behind the gains
         a.tile_list = static_cast<const uint32_t *>(p.list_un_all); a.nlist = p.n_un_all; a.ngroups = p.n_un_all;
-        if (compact) { a.frames = s.scratch; a.set_stride = (uint32_t)p.compact_stride; a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_compact); }
-        if (nv12_units) {
-            a.set_stride = (uint32_t)(frame_bytes_of(p.fw, p.fh, true) * p.ncams);
-            a.un_gsrc = static_cast<const uint32_t *>(surf ? p.un_gsrc_surf : p.un_gsrc_nv12);
-        }
-        if (yuv422_units) {
-            a.set_stride = (uint32_t)(frame_bytes_of(p.fw, p.fh, p.fmt) * p.ncams);
-            a.un_gsrc = static_cast<const uint32_t *>(p.un_gsrc_yuv422);
-        }
-        plan_launch_units(a, st, s.blend, s.sums, nv12_units, surf && nv12_units, out_nv12, yuv422_units);
+        if (rt.units == kLayoutCompact) a.frames = s.scratch;
+        a.set_stride = rt.set_stride;
+        a.un_gsrc = static_cast<const uint32_t *>(p.units[rt.units]);
+        plan_launch_units(a, st, s.blend, s.sums, rt.units, out_nv12);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     const int n_tap = use_units ? p.n_slow : p.ntiles;
@@ -726,14 +689,13 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
         if (s.sums) a.car = nullptr;
         a.frames = s.src.packed; a.set_stride = 0;   // the per-tap kernel reads whole frames: RAW ones in the balance modes
         // (packed 4:2:2: k_stitch_plan_yuv422, bevwarp_yuv422.hip)
-        if (p.yuv422()) yuv422_launch_stitch_plan(a, st, s.blend, s.balance || compact, s.balance || s.sums, out_nv12);
-        else with_formats(p.nv12(), surf, out_nv12, [&](auto in, auto on) {
+        if (rt.frames == kLayoutYuv422) yuv422_launch_stitch_plan(a, st, s.blend, rt.lum, rt.tap_sums, out_nv12);
+        else with_formats(rt.frames != kLayoutBGR, rt.frames == kLayoutSurf, out_nv12, [&](auto in, auto on) {
             constexpr bool NV12 = decltype(in)::nv12, SURF = decltype(in)::surf, OUT_NV12 = decltype(on)::value;
             auto launch = [&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm, NV12, OUT_NV12, SURF>), dim3(plan_grid(a)), dim3(256), 0, st, a); };
-            // LUM: luminance round trip per tap (the RAW frames of balance, or the tiles no unit owns beside the compact scratch); compact
-            // without sums: camera-per-GPU shards, whose stitch rank balances the colours.  Neither exists with NV12 images (out_nv12 above)
+            // (neither LUM nor SUMS exists with NV12 images: plan_route)
             if constexpr (OUT_NV12) with_flags([&](auto bl) { launch(bl, std::false_type{}, std::false_type{}); }, s.blend);
-            else with_flags(launch, s.blend, s.balance || compact, s.balance || s.sums);
+            else with_flags(launch, s.blend, rt.lum, rt.tap_sums);
         });
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
@@ -769,8 +731,8 @@ static inline hipError_t plan_lum_band(const Plan &p, hipStream_t st, const Fram
                                        const int *d_deltas, const HsvTables *d_tab)
 {
     if (p.n_groups == 0 || p.compact_stride == 0) return hipSuccess;
-    // the sampled groups as this kind of source addresses them (surfaces: relative to the camera's own planes, plan_src_pitch_impl)
-    const void *groups = src.is_surf() ? p.groups_surf : (src.nv12() ? p.groups_nv12 : (src.yuv422() ? p.groups_yuv422 : p.groups));
+    // the sampled groups as this kind of source addresses them (surfaces: relative to the camera's own planes)
+    const void *groups = p.sampled[frames_layout(src.fmt, src.is_surf())];
     if (!groups || src.fmt != p.fmt || src.cams != p.ncams || (src.is_surf() && src.pitch != p.src_pitch)) return hipErrorInvalidValue;
     const size_t frame_bytes = frame_bytes_of(p.fw, p.fh, src.fmt);
     const unsigned bpf = (unsigned)(p.n_groups + 256 * kLumTrips - 1) / (256 * kLumTrips);

@@ -37,6 +37,12 @@ struct FrameSource {
     }
 };
 
+// What a group list addresses.  Every list of the plan -- the units' group lists and the sampled groups of the balance schedule -- exists once
+// per layout of the memory it is read against: packed BGR, packed NV12, NV12 surfaces at Plan::src_pitch, packed 4:2:2, the compact scratch
+// (DESIGN.md section 8 has the table: what a slot holds, when a list is made, when it is missing).  A missing list is nullptr, which sends
+// the step to the per-tap kernel and is never an error.
+enum SrcLayout { kLayoutBGR = 0, kLayoutNV12, kLayoutSurf, kLayoutYuv422, kLayoutCompact, kSrcLayouts };
+
 // a compiled tile plan: its device buffers and the geometry they were built for (plan_build / plan_build_wide)
 struct Plan {
     void *entries = nullptr;     // uint2[ntiles][8][64]
@@ -55,8 +61,9 @@ struct Plan {
     int fw = 0, fh = 0, bw = 0, bh = 0;
     int tiles_x = 0, tiles_y = 0, ntiles = 0;
     int ncams = 4;
-    void *groups = nullptr;      // uint32[n_groups]: byte offsets (inside the frame set) of the sampled 4-texel groups
-    void *groups_nv12 = nullptr; // uint32[n_groups][2]: the same groups in an NV12 frame set (Y, U / V offsets; even frame heights)
+    // the group lists, one per layout of what they address (SrcLayout; bevw_unit.h has the translations).  sampled: the n_groups sampled
+    // 4-texel groups of the frame set in ascending order (balance schedule 1: plan_lum_groups; none for the compact scratch it writes)
+    void *units[kSrcLayouts] = {}, *sampled[kSrcLayouts] = {};
     int n_groups = 0;
     bool band_ok = false;        // the sampled-group list exists (balance schedule 1)
     int max_contrib = 0;
@@ -64,10 +71,8 @@ struct Plan {
     void *list_slow = nullptr;   // base tiles no unit owns (frame-border footprints; everything when there are no units)
     int n_slow = 0;
     // unit schedule (bevw_unit.h): k-d partition compiled on the host
-    void *un_desc = nullptr, *un_entries = nullptr, *un_gsrc = nullptr;
-    void *un_gsrc_compact = nullptr;         // the units' group lists for the compact scratch of the balance schedule (unit_gsrc_compact); nullptr: not usable
-    void *un_gsrc_nv12 = nullptr;            // the units' group lists for NV12 frame sets, two offsets per slot (unit_gsrc_nv12); nullptr: odd frame height
-    size_t compact_stride = 0;               // bytes between the compact scratch copies of consecutive frame sets
+    void *un_desc = nullptr, *un_entries = nullptr;
+    size_t compact_stride = 0;               // bytes between the compact scratch copies of consecutive frame sets (0: units[kLayoutCompact] does not exist)
     void *list_un_all = nullptr;             // every unit in partition order, class in bits 28..31
     int n_un_all = 0;
     int n_un[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // units per class (diagnostics)
@@ -76,22 +81,60 @@ struct Plan {
     int un_skew = 0;
     // The formats of the plan's steps, written by plan_set_format alone (plan_build resets them).  fmt: what their frame sets hold (bevw_set_input_format).
     SrcFormat fmt = SrcFormat::BGR;
-    bool nv12() const { return fmt == SrcFormat::NV12; }
-    bool yuv422() const { return src_is_yuv422(fmt); }
     // out_nv12: they write NV12 images of `pitch` bytes per row (bevw_set_output_format; needs pitch % 4 == 0 and no padded scratch).  Steps
     // with channel sums (balance) still write the BGR pre-gain image: their gain pass converts.
     bool out_nv12 = false;
-    // src_pitch: NV12 surfaces (bevw_set_input_pitch / bevw_run_surfaces_device) have rows of src_pitch bytes, and the group lists are
-    // translated for them (unit_gsrc_surf: offsets inside the camera's own planes, camera in the low bits); the host copies of the lists
-    // the translation starts from stay with the plan.
+    // src_pitch: NV12 surfaces (bevw_set_input_pitch / bevw_run_surfaces_device) have rows of src_pitch bytes: the pitch the kLayoutSurf lists
+    // are translated for (0: none).  The host copies of the BGR lists every translation starts from stay with the plan.
     int src_pitch = 0;
-    void *un_gsrc_surf = nullptr;            // the units' group lists, two dwords per slot
-    void *groups_surf = nullptr;             // the sampled groups of the balance schedule (k_lum_groups<true, true>), two dwords per group
-    // packed 4:2:2 frame sets (YUYV / UYVY): one dword per slot (unit_gsrc_yuv422), uploaded by plan_set_format when such a format is first set
-    void *un_gsrc_yuv422 = nullptr;          // the units' group lists
-    void *groups_yuv422 = nullptr;           // the sampled groups of the balance schedule (k_lum_groups_yuv422)
     std::vector<uint32_t> un_gsrc_host, groups_host, un_ranges_host;   // (un_ranges_host: first slot and slot count of every unit's list)
 };
+
+// The routing of one step of the plan: which list the units read, whether they may run, and what is left to the per-tap kernel.  Pure host
+// arithmetic and the one place that knows these rules (plan_stitch and plan_lum_groups ask it; tests/native/plan_route_exhaustive.cpp holds
+// it against the expressions it replaced, for every input).
+struct RouteIn {
+    SrcFormat fmt = SrcFormat::BGR;   // the plan's format (Plan::fmt)
+    bool surf = false;                // the step's frames are NV12 surfaces
+    bool out_nv12 = false;            // the plan writes NV12 images (Plan::out_nv12)
+    bool balance = false, sums = false, scratch = false;   // the step's (PlanStep; scratch: it brings a compact scratch)
+    bool units_on = false;            // the units switch is on and the plan has units
+    bool src_aligned = false, scratch_aligned = false;     // the frame sets / the compact scratch are 4-byte aligned
+    bool have[kSrcLayouts] = {};      // Plan::units[layout] exists
+    uint32_t set_bytes = 0, compact_stride = 0;   // bytes of one frame set in the plan's format; Plan::compact_stride
+};
+struct Route {
+    SrcLayout frames;      // how the step's frames are addressed: the per-tap kernel's instantiation, the sampled list of k_lum_groups
+    SrcLayout units;       // what the units read: the frames, or the BGR compact scratch
+    bool use_units;        // the units run, the per-tap kernel serves only what no unit owns; false: it serves every tile
+    bool out_nv12;         // the step writes NV12 images: never one that leaves a pre-gain BGR image (channel sums) or serves a shard (scratch)
+    uint32_t set_stride;   // PlanArgs::set_stride of the units (0: dense BGR frame sets)
+    bool lum, tap_sums;    // the LUM / SUMS flags of the per-tap kernel
+};
+inline SrcLayout frames_layout(SrcFormat fmt, bool surf)
+{
+    return src_is_yuv422(fmt) ? kLayoutYuv422 : surf ? kLayoutSurf : fmt == SrcFormat::NV12 ? kLayoutNV12 : kLayoutBGR;
+}
+inline Route plan_route(const RouteIn &in)
+{
+    Route r;
+    r.frames = frames_layout(in.fmt, in.surf);
+    // the units read the compact scratch where the step brings one, else the frames (surfaces are NV12: any other format with a surface
+    // table is refused before a step gets here, and routed as its packed frames)
+    r.units = in.scratch ? kLayoutCompact : frames_layout(in.fmt, in.surf && in.fmt == SrcFormat::NV12);
+    const bool bgr_units = r.units == kLayoutBGR || r.units == kLayoutCompact;
+    // the units need their list, 4-byte aligned memory behind it (dword-addressed group loads), and are not combined with the per-tap
+    // luminance kernel (balance); channel sums exist with BGR units only.  (The BGR list exists wherever the plan has units.)
+    r.use_units = !in.balance && in.units_on && in.src_aligned && (r.units == kLayoutBGR || in.have[r.units]) &&
+                  (r.units != kLayoutCompact || in.scratch_aligned) && (bgr_units || !in.sums);
+    r.out_nv12 = in.out_nv12 && !in.balance && !in.sums && !in.scratch;
+    r.set_stride = !r.use_units || r.units == kLayoutBGR ? 0u : r.units == kLayoutCompact ? in.compact_stride : in.set_bytes;
+    // LUM: luminance round trip per tap (the RAW frames of balance, or the tiles no unit owns beside the compact scratch); a scratch without
+    // sums: camera-per-GPU shards, whose stitch rank balances the colours.  Neither exists with NV12 images (out_nv12 above)
+    r.lum = in.balance || in.scratch;
+    r.tap_sums = in.balance || in.sums;
+    return r;
+}
 
 // compile LUT + masks into a plan (table kernels, unit compiler on the host).  out_pitch: pixels per output row when the caller's images
 // are pitched (0: dense); blend: the handle applies blend weights (its units carry no two-quad two-contributor class)
@@ -113,7 +156,7 @@ struct PlanStep {
     // step run concurrently on two streams: balance_plan_run); 0: this step's batch alone
     int psums_frames = 0, psums_first = 0;
     // the compact scratch plan_lum_groups filled from the frames (balance schedule 1): the units read IT (p.compact_stride bytes per frame
-    // set, group lists p.un_gsrc_compact), the per-tap kernel serves what no unit owns from the RAW frames with the luminance round trip per
+    // set, group lists p.units[kLayoutCompact]), the per-tap kernel serves what no unit owns from the RAW frames with the luminance round trip per
     // tap (deltas, tab); everything on the per-tap kernel when the units cannot run
     const uint8_t *scratch = nullptr;
 };

@@ -511,7 +511,7 @@ static inline void unit_compile(const std::vector<int16_t> lut1[4], const std::v
 }
 
 // The COMPACT scratch of the balance schedule (bevw_plan.h: k_lum_groups): the luminance-shifted copy of a frame set holds ONLY the
-// sampled 4-texel groups, 12 bytes each, in ascending order of their offsets in the frame set (Plan::groups) -- slot i of the scratch is group
+// sampled 4-texel groups, 12 bytes each, in ascending order of their offsets in the frame set (Plan::sampled[kLayoutBGR]) -- slot i of the scratch is group
 // groups[i].  A unit's group list for that layout is the rank of every group times 12.  The 16-byte load of slot i reaches 4 bytes into
 // slot i + 1; they matter only to a pixel that samples texel pair 3 of the group (texels 4g + 3, 4g + 4), and then texel 4g + 4 lies in the
 // pixel's footprint, i.e. group g + 1 (same row: sx + 1 < fw) is sampled as well and IS slot i + 1.
@@ -527,7 +527,7 @@ static inline bool unit_gsrc_compact(const std::vector<uint32_t> &gsrc, const st
     }
     return true;
 }
-// NV12 frame sets (bevw_set_input_format): a list of groups as BGR frame-set offsets (12 k for group k: a unit's group list, Plan::groups)
+// NV12 frame sets (bevw_set_input_format): a list of groups as BGR frame-set offsets (12 k for group k: a unit's group list, Plan::sampled[kLayoutBGR])
 // translated into the byte offsets of the group's Y bytes and U / V bytes inside an NV12 frame set (fw * fh * 3 / 2 bytes per camera):
 // out[2 i] = Y of texel (x, y), out[2 i + 1] = U of texel (x, y) in row y / 2 of the chroma plane.  The plan compiler is the same for
 // both formats; the NV12 instantiation of the unit kernel reads this list instead of the BGR one.  fw % 4 == 0, fh even.

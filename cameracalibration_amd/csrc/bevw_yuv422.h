@@ -9,7 +9,7 @@ namespace bevw {
 
 struct PlanArgs;   // bevw_plan.h
 
-// the unit kernel of a step (plan_launch_units): grid and tile list as for the other formats, a.un_gsrc = Plan::un_gsrc_yuv422
+// the unit kernel of a step (plan_launch_units): grid and tile list as for the other formats, a.un_gsrc = Plan::units[kLayoutYuv422]
 void yuv422_launch_units(const PlanArgs &a, hipStream_t st, bool blend, bool out_nv12);
 // the per-tap tile kernel of a step (plan_stitch_impl); OUT_NV12 exists without the luminance round trip and channel sums only
 void yuv422_launch_stitch_plan(const PlanArgs &a, hipStream_t st, bool blend, bool lum, bool sums, bool out_nv12);

@@ -333,35 +333,169 @@ static int check_input_pitch(int pitch_bytes, int fw, int fh, bool nv12)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// bevw_remapper
+// engine core: what a bevw_handle and a bevw_remapper have in common
 // ---------------------------------------------------------------------------------------------------------------
-struct bevw_remapper {
+// the words of an owner's error messages: its name, its frame width and its frames as they call them, the prefix of its bevw_*set_input_format
+// ... functions, its entry points for surfaces
+struct EngineNouns { const char *owner, *width, *frame, *setters, *surface_calls; };
+
+// The stream, timers, staging buffers, tile plan and pixel formats of one engine.  Its formats reach the plan through apply_format() alone,
+// and only with every stream of the engine idle (engine_set).
+struct EngineCore {
+    const EngineNouns *nouns = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;
+    std::vector<hipStream_t> side_streams;   // further streams the owner's steps run on (add_stream): drained with `stream`, destroyed with it
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     LapTimer laps;
-    int sw = 0, sh = 0, dw = 0, dh = 0;
-    DevBuf map1, map2, in, out, ones;
-    Plan plan;            // single-image contributor plan (same kernels as the BEV stitch, ncams = 1)
+    DevBuf in, out;                      // host entry points: the uploaded frames, the images on their way back
+    SurfStage surf_stage;                // host tables of NV12 surfaces (engine_staged_step)
+    Plan plan;
+    int fw = 0, fh = 0;                  // the frame size the formats are checked against
+    int cams = 4;                        // frames per set
+    int input_format = BEVW_INPUT_BGR, output_format = BEVW_OUTPUT_BGR;
+    int in_pitch_request = 0;            // 0: the frame width
+    SrcFormat fmt() const { return (SrcFormat)input_format; }
+    bool nv12() const { return input_format == BEVW_INPUT_NV12; }
+    bool yuv422() const { return src_is_yuv422(fmt()); }   // packed 4:2:2: YUYV / UYVY
+    bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
+    int in_pitch() const { return in_pitch_request ? in_pitch_request : fw; }   // bytes between the rows of an NV12 surface
+    // the frames of a step: packed frame sets behind d_frames, or (d_surf) a device table surf[frame set][cams] of NV12 surfaces, read in place
+    FrameSource source(const uint8_t *d_frames, const Nv12Surface *d_surf) const { return {d_surf ? nullptr : d_frames, d_surf, d_surf ? in_pitch() : 0, fmt(), cams}; }
+    // the plan follows the engine's formats (after plan_build; the setters of an engine whose plan is live)
+    int apply_format() { return plan_set_format(plan, fmt(), out_nv12(), nv12() ? in_pitch() : 0); }
+    bool open() { return hipStreamCreate(&stream) == hipSuccess && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess; }
+    bool add_stream(hipStream_t *st)
+    {
+        if (hipStreamCreate(st) != hipSuccess) { (void)hipGetLastError(); *st = nullptr; return false; }
+        side_streams.push_back(*st);
+        return true;
+    }
+    int drain()
+    {
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (hipStream_t st : side_streams) HIP_TRY(hipStreamSynchronize(st));
+        return BEVW_OK;
+    }
+    // the end of an engine, on its device, drained, behind the owner's own buffers
+    void close()
+    {
+        in.release(); out.release();
+        surf_stage.release();
+        plan_release(plan);
+        laps.release();
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        for (hipStream_t st : side_streams) (void)hipStreamDestroy(st);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// the sync / timer entry points of both owners (a null engine is refused by the owner's name)
+static int engine_enter(EngineCore *e, const char *owner) { return e ? use_device(e->device) : fail(BEVW_E_INVALID, "null %s", owner); }
+static int engine_sync(EngineCore *e, const char *owner)
+{
+    BEVW_TRY(engine_enter(e, owner));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return BEVW_OK;
+}
+static int engine_timer_start(EngineCore *e, const char *owner)
+{
+    BEVW_TRY(engine_enter(e, owner));
+    HIP_TRY(hipEventRecord(e->ev0, e->stream));
+    return BEVW_OK;
+}
+static int engine_timer_mark(EngineCore *e, const char *owner, int slot)
+{
+    BEVW_TRY(engine_enter(e, owner));
+    return e->laps.mark(slot, e->stream);
+}
+static int engine_timer_between(EngineCore *e, const char *owner, int slot_a, int slot_b, float *elapsed_ms)
+{
+    BEVW_TRY(engine_enter(e, owner));
+    return e->laps.between(slot_a, slot_b, elapsed_ms);
+}
+static int engine_timer_stop(EngineCore *e, float *elapsed_ms)
+{
+    if (!e || !elapsed_ms) return fail(BEVW_E_INVALID, "null argument");
+    BEVW_TRY(use_device(e->device));
+    HIP_TRY(hipEventRecord(e->ev1, e->stream));
+    HIP_TRY(hipEventSynchronize(e->ev1));
+    HIP_TRY(hipEventElapsedTime(elapsed_ms, e->ev0, e->ev1));
+    return BEVW_OK;
+}
+
+// The three format setters of an engine, behind the owner's own preconditions: with every stream idle (the plan's format and its group lists
+// are read at launch: no step of the old format or pitch is still queued) the field takes its value and the plan, if live, follows.
+static int engine_set(EngineCore &e, int EngineCore::*field, int value, bool plan_live)
+{
+    BEVW_TRY(use_device(e.device));
+    BEVW_TRY(e.drain());
+    e.*field = value;
+    if (!e.nv12()) e.in_pitch_request = 0;   // (only NV12 frames have a pitch: the others are dense)
+    if (plan_live) BEVW_TRY(e.apply_format());
+    return BEVW_OK;
+}
+
+// what an input format asks of the engine's frame size
+static int check_input_format(const EngineCore &e, int format)
+{
+    if (!input_format_known(format)) return fail(BEVW_E_INVALID, "unknown input format %d", format);
+    if (format == BEVW_INPUT_NV12 && (e.fw % 2 || e.fh % 2))
+        return fail(BEVW_E_INVALID, "NV12 needs an even %s width and height, got %dx%d", e.nouns->frame, e.fw, e.fh);
+    if (src_is_yuv422((SrcFormat)format) && e.fw % 2)   // (packed 4:2:2 shares chroma inside a row only: the height is free)
+        return fail(BEVW_E_INVALID, "%s needs an even %s width, got %dx%d", input_format_name(format), e.nouns->frame, e.fw, e.fh);
+    return BEVW_OK;
+}
+
+// the surface entry points: NV12 input, and rows of whole dwords
+static int need_surface_input(const EngineCore &e)
+{
+    if (!e.nv12())
+        return fail(BEVW_E_INVALID, "surfaces are NV12: the %s's input format is %s (%sinput_format)", e.nouns->owner, input_format_name(e.input_format), e.nouns->setters);
+    if (e.in_pitch() % 4 != 0)   // (a frame width that is even but not a multiple of 4: the default pitch, the width, does not serve)
+        return fail(BEVW_E_INVALID, "%s %d is not a multiple of 4: surfaces need an input pitch that is (%sinput_pitch)", e.nouns->width, e.fw, e.nouns->setters);
+    return BEVW_OK;
+}
+
+// the packed entry points on an engine with a padded input pitch: refused before anything is reserved or enqueued
+static int need_packed_frames(const EngineCore &e)
+{
+    if (e.in_pitch() != e.fw)
+        return fail(BEVW_E_INVALID, "the %s's input pitch is %d, not %s %d: its %ss are NV12 surfaces, use %s", e.nouns->owner, e.in_pitch(), e.nouns->width,
+                    e.fw, e.nouns->frame, e.nouns->surface_calls);
+    return BEVW_OK;
+}
+
+// A step on a caller's HOST table of `batch` x cams surfaces: the table is staged (SurfStage), step(device table) runs, and the slot's event is
+// recorded behind whatever was enqueued, whether or not the step failed: the slot's table stays until then.
+template <typename Step>
+static int engine_staged_step(EngineCore &e, const bevw_nv12_surface *surfaces, int batch, Step &&step)
+{
+    const Nv12Surface *d_surf = nullptr;
+    int slot = 0;
+    BEVW_TRY(e.surf_stage.stage(e.stream, surfaces, (size_t)batch * e.cams, d_surf, slot));
+    const int s = step(d_surf);
+    BEVW_TRY(e.surf_stage.done(e.stream, slot));
+    return s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// bevw_remapper
+// ---------------------------------------------------------------------------------------------------------------
+static const EngineNouns kRemapperNouns = {"remapper", "the source width", "source", "bevw_remapper_set_", "bevw_remap_surfaces_device"};
+struct bevw_remapper : EngineCore {
+    int dw = 0, dh = 0;   // (the source size: EngineCore::fw, fh)
+    DevBuf map1, map2, ones;
+    // the plan: a single-image contributor plan (same kernels as the BEV stitch, one frame per set)
     bool plan_ready = false;
     int ties_even = 0;    // BEVW_COMPAT_REMAP at creation: half-to-even ties -> the per-pixel kernel (the plan's arithmetic rounds half up)
-    int input_format = BEVW_INPUT_BGR;   // bevw_remapper_set_input_format
-    bool nv12() const { return input_format == BEVW_INPUT_NV12; }
-    SrcFormat fmt() const { return (SrcFormat)input_format; }
-    int output_format = BEVW_OUTPUT_BGR; // bevw_remapper_set_output_format
-    bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
-    int in_pitch_request = 0;            // bevw_remapper_set_input_pitch (0: the source width)
-    int in_pitch() const { return in_pitch_request ? in_pitch_request : sw; }
-    SurfStage surf_stage;                // bevw_remap_surfaces_device
-    // the sources of a step: packed images behind d_src, or (d_surf) a device table of NV12 surfaces with rows of in_pitch() bytes
-    FrameSource source(const uint8_t *d_src, const Nv12Surface *d_surf) const { return {d_surf ? nullptr : d_src, d_surf, d_surf ? in_pitch() : 0, fmt(), 1}; }
-    int apply_format() { return plan_set_format(plan, fmt(), out_nv12(), nv12() ? in_pitch() : 0); }
 };
 
 // cv2.remap as a 1-camera stitch: every destination pixel has exactly one contributor with mask 255.
 static int remapper_build_plan(bevw_remapper *r)
 {
-    static const int use_plan = [] { const char *s = getenv("BEVW_REMAP_PLAN"); return s ? atoi(s) : 1; }();
+    static const int use_plan = env_int("BEVW_REMAP_PLAN", 1);
     r->plan_ready = false;
     if (!use_plan || r->ties_even) return BEVW_OK;
     const size_t npx = (size_t)r->dw * r->dh;
@@ -369,7 +503,7 @@ static int remapper_build_plan(bevw_remapper *r)
     HIP_TRY(hipMemsetAsync(r->ones.p, 0xff, npx, r->stream));
     StitchTables T;
     for (int i = 0; i < 4; ++i) { T.lut1[i] = r->map1.as<int16_t>(); T.lut2[i] = r->map2.as<uint16_t>(); T.mask[i] = r->ones.as<uint8_t>(); }
-    BEVW_TRY(plan_build(r->plan, r->stream, T, r->sw, r->sh, r->dw, r->dh, 1, 0, false));
+    BEVW_TRY(plan_build(r->plan, r->stream, T, r->fw, r->fh, r->dw, r->dh, 1, 0, false));
     r->ones.release();
     r->plan_ready = r->plan.usable;
     return BEVW_OK;
@@ -384,14 +518,21 @@ static int remapper_alloc(int device, int sw, int sh, int dw, int dh, bevw_remap
     BEVW_TRY(use_device(device));
     bevw_remapper *r = new (std::nothrow) bevw_remapper();
     if (!r) return fail(BEVW_E_NOMEM, "out of host memory");
-    r->device = device; r->sw = sw; r->sh = sh; r->dw = dw; r->dh = dh;
+    r->nouns = &kRemapperNouns; r->device = device; r->fw = sw; r->fh = sh; r->cams = 1; r->dw = dw; r->dh = dh;
     r->ties_even = g_compat[BEVW_COMPAT_REMAP].load();
     int s = BEVW_OK;
-    if (hipStreamCreate(&r->stream) != hipSuccess || hipEventCreate(&r->ev0) != hipSuccess ||
-        hipEventCreate(&r->ev1) != hipSuccess)
-        s = fail(BEVW_E_HIP, "stream/event creation failed");
+    if (!r->open()) s = fail(BEVW_E_HIP, "stream/event creation failed");
     if (s == BEVW_OK) s = r->map1.reserve((size_t)dw * dh * 2 * sizeof(int16_t));
     if (s == BEVW_OK) s = r->map2.reserve((size_t)dw * dh * sizeof(uint16_t));
+    if (s != BEVW_OK) { bevw_remapper_destroy(r); return s; }
+    *out = r;
+    return BEVW_OK;
+}
+
+// the end of the three constructors: the maps are made (status s), the plan follows; a remapper that fails is destroyed
+static int remapper_finish(bevw_remapper *r, int s, bevw_remapper **out)
+{
+    if (s == BEVW_OK) s = remapper_build_plan(r);
     if (s != BEVW_OK) { bevw_remapper_destroy(r); return s; }
     *out = r;
     return BEVW_OK;
@@ -536,10 +677,7 @@ int bevw_fisheye_remapper_create(int device, int frame_width, int frame_height, 
     double Kd[9];
     camera_mat_dst(K, frame_width, frame_height, focal_scale, size_scale, offset_h, offset_v, Kd);
     int s = build_fisheye_maps(r->stream, K, D, Kd, dw, dh, r->map1.as<int16_t>(), r->map2.as<uint16_t>());
-    if (s == BEVW_OK) s = remapper_build_plan(r);
-    if (s != BEVW_OK) { bevw_remapper_destroy(r); return s; }
-    *out = r;
-    return BEVW_OK;
+    return remapper_finish(r, s, out);
 }
 
 int bevw_pinhole_remapper_create(int device, int frame_width, int frame_height, const double K[9], const double *D, int n_dist,
@@ -554,10 +692,7 @@ int bevw_pinhole_remapper_create(int device, int frame_width, int frame_height, 
     for (int i = 0; i < n_dist; ++i) d8[i] = D[i];
     camera_mat_dst(K, frame_width, frame_height, focal_scale, size_scale, offset_h, offset_v, Kd);
     int s = build_pinhole_maps(r->stream, K, d8, Kd, dw, dh, r->map1.as<int16_t>(), r->map2.as<uint16_t>());
-    if (s == BEVW_OK) s = remapper_build_plan(r);
-    if (s != BEVW_OK) { bevw_remapper_destroy(r); return s; }
-    *out = r;
-    return BEVW_OK;
+    return remapper_finish(r, s, out);
 }
 
 int bevw_remapper_from_maps(int device, int src_w, int src_h, const int16_t *map1, const uint16_t *map2, int dst_w,
@@ -569,16 +704,13 @@ int bevw_remapper_from_maps(int device, int src_w, int src_h, const int16_t *map
     hipError_t e = hipMemcpy(r->map1.p, map1, (size_t)dst_w * dst_h * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(r->map2.p, map2, (size_t)dst_w * dst_h * 2, hipMemcpyHostToDevice);
     if (e != hipSuccess) { bevw_remapper_destroy(r); return fail(BEVW_E_HIP, "map upload failed: %s", hipGetErrorString(e)); }
-    int s = remapper_build_plan(r);
-    if (s != BEVW_OK) { bevw_remapper_destroy(r); return s; }
-    *out = r;
-    return BEVW_OK;
+    return remapper_finish(r, BEVW_OK, out);
 }
 
 int bevw_remapper_dims(bevw_remapper *r, int32_t dims[4])
 {
     if (!r || !dims) return fail(BEVW_E_INVALID, "null argument");
-    dims[0] = r->sw; dims[1] = r->sh; dims[2] = r->dw; dims[3] = r->dh;
+    dims[0] = r->fw; dims[1] = r->fh; dims[2] = r->dw; dims[3] = r->dh;
     return BEVW_OK;
 }
 
@@ -595,22 +727,8 @@ int bevw_remapper_get_maps(bevw_remapper *r, int16_t *map1, uint16_t *map2)
 int bevw_remapper_set_input_pitch(bevw_remapper *r, int pitch_bytes)
 {
     if (!r) return fail(BEVW_E_INVALID, "null remapper");
-    BEVW_TRY(check_input_pitch(pitch_bytes, r->sw, r->sh, r->nv12()));
-    BEVW_TRY(use_device(r->device));
-    HIP_TRY(hipStreamSynchronize(r->stream));   // (the group lists are read at launch: no step with the old pitch is still queued)
-    r->in_pitch_request = pitch_bytes;
-    if (r->plan_ready) BEVW_TRY(r->apply_format());
-    return BEVW_OK;
-}
-
-// the checks the two surface entry points of a remapper share
-static int remap_need_surfaces(bevw_remapper *r, const void *table, int batch, void *d_dst)
-{
-    if (!r || !table || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
-    if (!r->nv12()) return fail(BEVW_E_INVALID, "surfaces are NV12: the remapper's input format is %s (bevw_remapper_set_input_format)", input_format_name(r->input_format));
-    if (r->in_pitch() % 4 != 0)
-        return fail(BEVW_E_INVALID, "the source width %d is not a multiple of 4: surfaces need an input pitch that is (bevw_remapper_set_input_pitch)", r->sw);
-    return BEVW_OK;
+    BEVW_TRY(check_input_pitch(pitch_bytes, r->fw, r->fh, r->nv12()));
+    return engine_set(*r, &EngineCore::in_pitch_request, pitch_bytes, r->plan_ready);
 }
 
 // one remap step: the plan, or the per-pixel kernel (NV12 images on the plan need dword-aligned quads in the caller's rows, dw % 4 == 0)
@@ -622,13 +740,14 @@ static int remap_step(bevw_remapper *r, const FrameSource &src, int batch, void 
         step.src = src; step.batch = batch; step.out = (uint8_t *)d_dst;
         return plan_stitch(r->plan, r->stream, step);
     }
-    return remap_launch(r->stream, src, r->sw, r->sh, r->map1.as<int16_t>(), r->map2.as<uint16_t>(), r->dw, r->dh, batch, (uint8_t *)d_dst,
+    return remap_launch(r->stream, src, r->fw, r->fh, r->map1.as<int16_t>(), r->map2.as<uint16_t>(), r->dw, r->dh, batch, (uint8_t *)d_dst,
                         r->ties_even, r->out_nv12());
 }
 
 int bevw_remap_surface_table_device(bevw_remapper *r, const void *d_surfaces, int batch, void *d_dst)
 {
-    BEVW_TRY(remap_need_surfaces(r, d_surfaces, batch, d_dst));
+    if (!r || !d_surfaces || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
+    BEVW_TRY(need_surface_input(*r));
     if (((uintptr_t)d_surfaces) & 7u) return fail(BEVW_E_INVALID, "the surface table is not 8-byte aligned");
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
@@ -637,23 +756,17 @@ int bevw_remap_surface_table_device(bevw_remapper *r, const void *d_surfaces, in
 
 int bevw_remap_surfaces_device(bevw_remapper *r, const bevw_nv12_surface *surfaces, int batch, void *d_dst)
 {
-    BEVW_TRY(remap_need_surfaces(r, surfaces, batch, d_dst));
+    if (!r || !surfaces || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
+    BEVW_TRY(need_surface_input(*r));
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
-    const Nv12Surface *d_surf = nullptr;
-    int slot = 0;
-    BEVW_TRY(r->surf_stage.stage(r->stream, surfaces, (size_t)batch, d_surf, slot));
-    const int s = remap_step(r, r->source(nullptr, d_surf), batch, d_dst);
-    BEVW_TRY(r->surf_stage.done(r->stream, slot));   // (whether or not the step failed: the slot's table stays until then)
-    return s;
+    return engine_staged_step(*r, surfaces, batch, [&](const Nv12Surface *d_surf) { return remap_step(r, r->source(nullptr, d_surf), batch, d_dst); });
 }
 
 int bevw_remap_device(bevw_remapper *r, const void *d_src, int batch, void *d_dst)
 {
     if (!r || !d_src || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
-    if (r->in_pitch() != r->sw)
-        return fail(BEVW_E_INVALID, "the remapper's input pitch is %d, not the source width %d: its sources are NV12 surfaces, use bevw_remap_surfaces_device",
-                    r->in_pitch(), r->sw);
+    BEVW_TRY(need_packed_frames(*r));
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
     return remap_step(r, r->source((const uint8_t *)d_src, nullptr), batch, d_dst);
@@ -665,38 +778,23 @@ int bevw_remapper_set_output_format(bevw_remapper *r, int format)
     if (format != BEVW_OUTPUT_BGR && format != BEVW_OUTPUT_NV12) return fail(BEVW_E_INVALID, "unknown output format %d", format);
     if (format == BEVW_OUTPUT_NV12 && (r->dw % 2 || r->dh % 2))
         return fail(BEVW_E_INVALID, "NV12 output needs an even destination width and height, got %dx%d", r->dw, r->dh);
-    BEVW_TRY(use_device(r->device));
-    HIP_TRY(hipStreamSynchronize(r->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
-    r->output_format = format;
-    if (r->plan_ready) BEVW_TRY(r->apply_format());
-    return BEVW_OK;
+    return engine_set(*r, &EngineCore::output_format, format, r->plan_ready);
 }
 
 int bevw_remapper_set_input_format(bevw_remapper *r, int format)
 {
     if (!r) return fail(BEVW_E_INVALID, "null remapper");
-    if (!input_format_known(format)) return fail(BEVW_E_INVALID, "unknown input format %d", format);
-    if (format == BEVW_INPUT_NV12 && (r->sw % 2 || r->sh % 2))
-        return fail(BEVW_E_INVALID, "NV12 needs an even source width and height, got %dx%d", r->sw, r->sh);
-    if (src_is_yuv422((SrcFormat)format) && r->sw % 2)
-        return fail(BEVW_E_INVALID, "%s needs an even source width, got %dx%d", input_format_name(format), r->sw, r->sh);
-    BEVW_TRY(use_device(r->device));
-    HIP_TRY(hipStreamSynchronize(r->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
-    r->input_format = format;
-    if (!r->nv12()) r->in_pitch_request = 0;   // (BGR sources are dense)
-    if (r->plan_ready) BEVW_TRY(r->apply_format());
-    return BEVW_OK;
+    BEVW_TRY(check_input_format(*r, format));
+    return engine_set(*r, &EngineCore::input_format, format, r->plan_ready);
 }
 
 int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst)
 {
     if (!r || !src || !dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
-    if (r->in_pitch() != r->sw)
-        return fail(BEVW_E_INVALID, "the remapper's input pitch is %d, not the source width %d: its sources are NV12 surfaces, use bevw_remap_surfaces_device",
-                    r->in_pitch(), r->sw);
+    BEVW_TRY(need_packed_frames(*r));
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
-    const size_t nin = (size_t)batch * frame_bytes_of(r->sw, r->sh, r->fmt()), nout = (size_t)batch * image_bytes_of(r->dw, r->dh, r->out_nv12());
+    const size_t nin = (size_t)batch * frame_bytes_of(r->fw, r->fh, r->fmt()), nout = (size_t)batch * image_bytes_of(r->dw, r->dh, r->out_nv12());
     BEVW_TRY(r->in.reserve(nin));
     BEVW_TRY(r->out.reserve(nout));
     HIP_TRY(hipMemcpyAsync(r->in.p, src, nin, hipMemcpyHostToDevice, r->stream));
@@ -706,54 +804,19 @@ int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst)
     return BEVW_OK;
 }
 
-int bevw_remapper_sync(bevw_remapper *r)
-{
-    if (!r) return fail(BEVW_E_INVALID, "null remapper");
-    BEVW_TRY(use_device(r->device));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    return BEVW_OK;
-}
-int bevw_remapper_timer_start(bevw_remapper *r)
-{
-    if (!r) return fail(BEVW_E_INVALID, "null remapper");
-    BEVW_TRY(use_device(r->device));
-    HIP_TRY(hipEventRecord(r->ev0, r->stream));
-    return BEVW_OK;
-}
-int bevw_remapper_timer_mark(bevw_remapper *r, int slot)
-{
-    if (!r) return fail(BEVW_E_INVALID, "null remapper");
-    BEVW_TRY(use_device(r->device));
-    return r->laps.mark(slot, r->stream);
-}
-int bevw_remapper_timer_between(bevw_remapper *r, int slot_a, int slot_b, float *elapsed_ms)
-{
-    if (!r) return fail(BEVW_E_INVALID, "null remapper");
-    BEVW_TRY(use_device(r->device));
-    return r->laps.between(slot_a, slot_b, elapsed_ms);
-}
-int bevw_remapper_timer_stop(bevw_remapper *r, float *elapsed_ms)
-{
-    if (!r || !elapsed_ms) return fail(BEVW_E_INVALID, "null argument");
-    BEVW_TRY(use_device(r->device));
-    HIP_TRY(hipEventRecord(r->ev1, r->stream));
-    HIP_TRY(hipEventSynchronize(r->ev1));
-    HIP_TRY(hipEventElapsedTime(elapsed_ms, r->ev0, r->ev1));
-    return BEVW_OK;
-}
+int bevw_remapper_sync(bevw_remapper *r) { return engine_sync(r, "remapper"); }
+int bevw_remapper_timer_start(bevw_remapper *r) { return engine_timer_start(r, "remapper"); }
+int bevw_remapper_timer_mark(bevw_remapper *r, int slot) { return engine_timer_mark(r, "remapper", slot); }
+int bevw_remapper_timer_between(bevw_remapper *r, int slot_a, int slot_b, float *elapsed_ms) { return engine_timer_between(r, "remapper", slot_a, slot_b, elapsed_ms); }
+int bevw_remapper_timer_stop(bevw_remapper *r, float *elapsed_ms) { return engine_timer_stop(r, elapsed_ms); }
 
 void bevw_remapper_destroy(bevw_remapper *r)
 {
     if (!r) return;
     if (hipSetDevice(r->device) == hipSuccess) {
-        if (r->stream) (void)hipStreamSynchronize(r->stream);
-        r->map1.release(); r->map2.release(); r->in.release(); r->out.release(); r->ones.release();
-        r->surf_stage.release();
-        plan_release(r->plan);
-        r->laps.release();
-        if (r->ev0) (void)hipEventDestroy(r->ev0);
-        if (r->ev1) (void)hipEventDestroy(r->ev1);
-        if (r->stream) (void)hipStreamDestroy(r->stream);
+        if (r->stream) (void)r->drain();
+        r->map1.release(); r->map2.release(); r->ones.release();
+        r->close();
     }
     delete r;
 }
@@ -837,47 +900,31 @@ int bevw_resize_linear_u8c3(int device, const uint8_t *src, int src_w, int src_h
 // ---------------------------------------------------------------------------------------------------------------
 // bevw_handle
 // ---------------------------------------------------------------------------------------------------------------
-struct bevw_handle {
-    bevw_config cfg;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;    // balance: the odd slices of a batch (balance_plan_run)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+static const EngineNouns kHandleNouns = {"handle", "FRAME_WIDTH", "frame", "bevw_set_", "bevw_run_surfaces_device or bevw_run_surface_table_device"};
+struct bevw_handle : EngineCore {
+    bevw_config cfg;                  // (EngineCore::device, fw, fh repeat its device and frame size)
+    hipStream_t stream2 = nullptr;    // balance: the odd slices of a batch (balance_plan_run); one of the core's side streams
     hipEvent_t ev_fork = nullptr, ev_skew = nullptr, ev_join = nullptr;
-    LapTimer laps;
     bool cam_set[4] = {false, false, false, false};
     double K[4][9], D[4][4], H[4][9];
     bool built = false;
     int uw = 0, uh = 0;
     DevBuf und1[4], und2[4], lut1[4], lut2[4], mask[4];
     DevBuf hsv, vsums, deltas, chsums;
-    DevBuf in, out, car, tmp;
+    DevBuf car, tmp;
     DevBuf pre;           // balance: the pre-gain BEV (the gain pass runs out of place)
-    Plan plan;
     int schedule_in_use = BEVW_SCHED_PER_PIXEL;
     int projection = BEVW_PROJ_LUT;   // bevw_set_projection
-    int input_format = BEVW_INPUT_BGR;   // bevw_set_input_format
-    bool nv12() const { return input_format == BEVW_INPUT_NV12; }
-    SrcFormat fmt() const { return (SrcFormat)input_format; }
-    bool yuv422() const { return src_is_yuv422(fmt()); }   // packed 4:2:2: YUYV / UYVY
     size_t set_bytes() const { return frame_bytes_of(cfg.frame_width, cfg.frame_height, fmt()) * 4; }   // one camera frame set as the handle reads it
-    int in_pitch_request = 0;            // bevw_set_input_pitch (0: the frame width)
-    int in_pitch() const { return in_pitch_request ? in_pitch_request : cfg.frame_width; }   // bytes between the rows of an NV12 surface
-    SurfStage surf_stage;                // bevw_run_surfaces_device
-    int output_format = BEVW_OUTPUT_BGR;   // bevw_set_output_format
-    bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
     int compat[BEVW_COMPAT_KEYS] = {1, 1, 0, 0};   // bevw_set_compat values at bevw_build: a handle keeps the arithmetic it was built with
     int pitch_request = BEVW_PITCH_DENSE;   // bevw_set_output_pitch
     int pitch_px = 0;                 // pixels per row of the device-side BEV images (== bev_width unless a pitch was requested)
     size_t out_image_bytes() const { return image_bytes_of(pitch_px, cfg.bev_height, out_nv12()); }   // one device-side BEV image
-    // the frames of a step: packed frame sets behind d_frames, or (d_surf) a device table surf[frame set][4] of NV12 surfaces, read in place
-    FrameSource source(const uint8_t *d_frames, const Nv12Surface *d_surf) const { return {d_surf ? nullptr : d_frames, d_surf, d_surf ? in_pitch() : 0, fmt(), shard_n ? shard_n : 4}; }
-    // the plan follows the handle's formats (bevw_build behind plan_build; the setters of a built handle, with its streams idle)
-    int apply_format() { return plan_set_format(plan, fmt(), out_nv12(), nv12() ? in_pitch() : 0); }
     DevBuf car_pitched;               // the car sprite with rows of pitch_px pixels (gain pass of a pitched handle)
     AnalyticRig arig;                 // filled by bevw_build
     Plan aplan;                       // analytic modes: the WIDE unit schedule compiled from the projection (analytic_units_build)
     int aplan_mode = -1;              // the projection mode aplan was compiled for (-1: none yet)
-    // camera-per-GPU mode: the cameras this handle owns (shard_n == 0: all four, the ordinary BevGenerator)
+    // camera-per-GPU mode: the cameras this handle owns (shard_n == 0: all four, the ordinary BevGenerator; else EngineCore::cams == shard_n)
     int shard_n = 0;
     int shard_cams[4] = {0, 1, 2, 3};
     int shard_box[4] = {0, 0, 0, 0};   // x0, y0, x1, y1: bounding box of the owned masks
@@ -970,7 +1017,7 @@ static int analytic_units_build(bevw_handle *h)
     const bevw_config &c = h->cfg;
     plan_release(h->aplan);
     h->aplan_mode = h->projection;
-    static const int units_env = [] { const char *s = getenv("BEVW_ANALYTIC_UNITS"); return s ? atoi(s) : 1; }();
+    static const int units_env = env_int("BEVW_ANALYTIC_UNITS", 1);
     const int fw = c.frame_width, fh = c.frame_height, bw = c.bev_width, bh = c.bev_height;
     if (!units_env || bw % 4 != 0 || fw % 4 != 0 || (size_t)fw * fh * 12 >= (1ull << 31) || fw > 32767 || fh > 32767) return BEVW_OK;
     const size_t bpx = (size_t)bw * bh;
@@ -1018,7 +1065,7 @@ static int stitch_analytic(bevw_handle *h, const uint8_t *d_frames, int batch, c
     unsigned long long *chs = h->chsums.as<unsigned long long>();
     // frames a thread samples with one evaluation of the projection (BEVW_ANALYTIC_FRAMES, read once per process; 1 = the projection per
     // output pixel AND frame: bench.py's direct_stitch_analytic_perpixel_b64)
-    static const int fpt_env = [] { const char *s = getenv("BEVW_ANALYTIC_FRAMES"); return s ? atoi(s) : 0; }();
+    static const int fpt_env = env_int("BEVW_ANALYTIC_FRAMES", 0);
     const int fpt = fpt_env >= 1 && fpt_env <= 1024 ? fpt_env : kAnalyticFrames;
     const bool f32 = h->projection == BEVW_PROJ_ANALYTIC_F32;
     const int tiles_x = h->aplan.tiles_x;
@@ -1136,6 +1183,14 @@ static int gain_car(bevw_handle *h, const uint8_t *d_car, const uint8_t *&car)
     return BEVW_OK;
 }
 
+// balance schedule of the tile plan (BEVW_BAL_MODE): 1 = shift the sampled texel groups of the raw frames once (k_lum_groups), then the units;
+// 0 = luminance round trip per fetched texel inside the per-tap kernel
+static int bal_mode()
+{
+    static const int mode = env_int("BEVW_BAL_MODE", 1);
+    return mode;
+}
+
 // blend + balance on the tile plan (BASELINE config 4), `parts` slices of the batch alternating over the handle's two streams.
 // Per slice: V sums of the raw frames (k_vsum: HBM-bound, reads every byte of the four frames) -> deltas -> luminance round trip of the
 // sampled texel groups into the compact scratch (k_lum_groups: balanced between its 1.3 GB and its arithmetic) -> the unit stitch with per-unit channel sums
@@ -1151,8 +1206,8 @@ static int balance_plan_run(bevw_handle *h, const FrameSource &src, int batch, c
     const size_t npx = (size_t)h->pitch_px * c.bev_height;
     BEVW_TRY(ensure_stats(h, batch));
     const size_t cstride = h->plan.compact_stride;   // the compact scratch: only the sampled texel groups of a frame set (bevw_unit.h: unit_gsrc_compact)
-    static const int parts_env = [] { const char *s = getenv("BEVW_BAL_PARTS"); return s ? atoi(s) : 0; }();
-    static const int skew_env = [] { const char *s = getenv("BEVW_BAL_SKEW"); return s ? atoi(s) : 0; }();
+    static const int parts_env = env_int("BEVW_BAL_PARTS", 0);
+    static const int skew_env = env_int("BEVW_BAL_SKEW", 0);
     // slices share the plan's padded scratch image when the BEV width is not a multiple of 4 pixels: one slice then
     const bool scratch = h->plan.pitch != h->plan.bw && !h->plan.out_pitched;
     // measured (profiles/r04/ab_config4_slices.log, batch 256): 1 slice 2.172 ms, 2 slices 2.142 (2.171 with the second stream one V-sum pass late),
@@ -1161,11 +1216,11 @@ static int balance_plan_run(bevw_handle *h, const FrameSource &src, int batch, c
     int parts = parts_env > 0 ? parts_env : (batch >= 32 ? 2 : 1);
     if (scratch) parts = 1;
     if (parts > batch) parts = batch;
-    if (parts > 1 && !h->stream2 && hipStreamCreate(&h->stream2) != hipSuccess) { (void)hipGetLastError(); h->stream2 = nullptr; parts = 1; }
+    if (parts > 1 && !h->stream2 && !h->add_stream(&h->stream2)) parts = 1;
     // BEVW_BAL_RING=1 (A/B of round 6, profiles/r06/README.md): the two intermediate buffers of a slice -- the compact scratch of shifted texel
     // groups and the pre-gain BEV -- belong to the STREAM, not to the frame sets: slice k reuses the addresses of slice k - 2, so that with
     // slices small enough both stay in the 256 MB Infinity Cache between their writer and their reader and are overwritten there
-    static const int ring_env = [] { const char *s = getenv("BEVW_BAL_RING"); return s ? atoi(s) : 0; }();
+    static const int ring_env = env_int("BEVW_BAL_RING", 0);
     const bool ring = ring_env != 0 && parts > 2;
     const int slice_max = (batch + parts - 1) / parts;
     const size_t slots = ring ? (size_t)2 * slice_max : (size_t)batch;
@@ -1173,7 +1228,7 @@ static int balance_plan_run(bevw_handle *h, const FrameSource &src, int batch, c
     // the gain pass reads the pre-gain BEV from a buffer of its own instead of rewriting the output in place: a read stream
     // and a write stream instead of one read-modify-write stream (config 4 2.108 -> 2.052 ms, profiles/r02/sweeps.log); costs
     // one more BEV batch of HBM (0.9 GB at batch 256).  No room for it: the gain pass runs in place -- never an error
-    static const int oop = [] { const char *s = getenv("BEVW_GAIN_OOP"); return s ? atoi(s) : 1; }();
+    static const int oop = env_int("BEVW_GAIN_OOP", 1);
     uint8_t *gain_in = d_out;
     if (h->out_nv12()) {   // NV12 images: the BGR pre-gain image never fits the caller's buffer -- always a buffer of its own
         BEVW_TRY(h->pre.reserve(npx * 3 * slots));
@@ -1228,10 +1283,7 @@ static int run_device(bevw_handle *h, const FrameSource &src, int batch, const u
     const bool aligned4 = (((uintptr_t)d_out | (uintptr_t)d_car) & 3u) == 0 && src.aligned4();
     if (pitched && (h->projection != BEVW_PROJ_LUT || h->schedule_in_use != BEVW_SCHED_TILE_PLAN || !aligned4))
         return fail(BEVW_E_INVALID, "an output pitch needs the tile-plan schedule, the table projection and 4-byte aligned buffers");
-    // balance schedule of the tile plan: 1 = shift the sampled texel groups of the raw frames once (k_lum_groups), then the units;
-    // 0 = luminance round trip per fetched texel inside the per-tap kernel
-    static const int bal_mode = [] { const char *s = getenv("BEVW_BAL_MODE"); return s ? atoi(s) : 1; }();
-    if (h->projection == BEVW_PROJ_LUT && h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && c.balance && bal_mode == 1 && h->plan.compact_stride != 0)
+    if (h->projection == BEVW_PROJ_LUT && h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && c.balance && bal_mode() == 1 && h->plan.compact_stride != 0)
         return balance_plan_run(h, src, batch, d_car, d_out);
     if (c.balance) {
         BEVW_TRY(ensure_stats(h, batch));
@@ -1285,10 +1337,10 @@ int bevw_create(const bevw_config *cfg, bevw_handle **out)
     bevw_handle *h = new (std::nothrow) bevw_handle();
     if (!h) return fail(BEVW_E_NOMEM, "out of host memory");
     h->cfg = *cfg;
+    h->nouns = &kHandleNouns; h->device = cfg->device; h->fw = cfg->frame_width; h->fh = cfg->frame_height;
     // (stream2 is created by the first balance step that wants it: HIP multiplexes a process's streams onto a handful of hardware queues --
     // 4 by default -- and every stream that merely exists makes it likelier that two streams meant to overlap share one)
-    if (hipStreamCreate(&h->stream) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess ||
-        hipEventCreate(&h->ev1) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
+    if (!h->open() || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_skew, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
         bevw_destroy(h);
         return fail(BEVW_E_HIP, "stream/event creation failed");
@@ -1447,22 +1499,15 @@ void bevw_destroy(bevw_handle *h)
 {
     if (!h) return;
     if (hipSetDevice(h->cfg.device) == hipSuccess) {
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        if (h->stream) (void)h->drain();
         for (int c = 0; c < 4; ++c) {
             h->und1[c].release(); h->und2[c].release(); h->lut1[c].release(); h->lut2[c].release(); h->mask[c].release();
         }
         h->hsv.release(); h->vsums.release(); h->deltas.release(); h->chsums.release(); h->sdeltas.release();
-        h->in.release(); h->out.release(); h->car.release(); h->tmp.release(); h->pre.release(); h->car_pitched.release();
-        if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-        h->surf_stage.release();
-        plan_release(h->plan);
+        h->car.release(); h->tmp.release(); h->pre.release(); h->car_pitched.release(); h->xchg.release();
         plan_release(h->aplan);
-        h->laps.release();
-        if (h->ev0) (void)hipEventDestroy(h->ev0);
-        if (h->ev1) (void)hipEventDestroy(h->ev1);
         for (hipEvent_t e : {h->ev_fork, h->ev_skew, h->ev_join}) if (e) (void)hipEventDestroy(e);
-        if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
-        if (h->stream) (void)hipStreamDestroy(h->stream);
+        h->close();
     }
     delete h;
 }
@@ -1552,36 +1597,20 @@ int bevw_output_pitch(bevw_handle *h)
 int bevw_set_input_format(bevw_handle *h, int format)
 {
     if (!h) return fail(BEVW_E_INVALID, "null handle");
-    if (!input_format_known(format)) return fail(BEVW_E_INVALID, "unknown input format %d", format);
+    BEVW_TRY(check_input_format(*h, format));
     if (format != BEVW_INPUT_BGR) {
-        const bevw_config &c = h->cfg;
         const char *name = input_format_name(format);
-        if (format == BEVW_INPUT_NV12 && (c.frame_width % 2 || c.frame_height % 2))
-            return fail(BEVW_E_INVALID, "NV12 needs an even frame width and height, got %dx%d", c.frame_width, c.frame_height);
-        if (format != BEVW_INPUT_NV12 && c.frame_width % 2)   // (packed 4:2:2 shares chroma inside a row only: the height is free)
-            return fail(BEVW_E_INVALID, "%s needs an even frame width, got %dx%d", name, c.frame_width, c.frame_height);
         if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "%s input is not available with the analytic projection", name);
         if (h->shard_n) return fail(BEVW_E_INVALID, "%s input is not available on camera-shard handles", name);
     }
-    BEVW_TRY(use_device(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
-    if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
-    h->input_format = format;
-    if (!h->nv12()) h->in_pitch_request = 0;   // (BGR frames are dense)
-    if (h->built) BEVW_TRY(h->apply_format());
-    return BEVW_OK;
+    return engine_set(*h, &EngineCore::input_format, format, h->built);
 }
 
 int bevw_set_input_pitch(bevw_handle *h, int pitch_bytes)
 {
     if (!h) return fail(BEVW_E_INVALID, "null handle");
-    BEVW_TRY(check_input_pitch(pitch_bytes, h->cfg.frame_width, h->cfg.frame_height, h->nv12()));
-    BEVW_TRY(use_device(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // (the group lists are read at launch: no step with the old pitch is still queued)
-    if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
-    h->in_pitch_request = pitch_bytes;
-    if (h->built) BEVW_TRY(h->apply_format());
-    return BEVW_OK;
+    BEVW_TRY(check_input_pitch(pitch_bytes, h->fw, h->fh, h->nv12()));
+    return engine_set(*h, &EngineCore::in_pitch_request, pitch_bytes, h->built);
 }
 
 int bevw_input_pitch(bevw_handle *h)
@@ -1607,12 +1636,7 @@ int bevw_set_output_format(bevw_handle *h, int format)
         if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "NV12 output is not available with the analytic projection");
         if (h->shard_n) return fail(BEVW_E_INVALID, "NV12 output is not available on camera-shard handles");
     }
-    BEVW_TRY(use_device(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // (the plan's format is read at launch: no step of the old format is still queued)
-    if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
-    h->output_format = format;
-    if (h->built) BEVW_TRY(h->apply_format());
-    return BEVW_OK;
+    return engine_set(*h, &EngineCore::output_format, format, h->built);
 }
 
 int bevw_output_format(bevw_handle *h)
@@ -1637,21 +1661,12 @@ static int download_images(bevw_handle *h, uint8_t *out, const void *d_src, size
     return BEVW_OK;
 }
 
-// the packed entry points on a handle with a padded input pitch: refused before anything is reserved or enqueued
-static int need_packed_frames(bevw_handle *h)
-{
-    if (h->in_pitch() != h->cfg.frame_width)
-        return fail(BEVW_E_INVALID, "the handle's input pitch is %d, not FRAME_WIDTH %d: its frames are NV12 surfaces, use bevw_run_surfaces_device "
-                    "or bevw_run_surface_table_device", h->in_pitch(), h->cfg.frame_width);
-    return BEVW_OK;
-}
-
 int bevw_run_device(bevw_handle *h, const void *d_frames, int batch, const void *d_car, void *d_out)
 {
     BEVW_TRY(need_built(h));
     if (h->shard_n) return fail(BEVW_E_INVALID, "handle is a camera shard: use bevw_shard_run_device + bevw_combine_device");
     if (!d_frames || !d_out || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
-    BEVW_TRY(need_packed_frames(h));
+    BEVW_TRY(need_packed_frames(*h));
     if (batch == 0) return BEVW_OK;
     return run_device(h, h->source((const uint8_t *)d_frames, nullptr), batch, (const uint8_t *)d_car, (uint8_t *)d_out);
 }
@@ -1660,10 +1675,8 @@ static int need_surfaces(bevw_handle *h, const void *table, int batch, void *d_o
 {
     BEVW_TRY(need_built(h));
     if (h->shard_n) return fail(BEVW_E_INVALID, "NV12 surfaces are not available on camera-shard handles");
-    if (!h->nv12()) return fail(BEVW_E_INVALID, "surfaces are NV12: the handle's input format is %s (bevw_set_input_format)", input_format_name(h->input_format));
+    BEVW_TRY(need_surface_input(*h));
     if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "NV12 surfaces are not available with the analytic projection");
-    if (h->in_pitch() % 4 != 0)   // (a frame width that is even but not a multiple of 4: the default pitch, FRAME_WIDTH, does not serve)
-        return fail(BEVW_E_INVALID, "FRAME_WIDTH %d is not a multiple of 4: surfaces need an input pitch that is (bevw_set_input_pitch)", h->cfg.frame_width);
     if (!table || !d_out || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
     return BEVW_OK;
 }
@@ -1680,12 +1693,9 @@ int bevw_run_surfaces_device(bevw_handle *h, const bevw_nv12_surface *surfaces, 
 {
     BEVW_TRY(need_surfaces(h, surfaces, batch, d_out));
     if (batch == 0) return BEVW_OK;
-    const Nv12Surface *d_surf = nullptr;
-    int slot = 0;
-    BEVW_TRY(h->surf_stage.stage(h->stream, surfaces, (size_t)batch * 4, d_surf, slot));
-    const int s = run_device(h, h->source(nullptr, d_surf), batch, (const uint8_t *)d_car, (uint8_t *)d_out);
-    BEVW_TRY(h->surf_stage.done(h->stream, slot));   // (whether or not the step failed, behind whatever was enqueued: the slot's table stays until then)
-    return s;
+    return engine_staged_step(*h, surfaces, batch, [&](const Nv12Surface *d_surf) {
+        return run_device(h, h->source(nullptr, d_surf), batch, (const uint8_t *)d_car, (uint8_t *)d_out);
+    });
 }
 
 int bevw_run(bevw_handle *h, const uint8_t *frames, int batch, const uint8_t *car, uint8_t *out)
@@ -1693,7 +1703,7 @@ int bevw_run(bevw_handle *h, const uint8_t *frames, int batch, const uint8_t *ca
     BEVW_TRY(need_built(h));
     if (h->shard_n) return fail(BEVW_E_INVALID, "handle is a camera shard: use bevw_shard_run_device + bevw_combine_device");
     if (!frames || !out || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
-    BEVW_TRY(need_packed_frames(h));
+    BEVW_TRY(need_packed_frames(*h));
     if (batch == 0) return BEVW_OK;
     const bevw_config &c = h->cfg;
     const size_t nin = (size_t)batch * h->set_bytes();
@@ -1720,7 +1730,7 @@ int bevw_run_cameras(bevw_handle *h, const uint8_t *front, const uint8_t *back, 
     BEVW_TRY(need_built(h));
     if (h->shard_n) return fail(BEVW_E_INVALID, "handle is a camera shard: use bevw_shard_run_device + bevw_combine_device");
     if (!front || !back || !left || !right || !out) return fail(BEVW_E_INVALID, "bad argument");
-    BEVW_TRY(need_packed_frames(h));
+    BEVW_TRY(need_packed_frames(*h));
     const bevw_config &c = h->cfg;
     const size_t frame = h->set_bytes() / 4, bev = (size_t)c.bev_width * c.bev_height * 3;
     BEVW_TRY(h->in.reserve(frame * 4));
@@ -1796,7 +1806,7 @@ int bevw_set_camera_shard(bevw_handle *h, const int32_t *cams, int ncams)
     }
     if (h->input_format != BEVW_INPUT_BGR) return fail(BEVW_E_INVALID, "camera-shard handles take BGR frames only (%s input is set)", input_format_name(h->input_format));
     if (h->out_nv12()) return fail(BEVW_E_INVALID, "camera-shard handles write BGR images only (NV12 output is set)");
-    h->shard_n = ncams;
+    h->shard_n = ncams; h->cams = ncams;
     for (int k = 0; k < 4; ++k) h->shard_cams[k] = k < ncams ? cams[k] : cams[0];
     h->built = false;
     return BEVW_OK;
@@ -1852,8 +1862,7 @@ int bevw_shard_run_device(bevw_handle *h, const void *d_frames, int batch, const
                        h->sdeltas.as<int>());
     BEVW_TRY(launch_check("k_lum_delta/k_delta_select"));
     step.deltas = h->sdeltas.as<int>(); step.tab = h->hsv.as<HsvTables>();
-    static const int bal_mode = [] { const char *s = getenv("BEVW_BAL_MODE"); return s ? atoi(s) : 1; }();
-    if (bal_mode == 1 && h->plan.compact_stride != 0) {
+    if (bal_mode() == 1 && h->plan.compact_stride != 0) {
         BEVW_TRY(h->tmp.reserve(h->plan.compact_stride * (size_t)batch));
         BEVW_TRY(plan_lum_groups(h->plan, h->stream, step.src, h->tmp.as<uint8_t>(), batch, step.deltas, step.tab));
         step.scratch = h->tmp.as<uint8_t>();
@@ -2098,40 +2107,10 @@ int bevw_color_balance(int device, const uint8_t *images, int batch, int width, 
     return BEVW_OK;
 }
 
-int bevw_sync(bevw_handle *h)
-{
-    if (!h) return fail(BEVW_E_INVALID, "null handle");
-    BEVW_TRY(use_device(h->cfg.device));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return BEVW_OK;
-}
-int bevw_timer_start(bevw_handle *h)
-{
-    if (!h) return fail(BEVW_E_INVALID, "null handle");
-    BEVW_TRY(use_device(h->cfg.device));
-    HIP_TRY(hipEventRecord(h->ev0, h->stream));
-    return BEVW_OK;
-}
-int bevw_timer_mark(bevw_handle *h, int slot)
-{
-    if (!h) return fail(BEVW_E_INVALID, "null handle");
-    BEVW_TRY(use_device(h->cfg.device));
-    return h->laps.mark(slot, h->stream);
-}
-int bevw_timer_between(bevw_handle *h, int slot_a, int slot_b, float *elapsed_ms)
-{
-    if (!h) return fail(BEVW_E_INVALID, "null handle");
-    BEVW_TRY(use_device(h->cfg.device));
-    return h->laps.between(slot_a, slot_b, elapsed_ms);
-}
-int bevw_timer_stop(bevw_handle *h, float *elapsed_ms)
-{
-    if (!h || !elapsed_ms) return fail(BEVW_E_INVALID, "null argument");
-    BEVW_TRY(use_device(h->cfg.device));
-    HIP_TRY(hipEventRecord(h->ev1, h->stream));
-    HIP_TRY(hipEventSynchronize(h->ev1));
-    HIP_TRY(hipEventElapsedTime(elapsed_ms, h->ev0, h->ev1));
-    return BEVW_OK;
-}
+int bevw_sync(bevw_handle *h) { return engine_sync(h, "handle"); }
+int bevw_timer_start(bevw_handle *h) { return engine_timer_start(h, "handle"); }
+int bevw_timer_mark(bevw_handle *h, int slot) { return engine_timer_mark(h, "handle", slot); }
+int bevw_timer_between(bevw_handle *h, int slot_a, int slot_b, float *elapsed_ms) { return engine_timer_between(h, "handle", slot_a, slot_b, elapsed_ms); }
+int bevw_timer_stop(bevw_handle *h, float *elapsed_ms) { return engine_timer_stop(h, elapsed_ms); }
 
 }  // extern "C"

@@ -7,9 +7,11 @@ namespace bevw {
 
 void plan_release(Plan &p)
 {
-    void *ptrs[] = {p.un_desc, p.un_entries, p.un_gsrc, p.un_gsrc_compact, p.un_gsrc_nv12, p.list_un_all, p.entries, p.hdr, p.groups, p.groups_nv12, p.un_gsrc_surf, p.groups_surf, p.un_gsrc_yuv422, p.groups_yuv422, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
+    void *ptrs[] = {p.un_desc, p.un_entries, p.list_un_all, p.entries, p.hdr, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
+    for (int l = 0; l < kSrcLayouts; ++l)
+        for (void *q : {p.units[l], p.sampled[l]}) if (q) (void)hipFree(q);
     p = Plan();
 }
 
@@ -22,52 +24,48 @@ const uint32_t *plan_sum_entries(const Plan &p, int first, int &nsum)
 static UnitTuning unit_tuning_env()
 {
     UnitTuning t;
-    if (const char *s = getenv("BEVW_UNIT_GROUPS")) t.max_groups = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_ROOT_W")) t.root_w = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_ROOT_H")) t.root_h = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_MIN_W")) t.min_w = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_LINE_COST")) t.line_cost = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_SECTOR_COST")) t.sector_cost = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_ALIGN_LINES")) t.align_lines = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_OWN_EMPTY")) t.own_empty = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_SKEW")) t.skew = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_ROW_ORDER")) t.row_order = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_OWN_PADDING")) t.own_padding = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_STAGGER")) t.stagger = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_RUN_COST")) t.run_cost = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_BIG")) t.big_class = atoi(s);
-    if (const char *s = getenv("BEVW_UNIT_WIDE_DOUBLE")) t.wide_double = atoi(s);
+    t.max_groups = env_int("BEVW_UNIT_GROUPS", t.max_groups);
+    t.root_w = env_int("BEVW_UNIT_ROOT_W", t.root_w);
+    t.root_h = env_int("BEVW_UNIT_ROOT_H", t.root_h);
+    t.min_w = env_int("BEVW_UNIT_MIN_W", t.min_w);
+    t.line_cost = env_int("BEVW_UNIT_LINE_COST", t.line_cost);
+    t.sector_cost = env_int("BEVW_UNIT_SECTOR_COST", t.sector_cost);
+    t.align_lines = env_int("BEVW_UNIT_ALIGN_LINES", t.align_lines);
+    t.own_empty = env_int("BEVW_UNIT_OWN_EMPTY", t.own_empty);
+    t.skew = env_int("BEVW_UNIT_SKEW", t.skew);
+    t.row_order = env_int("BEVW_UNIT_ROW_ORDER", t.row_order);
+    t.own_padding = env_int("BEVW_UNIT_OWN_PADDING", t.own_padding);
+    t.stagger = env_int("BEVW_UNIT_STAGGER", t.stagger);
+    t.run_cost = env_int("BEVW_UNIT_RUN_COST", t.run_cost);
+    t.big_class = env_int("BEVW_UNIT_BIG", t.big_class);
+    t.wide_double = env_int("BEVW_UNIT_WIDE_DOUBLE", t.wide_double);
     return t;
 }
 
 // tuning knobs for experiments (defaults are the shipped configuration)
 static const PlanTuning &plan_tuning()
 {
-    static const PlanTuning tune = [] {
-        PlanTuning t;
-        if (const char *s = getenv("BEVW_PLAN_NB")) t.nb = atoi(s);
-        if (const char *s = getenv("BEVW_PLAN_XCDMAP")) t.xcd_map = atoi(s);
-        if (const char *s = getenv("BEVW_PLAN_UNITS")) t.units = atoi(s);
-        return t;
-    }();
+    static const PlanTuning d, tune = {env_int("BEVW_PLAN_NB", d.nb), env_int("BEVW_PLAN_XCDMAP", d.xcd_map), env_int("BEVW_PLAN_UNITS", d.units)};
     return tune;
 }
 
 int plan_build(Plan &p, hipStream_t st, const StitchTables &T, int fw, int fh, int bw, int bh, int ncams, int out_pitch, bool blend)
 {
     static const UnitTuning unit_tune = unit_tuning_env();
+    // (the two switches whose default depends on the plan: whether they are set at all)
+    static const bool sector_cost_set = env_int("BEVW_UNIT_SECTOR_COST", INT_MIN) != INT_MIN, row_order_set = env_int("BEVW_UNIT_ROW_ORDER", INT_MIN) != INT_MIN;
     UnitTuning tune = unit_tune;
     (void)blend;   // (rounds 3 - 5 compiled blend handles without the two-quad two-contributor class: its float blend variant needed 177+ VGPRs;
                    // with round 6's integer weights it fits the kernel's budget, bevw_unit.h: plan_unit_any)
     // rows of whole sectors (an output pitch): column cuts on sector boundaries are free, all others split a sector for good -> a higher
     // price per write sector (3 -> 8: -0.4 ... -2 % on config 3, -2 % on the 4K rig, nothing slower; profiles/r03/sweeps.log).  The dense
     // layout keeps 3: there every cut shares sectors and the price only drives the source lines up (40 k -> 50 k per frame)
-    if (out_pitch > 0 && !getenv("BEVW_UNIT_SECTOR_COST")) tune.sector_cost = 8;
+    if (out_pitch > 0 && !sector_cost_set) tune.sector_cost = 8;
     // One-camera plans (the fisheye remapper, BASELINE config 2: 378 units x 8 chunks = 3.9 rounds of blocks over the chip's 768 slots) are
     // launched longest unit first: with so few rounds the tail of the spatial order costs more than the neighbours' shared lines return --
     // batch 16 / 32 / 64 / 128: -4 ... -5.5 % (0.0804 -> 0.0765 ms at 64), batch 256 +1.8 %.  The 4-camera plans keep the spatial order
     // (config 3 +4 % with it, the 4K rig +5.6 %).  profiles/r06/call9..11
-    if (ncams == 1 && !getenv("BEVW_UNIT_ROW_ORDER")) tune.row_order = 4;
+    if (ncams == 1 && !row_order_set) tune.row_order = 4;
     hipError_t e = plan_build_impl(p, st, T, fw, fh, bw, bh, ncams, plan_tuning().units != 0, tune, out_pitch);
     if (e != hipSuccess) return fail(BEVW_E_HIP, "tile-plan build failed: %s", hipGetErrorString(e));
     return BEVW_OK;
@@ -83,14 +81,16 @@ int plan_stitch(Plan &p, hipStream_t st, const PlanStep &step)
 int plan_set_format(Plan &p, SrcFormat fmt, bool out_nv12, int src_pitch)
 {
     p.fmt = fmt; p.out_nv12 = out_nv12;
-    if (p.yuv422()) {
-        hipError_t e = plan_yuv422_impl(p);
-        if (e != hipSuccess) return fail(BEVW_E_HIP, "uploading the 4:2:2 group lists failed: %s", hipGetErrorString(e));
-    }
-    if (src_pitch == p.src_pitch) return BEVW_OK;   // (the group lists are the ones of this pitch; none after plan_build, for pitch 0)
+    // The translated frame layouts: the lists of packed NV12 and of packed 4:2:2 are made when such a format is first set, the surface lists
+    // whenever the pitch is another one (pitch 0: none, as after plan_build)
+    static const char *const names[kSrcLayouts] = {"BGR", "NV12", "surface", "4:2:2", "compact"};
+    const bool new_pitch = src_pitch != p.src_pitch;
     p.src_pitch = src_pitch;
-    hipError_t e = plan_src_pitch_impl(p, src_pitch);
-    if (e != hipSuccess) return fail(BEVW_E_HIP, "uploading the surface group lists failed: %s", hipGetErrorString(e));
+    for (SrcLayout l : {frames_layout(fmt, false), kLayoutSurf}) {
+        if (l == kLayoutBGR || (l == kLayoutSurf ? !new_pitch : p.units[l] || p.sampled[l])) continue;
+        hipError_t e = plan_make_lists(p, l);
+        if (e != hipSuccess) return fail(BEVW_E_HIP, "uploading the %s group lists failed: %s", names[l], hipGetErrorString(e));
+    }
     return BEVW_OK;
 }
 
