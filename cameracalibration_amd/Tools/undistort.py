@@ -49,21 +49,26 @@ class Undistorter:
     """The map set of one (K, D, size, scales, offsets) on the device."""
 
     def __init__(self, K, D, width, height, focalscale=1.0, sizescale=1.0, offset_h=0.0, offset_v=0.0, device=0, input_format='bgr',
-                 output_format='bgr', input_pitch=None):
+                 output_format='bgr', input_pitch=None, channels=3):
         """input_format: 'bgr' (images [height, width, 3]) or 'nv12' ([height*3//2, width]: Y plane, then the interleaved U / V plane; the
         result is what cv2.remap gives for cv2.cvtColor(img, cv2.COLOR_YUV2BGR_NV12) -- bevw_remapper_set_input_format in include/bevwarp.h),
         'yuyv' / 'uyvy' ([height, width, 2]: packed 4:2:2 as a live camera delivers it; cv2.COLOR_YUV2BGR_YUY2 / _UYVY; an even width).
         output_format: 'bgr' (results [out_h, out_w, 3]) or 'nv12' ([out_h*3//2, out_w]: the NV12 form of the BGR result, chroma of each 2 x 2
         block from its top-left pixel -- bevw_set_output_format in include/bevwarp.h; needs an even output size).
         input_pitch: with input_format='nv12', bytes between the rows of the decoder surfaces run_surfaces() reads in place (None: width;
-        else a multiple of 4 >= width -- bevw_remapper_set_input_pitch); with a pitch other than width __call__ is refused."""
+        else a multiple of 4 >= width -- bevw_remapper_set_input_pitch); with a pitch other than width __call__ is refused.
+        channels: 3, or 1 for single uint8 planes (images [height, width], results [out_h, out_w]: what cv2.remap gives for a 2-D array --
+        bevw_remapper_set_channels); one channel is 'bgr' in and out without a pitch."""
         self._r = None
+        self.channels = _ffi.channels(channels)
         formats = _ffi.INPUT_FORMATS
         _ffi.input_format(input_format)
         out_formats = {'bgr': _ffi.OUTPUT_BGR, 'nv12': _ffi.OUTPUT_NV12}
         if output_format not in out_formats:
             raise Exception("output_format should be bgr/nv12")
         self.output_format = output_format
+        if self.channels == 1 and (input_format != 'bgr' or output_format != 'bgr' or input_pitch is not None):
+            raise Exception("channels=1 needs input_format='bgr', output_format='bgr' and no input_pitch")
         in_pitch = _ffi.check_input_pitch(input_pitch, width, input_format == 'nv12')
         _ffi.require_device()
         self.width, self.height = int(width), int(height)
@@ -80,6 +85,8 @@ class Undistorter:
                 check(lib().bevw_remapper_set_input_pitch(r, in_pitch))
             if output_format != 'bgr':
                 check(lib().bevw_remapper_set_output_format(r, out_formats[output_format]))
+            if self.channels == 1:
+                check(lib().bevw_remapper_set_channels(r, 1))
         except Exception:
             self.close()
             raise
@@ -91,7 +98,13 @@ class Undistorter:
     @property
     def out_image_bytes(self) -> int:
         """Bytes of one dense device image as run_surfaces() writes it."""
+        if self.channels == 1:
+            return self.out_w * self.out_h
         return self.out_w * self.out_h * 3 // 2 if self.output_format == 'nv12' else self.out_w * self.out_h * 3
+
+    def last_path(self) -> int:
+        """Which kernels served the last step: _ffi.PATH_NONE / PATH_UNITS / PATH_PER_PIXEL (bevw_remapper_last_path)."""
+        return int(lib().bevw_remapper_last_path(self._r))
 
     def run_surfaces(self, table, d_out: int, out_bytes: int = None) -> None:
         """Asynchronous remap of NV12 decoder surfaces, read where they lie.  ``table``: uint64 [B, 2] on the HOST -- per image the device
@@ -126,15 +139,19 @@ class Undistorter:
 
     def __call__(self, images):
         """uint8 [B, height, width, 3] (or one [height, width, 3]) -> undistorted images of the map size.  'nv12': [B, height*3//2, width]
-        (or one [height*3//2, width]); 'yuyv' / 'uyvy': [B, height, width, 2] (or one [height, width, 2]).  output_format 'nv12': [B, out_h*3//2, out_w] (or one [out_h*3//2, out_w])."""
+        (or one [height*3//2, width]); 'yuyv' / 'uyvy': [B, height, width, 2] (or one [height, width, 2]).  output_format 'nv12': [B, out_h*3//2, out_w] (or one [out_h*3//2, out_w]).
+        channels=1: [B, height, width] (or one [height, width]) -> [B, out_h, out_w] (or one [out_h, out_w])."""
         imgs = np.ascontiguousarray(images)
-        frame = _ffi.frame_shape(self.input_format, self.height, self.width)
+        frame = (self.height, self.width) if self.channels == 1 else _ffi.frame_shape(self.input_format, self.height, self.width)
         single = imgs.ndim == len(frame)
         if single:
             imgs = imgs[np.newaxis]
         if imgs.dtype != np.uint8 or imgs.shape[1:] != frame:
-            raise Exception("images must be uint8 [B, {}]".format(", ".join(str(n) for n in frame)))
+            what = "[B, height, width] = " if self.channels == 1 else ""
+            raise Exception("images must be uint8 {}[B, {}]".format(what, ", ".join(str(n) for n in frame)))
         shape = (self.out_h * 3 // 2, self.out_w) if self.output_format == 'nv12' else (self.out_h, self.out_w, 3)
+        if self.channels == 1:
+            shape = (self.out_h, self.out_w)
         out = np.empty((imgs.shape[0],) + shape, np.uint8)
         check(lib().bevw_remap(self._r, ptr(imgs), imgs.shape[0], ptr(out)))
         return out[0] if single else out

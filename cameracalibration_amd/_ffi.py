@@ -29,11 +29,19 @@ def input_format(name) -> int:
     return INPUT_FORMATS[name]
 
 
+def channels(n) -> int:
+    """The channel count of a remapper's images (bevw_remapper_set_channels): 3, or 1 for uint8 [H, W] planes."""
+    if isinstance(n, bool) or n not in (1, 3):
+        raise Exception("channels should be 1/3")
+    return int(n)
+
+
 def frame_shape(name, height: int, width: int):
     """Shape of one camera frame of a format: (H, W, 3) 'bgr', (H*3//2, W) 'nv12', (H, W, 2) 'yuyv' / 'uyvy'."""
     if name == 'nv12':
         return (height * 3 // 2, width)
     return (height, width, 2 if name in ('yuyv', 'uyvy') else 3)
+PATH_NONE, PATH_UNITS, PATH_PER_PIXEL = 0, 1, 2      # bevw_remapper_last_path
 OUTPUT_BGR, OUTPUT_NV12 = 0, 1                       # bevw_set_output_format, bevw_remapper_set_output_format
 COMPAT_FILLPOLY, COMPAT_ADDWEIGHTED, COMPAT_WARP, COMPAT_REMAP = 0, 1, 2, 3   # bevw_set_compat keys (include/bevwarp.h)
 
@@ -122,6 +130,9 @@ SIGNATURES = {
     "bevw_remapper_set_input_format": (_i, [_vp, _i]),
     "bevw_remapper_set_output_format": (_i, [_vp, _i]),
     "bevw_remapper_set_input_pitch": (_i, [_vp, _i]),
+    "bevw_remapper_set_channels": (_i, [_vp, _i]),
+    "bevw_remapper_channels": (_i, [_vp]),
+    "bevw_remapper_last_path": (_i, [_vp]),
     "bevw_remap_surfaces_device": (_i, [_vp, _vp, _i, _vp]),
     "bevw_remap_surface_table_device": (_i, [_vp, _vp, _i, _vp]),
     "bevw_remapper_timer_start": (_i, [_vp]),

@@ -2,9 +2,9 @@
 
     python -m cameracalibration_amd.build [--force]
 
-Four translation units -- bevwarp.hip (handles, table builders, tools, the camera-per-GPU exchange), bevwarp_plan.hip (the tile plan
-and its per-frame kernels), bevwarp_jpeg.hip (the JPEG codec) and bevwarp_yuv422.hip (every kernel that reads packed 4:2:2 camera frames:
-FORMAT_UNITS) -- are compiled in parallel into objects under csrc/build/ and linked;
+Five translation units -- bevwarp.hip (handles, table builders, tools, the camera-per-GPU exchange), bevwarp_plan.hip (the tile plan
+and its per-frame kernels), bevwarp_jpeg.hip (the JPEG codec), bevwarp_yuv422.hip (every kernel that reads packed 4:2:2 camera frames:
+FORMAT_UNITS) and bevwarp_gray.hip (every kernel of the one-channel remapper: CHANNEL_UNITS) -- are compiled in parallel into objects under csrc/build/ and linked;
 a unit is recompiled when its source, ANY header under csrc/ or the flag set changed.  The shared object is written next to this file (in-tree: it travels
 to the GPU box with the repo snapshot and is git-ignored).  -ffp-contract=off is REQUIRED: the arithmetic being reproduced has no fused
 multiply-add.
@@ -26,6 +26,9 @@ UNITS = ["bevwarp.hip", "bevwarp_plan.hip", "bevwarp_jpeg.hip"]
 # units that hold the kernels of one input format and nothing else: the shared device functions of the headers instantiated for that
 # format, under kernel names of their own (no kernel of UNITS is compiled a second time)
 FORMAT_UNITS = ["bevwarp_yuv422.hip"]
+# units that hold the kernels of one channel count: the one-channel remapper (bevw_remapper_set_channels), every kernel named *gray*
+CHANNEL_UNITS = ["bevwarp_gray.hip"]
+ALL_UNITS = UNITS + FORMAT_UNITS + CHANNEL_UNITS
 
 
 def _headers():
@@ -62,12 +65,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
         force = True
     jobs = []
     hdrs = _headers()
-    for src in UNITS + FORMAT_UNITS:
+    for src in ALL_UNITS:
         obj = os.path.join(OBJ, src.replace(".hip", ".o"))
         deps = [os.path.join(CSRC, src)] + hdrs + [me]
         if force or _newer(obj, deps):
             jobs.append([hipcc] + CFLAGS + EXTRA + ["-c", os.path.join(CSRC, src), "-o", obj])
-    objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in UNITS + FORMAT_UNITS]
+    objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in ALL_UNITS]
     if not jobs and not _newer(LIB, objs):
         return LIB
 
@@ -76,7 +79,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)
 
-    with ThreadPoolExecutor(max_workers=len(UNITS + FORMAT_UNITS)) as pool:
+    with ThreadPoolExecutor(max_workers=len(ALL_UNITS)) as pool:
         list(pool.map(run, jobs))
     with open(stamp, "w") as f:
         f.write(flags)

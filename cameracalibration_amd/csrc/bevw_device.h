@@ -301,11 +301,13 @@ __host__ __device__ __forceinline__ size_t frame_bytes_of(int fw, int fh, bool n
 // (x, y) takes Y from its own two bytes and U, V from the pair x / 2 of its own row -- chroma is shared horizontally only, so fh is free.
 // The arithmetic is NV12's (nv12_bgr): cv2.cvtColor(COLOR_YUV2BGR_YUY2 / COLOR_YUV2BGR_UYVY).
 // The format of the camera frames of a step; the values are the BEVW_INPUT_* constants of include/bevwarp.h.
-enum class SrcFormat : int { BGR = 0, NV12 = 1, YUYV = 4, UYVY = 5 };
+// GRAY is internal: the one-channel frames of a remapper (bevw_remapper_set_channels), a channel count and no BEVW_INPUT_* value.
+enum class SrcFormat : int { BGR = 0, NV12 = 1, YUYV = 4, UYVY = 5, GRAY = 0x100 };
 __host__ __device__ __forceinline__ bool src_is_yuv422(SrcFormat f) { return f == SrcFormat::YUYV || f == SrcFormat::UYVY; }
-// bytes of one frame: BGR 3 per texel, NV12 1.5, packed 4:2:2 2
+// bytes of one frame: BGR 3 per texel, NV12 1.5, packed 4:2:2 2, one channel 1
 __host__ __device__ __forceinline__ size_t frame_bytes_of(int fw, int fh, SrcFormat f)
 {
+    if (f == SrcFormat::GRAY) return (size_t)fw * fh;
     return src_is_yuv422(f) ? (size_t)fw * fh * 2 : frame_bytes_of(fw, fh, f == SrcFormat::NV12);
 }
 // The byte order as the kernels take it: the v_perm_b32 selectors that pick, from the 8 bytes of four texels {hi, lo}, their four Y bytes

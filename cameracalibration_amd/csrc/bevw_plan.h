@@ -26,6 +26,7 @@
 #include "bevw_device.h"
 #include "bevw_planapi.h"
 #include "bevw_yuv422.h"
+#include "bevw_gray.h"
 
 namespace bevw {
 
@@ -465,6 +466,10 @@ static inline hipError_t plan_make_lists(Plan &p, SrcLayout lay)
         case kLayoutSurf:   // (a units' list with a unit of more than two cameras is not used: the per-tap kernel then serves every tile)
             return p.src_pitch > 0 && p.fh % 2 == 0 && unit_gsrc_surf(bgr, p.fw, p.fh, p.src_pitch, tr, units ? &p.un_ranges_host : nullptr);
         case kLayoutYuv422: unit_gsrc_yuv422(bgr, p.fw, p.fh, tr); return true;   // (the same list serves both byte orders)
+        case kLayoutGray:   // the units alone, and only single-contributor classes: k_units_gray has no blend (a one-camera plan has no other)
+            if (!units || p.n_un[4] + p.n_un[5] + p.n_un[6] != 0) return false;
+            unit_gsrc_gray(bgr, p.fw, p.fh, tr);
+            return true;
         default:   // kLayoutCompact: the units alone, and only where the scratch stays below 2^31 bytes per frame set
             return units && unit_gsrc_compact(bgr, p.groups_host, tr) && unit_compact_stride(p.groups_host.size()) < (1ull << 31);
         }
@@ -614,6 +619,39 @@ static inline void plan_launch_units(const PlanArgs &a, hipStream_t st, bool ble
     });
 }
 
+// what plan_route is asked for one step of the plan
+static inline RouteIn plan_route_in(const Plan &p, const PlanStep &s, const PlanTuning &tune)
+{
+    RouteIn ri;
+    ri.fmt = p.fmt; ri.surf = s.src.is_surf(); ri.out_nv12 = p.out_nv12;
+    ri.balance = s.balance; ri.sums = s.sums; ri.scratch = s.scratch != nullptr;
+    ri.units_on = tune.units && p.n_un_all > 0;
+    ri.src_aligned = s.src.aligned4(); ri.scratch_aligned = (((uintptr_t)s.scratch) & 3u) == 0;
+    for (int l = 0; l < kPlanLayouts; ++l) ri.have[l] = p.units[l] != nullptr;
+    ri.set_bytes = (uint32_t)(frame_bytes_of(p.fw, p.fh, p.fmt) * p.ncams); ri.compact_stride = (uint32_t)p.compact_stride;
+    return ri;
+}
+
+// One step of a one-channel plan (SrcFormat::GRAY: bevw_remapper_set_channels): k_units_gray over every unit, k_stitch_plan_gray over the
+// base tiles no unit owns (bevwarp_gray.hip).  Images of bw x bh bytes: bw % 4 == 0 and a 4-byte aligned `out` (a quad is one dword store).
+static inline hipError_t plan_gray_step(const Plan &p, hipStream_t st, const PlanStep &s, const PlanTuning &tune, const Route &rt)
+{
+    if (!rt.use_units || rt.units != kLayoutGray || p.pitch != p.bw || p.bw % 4 != 0 || (((uintptr_t)s.out) & 3u) != 0 || s.car || s.blend)
+        return hipErrorInvalidValue;   // (the caller runs the per-pixel kernel instead: plan_units_serve)
+    PlanArgs a = plan_args(p, s.src, s.batch, nullptr, s.out, tune);
+    a.plan = static_cast<const uint2 *>(p.entries); a.hdr = static_cast<const uint32_t *>(p.hdr);
+    a.tile_list = static_cast<const uint32_t *>(p.list_un_all); a.nlist = p.n_un_all; a.ngroups = p.n_un_all;
+    a.set_stride = rt.set_stride;
+    a.un_gsrc = static_cast<const uint32_t *>(p.units[kLayoutGray]);
+    gray_launch_units(a, st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || p.n_slow == 0) return e;
+    a.tile_list = static_cast<const uint32_t *>(p.list_slow); a.nlist = p.n_slow; a.ngroups = (p.n_slow + 3) / 4;
+    a.set_stride = 0;
+    gray_launch_stitch_plan(a, st);
+    return hipGetLastError();
+}
+
 // One step of the tile plan on `st` (PlanStep, bevw_planapi.h).
 static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanStep &s, const PlanTuning &tune)
 {
@@ -626,14 +664,8 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
     a.plan = static_cast<const uint2 *>(p.entries); a.hdr = static_cast<const uint32_t *>(p.hdr);
     a.deltas = s.deltas; a.tab = s.tab;
     const bool padded = p.pitch != p.bw, scratch = padded && !p.out_pitched;
-    RouteIn ri;
-    ri.fmt = p.fmt; ri.surf = surf; ri.out_nv12 = p.out_nv12;
-    ri.balance = s.balance; ri.sums = s.sums; ri.scratch = s.scratch != nullptr;
-    ri.units_on = tune.units && p.n_un_all > 0;
-    ri.src_aligned = s.src.aligned4(); ri.scratch_aligned = (((uintptr_t)s.scratch) & 3u) == 0;
-    for (int l = 0; l < kSrcLayouts; ++l) ri.have[l] = p.units[l] != nullptr;
-    ri.set_bytes = (uint32_t)(frame_bytes_of(p.fw, p.fh, p.fmt) * p.ncams); ri.compact_stride = (uint32_t)p.compact_stride;
-    const Route rt = plan_route(ri);
+    const Route rt = plan_route(plan_route_in(p, s, tune));
+    if (p.fmt == SrcFormat::GRAY) return plan_gray_step(p, st, s, tune, rt);
     const bool out_nv12 = rt.out_nv12, use_units = rt.use_units;
     if (out_nv12 && (scratch || p.pitch % 4 != 0)) return hipErrorInvalidValue;   // (the caller runs the per-pixel kernel instead)
     if (padded) {

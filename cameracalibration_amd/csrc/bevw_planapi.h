@@ -41,7 +41,9 @@ struct FrameSource {
 // per layout of the memory it is read against: packed BGR, packed NV12, NV12 surfaces at Plan::src_pitch, packed 4:2:2, the compact scratch
 // (DESIGN.md section 8 has the table: what a slot holds, when a list is made, when it is missing).  A missing list is nullptr, which sends
 // the step to the per-tap kernel and is never an error.
-enum SrcLayout { kLayoutBGR = 0, kLayoutNV12, kLayoutSurf, kLayoutYuv422, kLayoutCompact, kSrcLayouts };
+// kLayoutGray: the one-channel frames of a remapper (SrcFormat::GRAY), 1 byte per texel.  It stands behind kSrcLayouts, the layouts of
+// three-channel sources: the units' list alone, no sampled list (no balance schedule), and routed by the format alone.
+enum SrcLayout { kLayoutBGR = 0, kLayoutNV12, kLayoutSurf, kLayoutYuv422, kLayoutCompact, kSrcLayouts, kLayoutGray = kSrcLayouts, kPlanLayouts };
 
 // a compiled tile plan: its device buffers and the geometry they were built for (plan_build / plan_build_wide)
 struct Plan {
@@ -63,7 +65,7 @@ struct Plan {
     int ncams = 4;
     // the group lists, one per layout of what they address (SrcLayout; bevw_unit.h has the translations).  sampled: the n_groups sampled
     // 4-texel groups of the frame set in ascending order (balance schedule 1: plan_lum_groups; none for the compact scratch it writes)
-    void *units[kSrcLayouts] = {}, *sampled[kSrcLayouts] = {};
+    void *units[kPlanLayouts] = {}, *sampled[kPlanLayouts] = {};
     int n_groups = 0;
     bool band_ok = false;        // the sampled-group list exists (balance schedule 1)
     int max_contrib = 0;
@@ -100,7 +102,7 @@ struct RouteIn {
     bool balance = false, sums = false, scratch = false;   // the step's (PlanStep; scratch: it brings a compact scratch)
     bool units_on = false;            // the units switch is on and the plan has units
     bool src_aligned = false, scratch_aligned = false;     // the frame sets / the compact scratch are 4-byte aligned
-    bool have[kSrcLayouts] = {};      // Plan::units[layout] exists
+    bool have[kPlanLayouts] = {};     // Plan::units[layout] exists
     uint32_t set_bytes = 0, compact_stride = 0;   // bytes of one frame set in the plan's format; Plan::compact_stride
 };
 struct Route {
@@ -113,7 +115,7 @@ struct Route {
 };
 inline SrcLayout frames_layout(SrcFormat fmt, bool surf)
 {
-    return src_is_yuv422(fmt) ? kLayoutYuv422 : surf ? kLayoutSurf : fmt == SrcFormat::NV12 ? kLayoutNV12 : kLayoutBGR;
+    return fmt == SrcFormat::GRAY ? kLayoutGray : src_is_yuv422(fmt) ? kLayoutYuv422 : surf ? kLayoutSurf : fmt == SrcFormat::NV12 ? kLayoutNV12 : kLayoutBGR;
 }
 inline Route plan_route(const RouteIn &in)
 {
@@ -127,7 +129,11 @@ inline Route plan_route(const RouteIn &in)
     // luminance kernel (balance); channel sums exist with BGR units only.  (The BGR list exists wherever the plan has units.)
     r.use_units = !in.balance && in.units_on && in.src_aligned && (r.units == kLayoutBGR || in.have[r.units]) &&
                   (r.units != kLayoutCompact || in.scratch_aligned) && (bgr_units || !in.sums);
-    r.out_nv12 = in.out_nv12 && !in.balance && !in.sums && !in.scratch;
+    // one channel: the units on the frames themselves or nothing -- no balance chain, no shard scratch, no NV12 image exists in one channel,
+    // and a step without units leaves the plan (the caller runs the per-pixel kernel: plan_units_serve)
+    const bool gray = in.fmt == SrcFormat::GRAY;
+    if (gray) r.use_units = r.use_units && r.units == kLayoutGray && !in.out_nv12;
+    r.out_nv12 = in.out_nv12 && !in.balance && !in.sums && !in.scratch && !gray;
     r.set_stride = !r.use_units || r.units == kLayoutBGR ? 0u : r.units == kLayoutCompact ? in.compact_stride : in.set_bytes;
     // LUM: luminance round trip per tap (the RAW frames of balance, or the tiles no unit owns beside the compact scratch); a scratch without
     // sums: camera-per-GPU shards, whose stitch rank balances the colours.  Neither exists with NV12 images (out_nv12 above)
@@ -161,6 +167,9 @@ struct PlanStep {
     const uint8_t *scratch = nullptr;
 };
 int plan_stitch(Plan &p, hipStream_t st, const PlanStep &step);
+// whether the unit kernel serves that step (plan_route on the plan's lists and the step's pointers): what a remapper records as the path of
+// the step, and for one-channel frames whether the step may enter the plan at all
+bool plan_units_serve(const Plan &p, const PlanStep &step);
 
 // balance: luminance round trip of the sampled texel groups of the raw frames into the compact scratch (p.compact_stride bytes per frame set)
 int plan_lum_groups(const Plan &p, hipStream_t st, const FrameSource &src, uint8_t *d_scratch, int batch, const int *d_deltas, const HsvTables *d_tab);

@@ -555,6 +555,19 @@ static inline void unit_gsrc_yuv422(const std::vector<uint32_t> &gsrc, int fw, i
         out[i] = 2u * (cam * texels + y * (uint32_t)fw + x);
     }
 }
+// One-channel frame sets (bevw_remapper_set_channels: 8UC1 sources of a remapper): the fourth translation -- ONE dword per slot, the byte offset
+// of the group's first texel inside a frame set of 1 byte per texel: cam * fw * fh + y * fw + x = o / 3 for the BGR offset o, a multiple of
+// 4 (x % 4 == 0, fw % 4 == 0).  The slot's 8-byte load there IS its four pair entries (bevw_kernels_gray.h); fh is free.
+static inline void unit_gsrc_gray(const std::vector<uint32_t> &gsrc, int fw, int fh, std::vector<uint32_t> &out)
+{
+    out.assign(gsrc.size(), kPairNoGroup);
+    const uint32_t frame_bytes = (uint32_t)fw * fh * 3, row_bytes = (uint32_t)fw * 3, texels = (uint32_t)fw * fh;
+    for (size_t i = 0; i < gsrc.size(); ++i) {
+        if (gsrc[i] == kPairNoGroup) continue;
+        const uint32_t cam = gsrc[i] / frame_bytes, t = gsrc[i] % frame_bytes, y = t / row_bytes, x = t % row_bytes / 3;
+        out[i] = cam * texels + y * (uint32_t)fw + x;
+    }
+}
 // NV12 surfaces (bevw_run_surfaces_device): the same list translated into offsets relative to the CAMERA'S OWN planes, whose rows are `pitch`
 // bytes apart (bevw_set_input_pitch; >= fw, a multiple of 4): out[2 i] = Y of texel (x, y) inside the Y plane, out[2 i + 1] = U of texel
 // (x, y) inside the U / V plane | the camera (0 .. 3) in the two low bits -- group offsets are multiples of 4 (x % 4 == 0, pitch % 4 == 0),

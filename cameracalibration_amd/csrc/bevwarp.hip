@@ -18,6 +18,7 @@
 #include "bevw_kernels.h"
 #include "bevw_planapi.h"
 #include "bevw_yuv422.h"
+#include "bevw_gray.h"
 #include "bevw_comm.h"
 
 using namespace bevw;
@@ -355,7 +356,8 @@ struct EngineCore {
     int cams = 4;                        // frames per set
     int input_format = BEVW_INPUT_BGR, output_format = BEVW_OUTPUT_BGR;
     int in_pitch_request = 0;            // 0: the frame width
-    SrcFormat fmt() const { return (SrcFormat)input_format; }
+    int channels = 3;                    // 1: 8UC1 frames and images (bevw_remapper_set_channels; BGR in and out, no pitch)
+    SrcFormat fmt() const { return channels == 1 ? SrcFormat::GRAY : (SrcFormat)input_format; }
     bool nv12() const { return input_format == BEVW_INPUT_NV12; }
     bool yuv422() const { return src_is_yuv422(fmt()); }   // packed 4:2:2: YUYV / UYVY
     bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
@@ -486,6 +488,8 @@ static int engine_staged_step(EngineCore &e, const bevw_nv12_surface *surfaces, 
 static const EngineNouns kRemapperNouns = {"remapper", "the source width", "source", "bevw_remapper_set_", "bevw_remap_surfaces_device"};
 struct bevw_remapper : EngineCore {
     int dw = 0, dh = 0;   // (the source size: EngineCore::fw, fh)
+    int last_path = BEVW_PATH_NONE;   // which kernels served the last step (bevw_remapper_last_path)
+    size_t image_bytes() const { return channels == 1 ? (size_t)dw * dh : image_bytes_of(dw, dh, out_nv12()); }   // one destination image
     DevBuf map1, map2, ones;
     // the plan: a single-image contributor plan (same kernels as the BEV stitch, one frame per set)
     bool plan_ready = false;
@@ -544,7 +548,9 @@ static int remap_launch(hipStream_t st, const FrameSource &src, int sw, int sh, 
 {
     for_each_chunk(batch, [&](int b0, int nb) {
         const FrameSource fr = src.from(b0, sw, sh);
-        if (src.yuv422())   // (k_remap_lut_yuv422: bevwarp_yuv422.hip)
+        if (src.fmt == SrcFormat::GRAY)   // (k_remap_lut_gray: bevwarp_gray.hip)
+            gray_launch_remap_lut(st, dim3((dw + 255) / 256, dh, nb), fr.packed, sw, sh, m1, m2, dw, dh, d_dst + (size_t)b0 * dw * dh, ties_even);
+        else if (src.yuv422())   // (k_remap_lut_yuv422: bevwarp_yuv422.hip)
             yuv422_launch_remap_lut(st, dim3((dw + 255) / 256, dh, nb), out_nv12, fr.packed, sw, sh, m1, m2, dw, dh,
                                     d_dst + (size_t)b0 * image_bytes_of(dw, dh, out_nv12), ties_even, yuv422_order(src.fmt));
         else with_formats(src.nv12(), src.is_surf(), out_nv12, [&](auto in, auto on) {
@@ -724,22 +730,60 @@ int bevw_remapper_get_maps(bevw_remapper *r, int16_t *map1, uint16_t *map2)
     return BEVW_OK;
 }
 
+// the formats a one-channel remapper keeps: BGR in and out, dense rows
+static int need_three_channels(const bevw_remapper *r, const char *what)
+{
+    if (r->channels == 1) return fail(BEVW_E_INVALID, "%s: the remapper has one channel (bevw_remapper_set_channels), which is BGR in and out without a pitch", what);
+    return BEVW_OK;
+}
+
+int bevw_remapper_set_channels(bevw_remapper *r, int channels)
+{
+    if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    if (channels != 1 && channels != 3) return fail(BEVW_E_INVALID, "channel count must be 1 or 3, got %d", channels);
+    if (channels == 1 && (r->input_format != BEVW_INPUT_BGR || r->out_nv12() || r->in_pitch_request != 0))
+        return fail(BEVW_E_INVALID, "one channel needs BGR input, BGR output and no input pitch: the remapper's are %s, %s, %d",
+                    input_format_name(r->input_format), r->out_nv12() ? "NV12" : "BGR", r->in_pitch_request);
+    return engine_set(*r, &EngineCore::channels, channels, r->plan_ready);
+}
+
+int bevw_remapper_channels(bevw_remapper *r)
+{
+    if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    return r->channels;
+}
+
+int bevw_remapper_last_path(bevw_remapper *r)
+{
+    if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    return r->last_path;
+}
+
 int bevw_remapper_set_input_pitch(bevw_remapper *r, int pitch_bytes)
 {
     if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    if (pitch_bytes != 0) BEVW_TRY(need_three_channels(r, "an input pitch"));
     BEVW_TRY(check_input_pitch(pitch_bytes, r->fw, r->fh, r->nv12()));
     return engine_set(*r, &EngineCore::in_pitch_request, pitch_bytes, r->plan_ready);
 }
 
-// one remap step: the plan, or the per-pixel kernel (NV12 images on the plan need dword-aligned quads in the caller's rows, dw % 4 == 0)
+// one remap step: the plan, or the per-pixel kernel (NV12 images on the plan need dword-aligned quads in the caller's rows, dw % 4 == 0).
+// One channel: a quad is one dword of the caller's rows (dw % 4 == 0, no padded scratch), and the plan is the unit schedule or nothing --
+// a step its units do not serve (no list, BEVW_PLAN_UNITS=0) runs the per-pixel kernel.
 static int remap_step(bevw_remapper *r, const FrameSource &src, int batch, void *d_dst)
 {
+    const bool gray = r->channels == 1;
     if (r->plan_ready && (!src.is_surf() || r->plan.src_pitch == src.pitch) && src.aligned4() && (((uintptr_t)d_dst) & 3u) == 0 &&
-        (!r->out_nv12() || r->dw % 4 == 0)) {
+        (!(r->out_nv12() || gray) || r->dw % 4 == 0)) {
         PlanStep step;
         step.src = src; step.batch = batch; step.out = (uint8_t *)d_dst;
-        return plan_stitch(r->plan, r->stream, step);
+        const bool units = plan_units_serve(r->plan, step);
+        if (units || !gray) {
+            r->last_path = units ? BEVW_PATH_UNITS : BEVW_PATH_PER_PIXEL;
+            return plan_stitch(r->plan, r->stream, step);
+        }
     }
+    r->last_path = BEVW_PATH_PER_PIXEL;
     return remap_launch(r->stream, src, r->fw, r->fh, r->map1.as<int16_t>(), r->map2.as<uint16_t>(), r->dw, r->dh, batch, (uint8_t *)d_dst,
                         r->ties_even, r->out_nv12());
 }
@@ -747,6 +791,7 @@ static int remap_step(bevw_remapper *r, const FrameSource &src, int batch, void 
 int bevw_remap_surface_table_device(bevw_remapper *r, const void *d_surfaces, int batch, void *d_dst)
 {
     if (!r || !d_surfaces || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
+    BEVW_TRY(need_three_channels(r, "surfaces are NV12"));
     BEVW_TRY(need_surface_input(*r));
     if (((uintptr_t)d_surfaces) & 7u) return fail(BEVW_E_INVALID, "the surface table is not 8-byte aligned");
     if (batch == 0) return BEVW_OK;
@@ -757,6 +802,7 @@ int bevw_remap_surface_table_device(bevw_remapper *r, const void *d_surfaces, in
 int bevw_remap_surfaces_device(bevw_remapper *r, const bevw_nv12_surface *surfaces, int batch, void *d_dst)
 {
     if (!r || !surfaces || !d_dst || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
+    BEVW_TRY(need_three_channels(r, "surfaces are NV12"));
     BEVW_TRY(need_surface_input(*r));
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
@@ -776,6 +822,7 @@ int bevw_remapper_set_output_format(bevw_remapper *r, int format)
 {
     if (!r) return fail(BEVW_E_INVALID, "null remapper");
     if (format != BEVW_OUTPUT_BGR && format != BEVW_OUTPUT_NV12) return fail(BEVW_E_INVALID, "unknown output format %d", format);
+    if (format == BEVW_OUTPUT_NV12) BEVW_TRY(need_three_channels(r, "NV12 output"));
     if (format == BEVW_OUTPUT_NV12 && (r->dw % 2 || r->dh % 2))
         return fail(BEVW_E_INVALID, "NV12 output needs an even destination width and height, got %dx%d", r->dw, r->dh);
     return engine_set(*r, &EngineCore::output_format, format, r->plan_ready);
@@ -784,6 +831,7 @@ int bevw_remapper_set_output_format(bevw_remapper *r, int format)
 int bevw_remapper_set_input_format(bevw_remapper *r, int format)
 {
     if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    if (input_format_known(format) && format != BEVW_INPUT_BGR) BEVW_TRY(need_three_channels(r, "an input format other than BGR"));
     BEVW_TRY(check_input_format(*r, format));
     return engine_set(*r, &EngineCore::input_format, format, r->plan_ready);
 }
@@ -794,7 +842,7 @@ int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst)
     BEVW_TRY(need_packed_frames(*r));
     if (batch == 0) return BEVW_OK;
     BEVW_TRY(use_device(r->device));
-    const size_t nin = (size_t)batch * frame_bytes_of(r->fw, r->fh, r->fmt()), nout = (size_t)batch * image_bytes_of(r->dw, r->dh, r->out_nv12());
+    const size_t nin = (size_t)batch * frame_bytes_of(r->fw, r->fh, r->fmt()), nout = (size_t)batch * r->image_bytes();
     BEVW_TRY(r->in.reserve(nin));
     BEVW_TRY(r->out.reserve(nout));
     HIP_TRY(hipMemcpyAsync(r->in.p, src, nin, hipMemcpyHostToDevice, r->stream));

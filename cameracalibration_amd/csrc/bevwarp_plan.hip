@@ -10,7 +10,7 @@ void plan_release(Plan &p)
     void *ptrs[] = {p.un_desc, p.un_entries, p.list_un_all, p.entries, p.hdr, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
-    for (int l = 0; l < kSrcLayouts; ++l)
+    for (int l = 0; l < kPlanLayouts; ++l)
         for (void *q : {p.units[l], p.sampled[l]}) if (q) (void)hipFree(q);
     p = Plan();
 }
@@ -78,12 +78,14 @@ int plan_stitch(Plan &p, hipStream_t st, const PlanStep &step)
     return BEVW_OK;
 }
 
+bool plan_units_serve(const Plan &p, const PlanStep &step) { return plan_route(plan_route_in(p, step, plan_tuning())).use_units; }
+
 int plan_set_format(Plan &p, SrcFormat fmt, bool out_nv12, int src_pitch)
 {
     p.fmt = fmt; p.out_nv12 = out_nv12;
-    // The translated frame layouts: the lists of packed NV12 and of packed 4:2:2 are made when such a format is first set, the surface lists
+    // The translated frame layouts: the lists of packed NV12, of packed 4:2:2 and of one channel are made when such a format is first set, the surface lists
     // whenever the pitch is another one (pitch 0: none, as after plan_build)
-    static const char *const names[kSrcLayouts] = {"BGR", "NV12", "surface", "4:2:2", "compact"};
+    static const char *const names[kPlanLayouts] = {"BGR", "NV12", "surface", "4:2:2", "compact", "one-channel"};
     const bool new_pitch = src_pitch != p.src_pitch;
     p.src_pitch = src_pitch;
     for (SrcLayout l : {frames_layout(fmt, false), kLayoutSurf}) {

@@ -375,6 +375,21 @@ int bevw_remap_surface_table_device(bevw_remapper *r, const void *d_surfaces, in
  * images [batch][dst_h*3/2][dst_w] -- the NV12 form of what the BGR remapper writes.  Combines with either input format.  Refused
  * (BEVW_E_INVALID) for an odd dst_w or dst_h. */
 int bevw_remapper_set_output_format(bevw_remapper *r, int format);
+/* Single-channel images: what cv2.remap does with an (H, W) uint8 array.  channels = 3 (the default) or 1.  With 1, bevw_remap and
+ * bevw_remap_device read src as [batch][src_h][src_w] and write dst as [batch][dst_h][dst_w], one byte per pixel: INTER_LINEAR,
+ * BORDER_CONSTANT 0, byte for byte cv2.remap(grey, map1, map2, INTER_LINEAR) in either BEVW_COMPAT_REMAP mode.  The maps, the plan and
+ * the unit schedule are the three-channel remapper's; the step runs the unit kernel where src_w % 4 == 0, dst_w % 4 == 0 and both device
+ * pointers are 4-byte aligned, and the per-pixel kernel otherwise (bevw_remapper_last_path tells).  The setter waits for every queued
+ * step of the remapper.  One channel is BGR in and out with dense rows: bevw_remapper_set_channels(r, 1) is refused (BEVW_E_INVALID)
+ * on a remapper with another input format, NV12 output or an input pitch, and on a one-channel remapper every input format but BGR,
+ * BEVW_OUTPUT_NV12, an input pitch and the surface entry points are refused; bevw_last_error() names the channel count each time. */
+int bevw_remapper_set_channels(bevw_remapper *r, int channels);
+int bevw_remapper_channels(bevw_remapper *r);   /* 1 or 3 */
+/* Which kernels served the remapper's last step, whatever its channel count (a diagnostic: tests assert it instead of assuming it). */
+#define BEVW_PATH_NONE 0        /* no step yet */
+#define BEVW_PATH_UNITS 1       /* the unit kernel (+ the per-tap kernel for the base tiles whose footprints touch the frame border) */
+#define BEVW_PATH_PER_PIXEL 2   /* no unit kernel: the k_remap_lut family (three channels with a plan that has no units: its per-tap kernel) */
+int bevw_remapper_last_path(bevw_remapper *r);
 int bevw_remapper_sync(bevw_remapper *r);
 int bevw_remapper_timer_start(bevw_remapper *r);
 int bevw_remapper_timer_stop(bevw_remapper *r, float *elapsed_ms);

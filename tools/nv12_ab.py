@@ -67,16 +67,17 @@ class Stitch:
 
 
 class Remap:
-    def __init__(self, fmt, unique, batch):
+    def __init__(self, fmt, unique, batch, channels=3):
+        """channels=1: a one-channel remapper on frames [height, width] (tools/gray_ab.py)."""
         from cameracalibration_amd.Tools import undistort as U
 
         c = W.CONFIG_UNDISTORT
         K, D = W.undistort_calibration()
         self.u = U.Undistorter(K, D, c["FRAME_WIDTH"], c["FRAME_HEIGHT"], focalscale=c["FOCAL_SCALE"], sizescale=c["SIZE_SCALE"],
-                               input_format=fmt)
+                               input_format=fmt, channels=channels)
         self.batch, self.r, L = batch, self.u._r, _ffi.lib()
         self.d_in = replicated(unique, batch)
-        self.img = self.u.out_w * self.u.out_h * 3
+        self.img = self.u.out_image_bytes
         self.d_out = _ffi.DeviceBuffer(batch * self.img)
         self.sync = lambda: _ffi.check(L.bevw_remapper_sync(self.r))
         self.tstart = lambda: _ffi.check(L.bevw_remapper_timer_start(self.r))
@@ -97,7 +98,7 @@ class Remap:
         _ffi.check(_ffi.lib().bevw_remap_device(self.r, self.d_in.ptr, self.batch, self.d_out.ptr))
 
     def fetch(self, b):
-        return self.d_out.download((self.u.out_h, self.u.out_w, 3), offset=b * self.img)
+        return self.d_out.download((self.u.out_h, self.u.out_w) + ((3,) if self.u.channels == 3 else ()), offset=b * self.img)
 
 
 def timed(run, steps):
