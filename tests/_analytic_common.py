@@ -46,6 +46,8 @@ def shifted_rig():
 
 
 RIGS = {"small": small_rig, "shifted": shifted_rig}
+import _rigs  # noqa: E402  (the rig catalogue: its analytic subset, all at SMALL_CFG)
+RIGS.update({_n: (lambda _n=_n: _rigs.family(_n)[0]) for _n in _rigs.ANALYTIC})
 
 
 def make_frames(n, cfg=SMALL_CFG, seed=13, cast=False):
