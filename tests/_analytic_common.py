@@ -19,18 +19,12 @@ Measured values (test_analytic.py prints them and asserts they have not moved pa
                      (the disturbed bytes themselves); where the disturbance moves a gain across a rounding tie of one of the 3 x 256
                      (channel, value) products, every byte of that value flips: 1.9e-3 ... 3.9e-3.
 """
-import os
-import sys
-
 import numpy as np
 
 from cameracalibration_amd import workloads as W
 from oracle import np_analytic, oracle as O
-
-TESTS = os.path.dirname(os.path.abspath(__file__))
-if TESTS not in sys.path:
-    sys.path.insert(0, TESTS)
-from test_gpu_parity import SMALL_CFG, small_rig  # noqa: E402
+from tests import _rigs   # the rig catalogue: its analytic subset, all at SMALL_CFG
+from tests._harness import SMALL_CFG, small_rig
 
 F32_POSITION_ERROR = 4.1e-3      # measured 4.06e-3 (see above)
 F32_EPS = 4 * F32_POSITION_ERROR
@@ -46,7 +40,6 @@ def shifted_rig():
 
 
 RIGS = {"small": small_rig, "shifted": shifted_rig}
-import _rigs  # noqa: E402  (the rig catalogue: its analytic subset, all at SMALL_CFG)
 RIGS.update({_n: (lambda _n=_n: _rigs.family(_n)[0]) for _n in _rigs.ANALYTIC})
 
 
@@ -212,3 +205,14 @@ def check_f32(got, want, band_px, what=""):
     print("%s: fp32 vs fp64 specification outside the band (%d px inside): PSNR %.1f dB, %.2f %% identical, max %d LSB" % (
         what, int(band_px.sum()), p, 100 * float((d == 0).mean()), int(d.max())))
     assert d.max() <= 2 and (d == 0).mean() > 0.97 and p > 55.0, (what, int(d.max()), float((d == 0).mean()), p)
+
+
+def check_batch(got, gen, frames, car, balance, what):
+    """every image of a batch against the specification of its own frame set"""
+    assert got.shape[0] == frames.shape[0]
+    for b in range(frames.shape[0]):
+        want = gen(*frames[b], car)
+        if balance:
+            check_balance(got[b], want, float(gen.gains(*frames[b]).max()), "%s, image %d" % (what, b))
+        else:
+            check_f64(got[b], want, "%s, image %d" % (what, b))

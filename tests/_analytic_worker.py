@@ -11,19 +11,16 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
 
 
 def main():
     case_dir = sys.argv[1]
-    import _analytic_common as AC
-    from cameracalibration_amd import _ffi as ffi
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV as SB
-    from test_gpu_parity import set_args
+    from tests import _analytic_common as AC
+    from tests._harness import set_args, worker_library
 
-    ffi.require_device()
+    ffi, SB = worker_library({})
     jobs = json.load(open(os.path.join(case_dir, "jobs.json")))
     info = {}
     for j in jobs:

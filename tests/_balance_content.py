@@ -6,7 +6,7 @@ rounded per-camera deltas -> the HSV round trip with a saturating V -> per-image
 of them is stored per frame set and indexed on the host and in the kernels; uniform random frames give every set of a batch the same
 statistics (delta 0, gains within 1e-3 of 1), so an index that is wrong by a set, a camera or a ring slot changes nothing there.
 
-The pool: N = 33 frame sets for tests/test_nv12_gpu.SMALL_CFG (33 is a key of PLAIN / SLICES in tests/test_batch_chunks_gpu.py: a
+The pool: N = 33 frame sets for tests/_harness.SMALL_CFG (33 is a key of PLAIN / SLICES in tests/_harness.py: a
 balance step of 33 runs as two slices of 16 and 17 frame sets).  GRADED sets are uniform random bytes times a factor per (set, camera,
 channel) drawn from 8 .. 256, then >> 8: brightness differs per camera and per set, the cast per set.  SPECIAL sets sit at fixed
 positions, five of them in the first nine (batch 9, and the reversed host entry over the first 17):
@@ -39,9 +39,8 @@ import numpy as np
 
 from tests import _nv12_spec as S
 from tests import _yuv422_spec as Y
-from tests import test_nv12_gpu as TI
+from tests._harness import SMALL_CFG as CFG, random_car, small_rig, uncovered  # noqa: F401
 
-CFG = TI.SMALL_CFG
 N = 33
 SEED = 7100
 FORMATS = ("bgr", "nv12", "yuyv", "uyvy")
@@ -152,7 +151,7 @@ def forms(fmt, seed=SEED):
 
 
 def car(cfg=CFG, seed=SEED):
-    return TI.random_car(np.random.default_rng([seed, 99]), cfg)
+    return random_car(np.random.default_rng([seed, 99]), cfg)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -164,7 +163,7 @@ class Chain:
 
     def __init__(self, oracle, blend, cfg=CFG, rig=None):
         self.O, self.L = oracle, oracle.lib()
-        self.plain = oracle.RefBevGenerator(rig or TI.small_rig(), cfg, blend=blend, balance=False)
+        self.plain = oracle.RefBevGenerator(rig or small_rig(), cfg, blend=blend, balance=False)
 
     def vsums(self, frames4):
         return [self.O.sum_v(f) for f in frames4]

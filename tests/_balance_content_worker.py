@@ -5,7 +5,7 @@ argv: case_dir NAME=VALUE [NAME=VALUE ...].  The parent sets the switches in thi
 tests/_balance_content.py (BGR and NV12 forms), the car sprite and the expected images (CPU oracle on the frames, on the
 _nv12_spec-converted frames for NV12) as .npy files in case_dir.  A blend + balance handle per pixel format -- BGR in and out, NV12 in and
 out -- runs batch 33 twice in a row through the device entry, so that ring slots and scratch buffers are reused, each run with the sentinel
-fill and the guard image of tests/test_batch_chunks_gpu.py, every image compared with tolerance 0.  Any refusal by the library ends the
+fill and the guard image of tests/_harness.run_batches, every image compared with tolerance 0.  Any refusal by the library ends the
 worker with its error."""
 import os
 import sys
@@ -15,7 +15,7 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
-from tests import test_batch_chunks_gpu as TB  # noqa: E402
+from tests import _harness as H  # noqa: E402
 
 PREFIXES = ("BEVW_BAL_", "BEVW_GAIN_", "BEVW_PLAN_")
 
@@ -23,18 +23,14 @@ PREFIXES = ("BEVW_BAL_", "BEVW_GAIN_", "BEVW_PLAN_")
 def main():
     case_dir, switches = sys.argv[1], dict(a.split("=", 1) for a in sys.argv[2:])
     name = " ".join(sys.argv[2:])
-    assert switches and all(os.environ.get(k) == v for k, v in switches.items()), "%s must be set before the library loads" % name
-    assert sorted(k for k in os.environ if k.startswith(PREFIXES)) == sorted(switches), "exactly the switches of this worker"
-    from cameracalibration_amd import _ffi as ffi
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV as SB
-
-    ffi.require_device()
+    assert switches, name
+    ffi, SB = H.worker_library(switches, only=PREFIXES)
     z = lambda n: np.load(os.path.join(case_dir, n + ".npy"), mmap_mode="r")
-    inputs = TB.Inputs(ffi, np.asarray(z("nv")), np.asarray(z("bgr")), np.asarray(z("car")))
+    inputs = H.Inputs(ffi, np.asarray(z("nv")), np.asarray(z("bgr")), np.asarray(z("car")))
     try:
         for fmt in ("bgr", "nv12"):
             want = (z("want_" + fmt), z("want_nv12_out") if fmt == "nv12" else None, np.asarray(z("none")))
-            TB.stitch_handle(ffi, SB, inputs, want, fmt, fmt, True, True, batches=(33, 33), host_entry=False, one_slice=True)
+            H.stitch_handle(ffi, SB, inputs, want, fmt, fmt, True, True, batches=(33, 33), host_entry=False, one_slice=True)
             print("ok %s -> %s, blend 1 balance 1, batch 33 twice" % (fmt, fmt), flush=True)
     finally:
         inputs.free()

@@ -130,3 +130,8 @@ def numpy_remap(img, map1, map2):
             p = img[np.clip(ty, 0, sh - 1), np.clip(tx, 0, sw - 1)].astype(np.int64)
             acc += p * (wx * wy * inside)[..., None]
     return ((acc + 512) >> 10).astype(np.uint8)
+
+
+def child_cases():
+    """(family, size, input format) of the plan-off child of tests/test_caller_maps_gpu.py: every family at its first size."""
+    return [(name, sizes(name)[0], inp) for name in FAMILIES for inp in ("bgr", "nv12", "yuyv")]

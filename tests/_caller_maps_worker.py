@@ -12,23 +12,21 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+from tests import _caller_maps as CM  # noqa: E402
+from tests import _harness as H  # noqa: E402
 from tests import _nv12_out_spec as SO  # noqa: E402
-from tests import test_caller_maps_gpu as T  # noqa: E402
 
 
 def main():
     case_file = sys.argv[1]
-    assert os.environ.get("BEVW_REMAP_PLAN") == "0", "BEVW_REMAP_PLAN=0 must be set before the library loads"
-    from cameracalibration_amd import _ffi as ffi
-
-    ffi.require_device()
+    ffi, _ = H.worker_library({"BEVW_REMAP_PLAN": "0"})
     z = np.load(case_file)
-    cases = T.child_cases()
+    cases = CM.child_cases()
     for name, size, inp in cases:
         raw, want = z["raw_%d_%d_%s" % (size[0], size[1], inp)], z["want_%s_%s" % (name, inp)]
-        with T.Remapper(ffi, name, size, inp) as r:
-            for out in T.OUTPUTS:
-                T.assert_equal(r.remap(raw, out), SO.bgr_to_nv12(want) if out == "nv12" else want, "%s %s -> %s, plan off" % (name, inp, out))
+        with H.Remapper(ffi, CM.family(name, *size), size, inp) as r:
+            for out in ("bgr", "nv12"):
+                H.assert_equal(r.remap(raw, out), SO.bgr_to_nv12(want) if out == "nv12" else want, "%s %s -> %s, plan off" % (name, inp, out))
         print("ok", name, inp, flush=True)
     print("worker OK %d cases" % len(cases), flush=True)
 

@@ -13,25 +13,16 @@ sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
 
+from tests import _harness as H  # noqa: E402
 from tests import _nv12_surfaces as SF  # noqa: E402
-from tests import test_nv12_gpu as TI  # noqa: E402
-from tests import test_nv12_out_gpu as TO  # noqa: E402
-from tests import test_nv12_surfaces_gpu as TS  # noqa: E402
 
 MODES = ((0, 0), (1, 0), (0, 1), (1, 1))   # (blend, balance)
 INPUTS = ("bgr", "nv12", "surfaces")
 OUTPUTS = ("bgr", "nv12")
 
 
-def check(out_fmt, got, want_bgr, none, what, black):
-    if out_fmt == "nv12":
-        TO.assert_nv12(got, want_bgr, none, what, black=black)
-    else:
-        TI.assert_same(got, want_bgr, none, what)
-
-
 def stitch(ffi, SB, z):
-    cfg = TI.SMALL_CFG
+    cfg = H.SMALL_CFG
     fw, fh = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"]
     nv, bgr, car = z["nv"], z["bgr"], z["car"]
     surf = SF.Surfaces(ffi, nv.reshape(12, fh * 3 // 2, fw), fw, fh, fw + 4, layout_seed=31, fill_seed=32, mode="shuffled")
@@ -43,19 +34,19 @@ def stitch(ffi, SB, z):
                     what = "%s -> %s, blend %d balance %d" % (inp, out, blend, balance)
                     kw = dict(blend=bool(blend), balance=bool(balance), input_format="bgr" if inp == "bgr" else "nv12", output_format=out)
                     if inp == "surfaces":
-                        bev = TI.generator(SB, TI.small_rig(), cfg, input_pitch=fw + 4, **kw)
+                        bev = H.generator(SB, H.small_rig(), cfg, input_pitch=fw + 4, **kw)
                         assert bev.plan_info()["schedule"] == ffi.SCHED_TILE_PLAN, what
-                        d_out = TS.run_table(ffi, bev, surf.table.reshape(3, 4, 2), car, cfg)
+                        d_out = H.run_table(ffi, bev, surf.table.reshape(3, 4, 2), car, cfg)
                         try:
-                            got = [TS.fetch(ffi, bev, d_out, cfg, b) for b in range(3)]
+                            got = [H.fetch(ffi, bev, d_out, cfg, b) for b in range(3)]
                         finally:
                             d_out.free()
                     else:
-                        bev = TI.generator(SB, TI.small_rig(), cfg, **kw)
+                        bev = H.generator(SB, H.small_rig(), cfg, **kw)
                         assert bev.plan_info()["schedule"] == ffi.SCHED_TILE_PLAN, what
                         got = bev.batch(bgr if inp == "bgr" else nv, car)
                     for b in range(3):
-                        check(out, got[b], want[b], none, "%s, set %d" % (what, b), black=False)
+                        H.check_image(got[b], want[b], none, "%s, set %d" % (what, b), out, black=False)
                     print("ok", what, flush=True)
     finally:
         surf.free()
@@ -64,9 +55,9 @@ def stitch(ffi, SB, z):
 def undistort(ffi, z):
     from cameracalibration_amd.Tools import undistort as U
 
-    cfg = TI.SMALL_CFG
+    cfg = H.SMALL_CFG
     w, h = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"]
-    K, D, _ = TI.small_rig()["front"]
+    K, D, _ = H.small_rig()["front"]
     nv, bgr, want, outside = z["nv"][:, 0], z["bgr"][:, 0], z["und_want"], z["und_outside"]
     surf = SF.Surfaces(ffi, nv, w, h, w + 4, layout_seed=33, fill_seed=34, mode="split")
     try:
@@ -90,7 +81,7 @@ def undistort(ffi, z):
                     got = und(bgr if inp == "bgr" else nv)
                     assert got.shape == shape, what
                 for b in range(3):
-                    check(out, got[b], want[b], outside, "%s, image %d" % (what, b), black=True)
+                    H.check_image(got[b], want[b], outside, "%s, image %d" % (what, b), out, black=True)
                 und.close()
                 print("ok", what, flush=True)
     finally:
@@ -99,11 +90,7 @@ def undistort(ffi, z):
 
 def main():
     case_file, switch = sys.argv[1], sys.argv[2]
-    assert os.environ.get(switch) == "0", "%s=0 must be set before the library loads" % switch
-    from cameracalibration_amd import _ffi as ffi
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV as SB
-
-    ffi.require_device()
+    ffi, SB = H.worker_library({switch: "0"})
     z = np.load(case_file)
     stitch(ffi, SB, z)
     if switch == "BEVW_REMAP_PLAN":

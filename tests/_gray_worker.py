@@ -12,25 +12,22 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from tests import _caller_maps as CM  # noqa: E402
-from tests import test_gray_gpu as T  # noqa: E402
+from tests import _harness as H  # noqa: E402
 
 
 def main():
     case_file = sys.argv[1]
-    assert os.environ.get("BEVW_REMAP_PLAN") == "0", "BEVW_REMAP_PLAN=0 must be set before the library loads"
-    from cameracalibration_amd import _ffi as ffi
-
-    ffi.require_device()
+    ffi, _ = H.worker_library({"BEVW_REMAP_PLAN": "0"})
     z = np.load(case_file)
     frames, want = z["frames"], z["want"]
     size = CM.SMALL
     maps = CM.family("minify8", *size)
-    outside = T.outside_of(maps[0], size[0], size[1])
-    with T.Remapper(ffi, maps, size) as g:
+    outside = H.outside_of(maps[0], size[0], size[1])
+    with H.Remapper(ffi, maps, size, channels=1) as g:
         got = g.remap(frames)
         assert g.last_path() == ffi.PATH_PER_PIXEL, g.last_path()
     for b in range(frames.shape[0]):
-        T.assert_same(got[b], want[b], outside, "plan off, image %d" % b)
+        H.assert_same_gray(got[b], want[b], outside, "plan off, image %d" % b)
     print("worker OK", flush=True)
 
 

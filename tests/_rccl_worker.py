@@ -9,11 +9,10 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
 
-import _shard_common as SC  # noqa: E402
+from tests import _shard_common as SC  # noqa: E402
 from cameracalibration_amd import _ffi, workloads as W  # noqa: E402
 
 BATCH = 3

@@ -1,7 +1,7 @@
 """A catalogue of four-camera rigs other than the sample rig, shared by tests/test_rigs_host.py and tests/test_rigs_gpu.py.
 
 Every rig the other tests stitch is workloads.repo_rig() cropped, scaled or shifted: the cameras look the same way, are mounted the same
-way up and have the same weak barrel distortion.  `family(name) -> (rig, cfg)` derives rigs from test_gpu_parity.small_rig() at SMALL_CFG
+way up and have the same weak barrel distortion.  `family(name) -> (rig, cfg)` derives rigs from _harness.small_rig() at SMALL_CFG
 (320 x 256 frames, 248 x 250 BEV) whose calibration differs in kind: the BEV turned or mirrored, cameras rolled about their axis, strong
 minification and magnification, no distortion, strong barrel and pincushion distortion, principal points far off the centre, unequal focal
 lengths, a steep perspective, four identical cameras, and other SIZE_SCALE / FOCAL_SCALE values (an undistort grid of another size).
@@ -14,15 +14,10 @@ share of the BEV the host emulator's units take (tests/native/unit_emulate.cpp o
 holds plan_info()["tiles_staged"] to the same floors.  None of these values comes from the library under test."""
 import copy
 import math
-import os
-import sys
 
 import numpy as np
 
-TESTS = os.path.dirname(os.path.abspath(__file__))
-if TESTS not in sys.path:
-    sys.path.insert(0, TESTS)
-from test_gpu_parity import SMALL_CFG, small_rig  # noqa: E402
+from tests._harness import SMALL_CFG, small_rig
 
 CAMS = ("front", "back", "left", "right")
 MAGNIFY = 4.0   # the largest whole factor at which every camera keeps a non-fill share of 0.10 (at 5 `right` keeps 0.06, at 8 `left` nothing)

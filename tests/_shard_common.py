@@ -1,15 +1,18 @@
 """Shared inputs of the camera-per-GPU tests (parent and workers must derive identical data)."""
+import socket
+
 import numpy as np
 
-from cameracalibration_amd import workloads as W
-
-CFG = dict(FRAME_WIDTH=320, FRAME_HEIGHT=256, BEV_WIDTH=248, BEV_HEIGHT=250, CAR_WIDTH=62, CAR_HEIGHT=100,
-           FOCAL_SCALE=1.0, SIZE_SCALE=2.0)
+from cameracalibration_amd import workloads as W  # noqa: F401
+from tests._harness import SMALL_CFG as CFG, small_rig as rig  # noqa: F401
 
 
-def rig():
-    A = np.diag([0.25, 0.25, 1.0])
-    return {n: (A @ K, D.copy(), A @ H @ np.linalg.inv(A)) for n, (K, D, H) in W.repo_rig().items()}
+def free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
 
 
 def apply_cfg(cfg=None):

@@ -9,12 +9,11 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
-import _shard_common as SC  # noqa: E402
+from tests import _shard_common as SC  # noqa: E402
 
 
 def main():
@@ -26,7 +25,7 @@ def main():
     SC.apply_cfg()
     factory = None
     if engine == "oracle":
-        from _shard_oracle import OracleShardEngine as factory
+        from tests._shard_oracle import OracleShardEngine as factory
     gen = CS.CameraShardedBev(blend, balance, rig=SC.rig(), rank=rank, world_size=world, engine_factory=factory,
                               transport=SC.GlooTransport(rank, world))
     assert gen.world_size == world and gen.rank == rank

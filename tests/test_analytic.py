@@ -16,21 +16,7 @@ import numpy as np
 import pytest
 
 from cameracalibration_amd import workloads as W
-
-
-@pytest.fixture(scope="module")
-def ffi():
-    from cameracalibration_amd import _ffi
-
-    _ffi.require_device()
-    return _ffi
-
-
-@pytest.fixture(scope="module")
-def SB():
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV
-
-    return surroundBEV
+from tests._harness import SB, ffi  # noqa: F401
 
 
 def psnr(a, b, sel=None):
@@ -99,7 +85,7 @@ def test_balance_specification_shows_the_same_picture_as_the_table_path(oracle, 
 @pytest.mark.parametrize("blend", [False, True])
 def test_balance_specification_parts_on_the_small_rig(oracle, blend):
     """the car goes on after the gain, balance off is the unbalanced generator, the luminance shift is the oracle's"""
-    import _analytic_common as AC
+    from tests import _analytic_common as AC
     from oracle import np_analytic
 
     frames, car = AC.make_frames(1, cast=True)[0], AC.make_car()
@@ -118,7 +104,7 @@ def test_balance_specification_parts_on_the_small_rig(oracle, blend):
 def test_the_shifted_rig_has_partial_footprints_and_the_small_rig_none(oracle):
     """k_stitch_analytic on left-over tiles and the border branches of analytic_sample / k_stitch_perpixel run only where a footprint
     crosses the frame border: the shifted rig has such pixels (and thousands that sample nothing), the small rig none"""
-    import _analytic_common as AC
+    from tests import _analytic_common as AC
 
     for blend in (False, True):
         small, shifted = AC.footprint_census("small", blend=blend), AC.footprint_census("shifted", blend=blend)
@@ -132,7 +118,7 @@ def test_the_shifted_rig_has_partial_footprints_and_the_small_rig_none(oracle):
 def test_fp32_position_error_is_the_recorded_one_and_the_edge_band_is_small(oracle, rig):
     """F32_EPS is measured: the projection in NumPy float32 against float64 on the test rigs, times 4.  The band it defines -- where the
     fp32 mode may decide validity the other way, and nothing is bounded -- holds at most 0.5 % of any camera's masked, valid pixels."""
-    import _analytic_common as AC
+    from tests import _analytic_common as AC
 
     e_uv, e_p, flips = AC.f32_position_error(rig)
     print("%s rig: float32 against float64 positions: |u, v| <= %.3g, |px, py| <= %.3g pixel, %d validity flips; F32_EPS = %.3g" % (
@@ -153,7 +139,7 @@ def test_fp32_position_error_is_the_recorded_one_and_the_edge_band_is_small(orac
 def test_balance_gains_are_far_from_one_and_the_tie_share_is_the_recorded_one(oracle, rig, blend):
     """The cast frames give gains near (1.23, 0.91, 0.91): a wrong channel sum moves the picture.  BALANCE_FLIP_SHARE, from which the
     balance bar's share of identical bytes follows, is measured here: a +-1 disturbance of 0.1 % of the covered pre-gain bytes."""
-    import _analytic_common as AC
+    from tests import _analytic_common as AC
 
     frames = AC.make_frames(3, cast=True)
     gen = AC.spec(rig, blend=blend, balance=True)
@@ -227,10 +213,10 @@ def test_hip_analytic_per_pixel_kernel_f32_against_the_specification(ffi, frames
     from conftest import ROOT
     code = (
         "import numpy as np, sys\n"
-        "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "sys.path.insert(0, %r)\n"
         "from oracle import oracle as O, np_analytic as NA\n"
         "from cameracalibration_amd.SurroundBirdEyeView import surroundBEV as SB\n"
-        "import test_analytic as T, conftest as CT\n"
+        "from tests import _analytic_common as T, conftest as CT\n"
         "rr = CT.RepoRig()\n"
         "a = SB.BevGenerator.get_args()\n"
         "for k, v in dict(O.DEFAULT_CFG).items(): setattr(a, k, v)\n"
@@ -243,7 +229,7 @@ def test_hip_analytic_per_pixel_kernel_f32_against_the_specification(ffi, frames
         "    d = np.abs(got[0].astype(np.int32) - spec.astype(np.int32))\n"
         "    print('per-pixel fp32 kernel vs fp64 specification, blend=%%s: PSNR %%.1f dB, %%.2f %%%% identical, max %%d LSB' %% (blend, T.psnr(spec, got[0]), 100 * (d == 0).mean(), int(d.max())))\n"
         "    assert T.psnr(spec, got[0]) > 55.0 and (d == 0).mean() > 0.97 and d.max() <= 2, (T.psnr(spec, got[0]), (d == 0).mean(), d.max())\n"
-        "print('per-pixel analytic ok')\n") % (ROOT, os.path.join(ROOT, "tests"))
+        "print('per-pixel analytic ok')\n") % ROOT
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, BEVW_ANALYTIC_UNITS="0", BEVW_ANALYTIC_FRAMES=str(frames_per_thread)),
                        capture_output=True, text=True, timeout=600)
     print(r.stdout)

@@ -16,19 +16,17 @@ The switches BEVW_ANALYTIC_UNITS / BEVW_ANALYTIC_FRAMES are read once per proces
 """
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-import _analytic_common as AC
-from _analytic_common import SMALL_CFG
-from test_gpu_parity import random_rig_case, set_args
+from tests import _analytic_common as AC
+from tests import _harness as H
+from tests._analytic_common import SMALL_CFG, check_batch
+from tests._harness import SB, random_rig_case, run_child, set_args  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWITCHES = ("BEVW_ANALYTIC_UNITS", "BEVW_ANALYTIC_FRAMES")
 CHILD_TIMEOUT = 120
 
@@ -42,31 +40,12 @@ def ffi():
     return _ffi
 
 
-@pytest.fixture(scope="module")
-def SB():
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV
-
-    return surroundBEV
-
-
 def generator(SB, rig, cfg, blend, balance=False, projection="analytic"):
-    set_args(SB, cfg)
-    return SB.BevGenerator(blend=blend, balance=balance, rig=AC.RIGS[rig](), projection=projection)
+    return H.generator(SB, AC.RIGS[rig](), cfg, blend=blend, balance=balance, projection=projection)
 
 
 def tiles_left(bev):
     return bev.plan_info()["analytic_tiles_left"]
-
-
-def check_batch(got, gen, frames, car, balance, what):
-    """every image of a batch against the specification of its own frame set"""
-    assert got.shape[0] == frames.shape[0]
-    for b in range(frames.shape[0]):
-        want = gen(*frames[b], car)
-        if balance:
-            AC.check_balance(got[b], want, float(gen.gains(*frames[b]).max()), "%s, image %d" % (what, b))
-        else:
-            AC.check_f64(got[b], want, "%s, image %d" % (what, b))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -229,12 +208,7 @@ def run_worker(tmp_path, env, jobs, frame_sets):
     for name, fr in frame_sets.items():
         np.save(os.path.join(d, name), fr)
     json.dump(jobs, open(os.path.join(d, "jobs.json"), "w"))
-    e = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-    e.update(env)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_analytic_worker.py"), d], env=e, cwd=ROOT, capture_output=True, text=True,
-                       timeout=CHILD_TIMEOUT)
-    print(p.stdout)
-    assert p.returncode == 0 and "worker OK" in p.stdout, "worker exit %d\n%s\n%s" % (p.returncode, p.stdout[-4000:], p.stderr[-4000:])
+    run_child("_analytic_worker.py", [d], env, SWITCHES, CHILD_TIMEOUT)
     info = json.load(open(os.path.join(d, "info.json")))
     return {j["name"]: (np.load(os.path.join(d, "got_%s.npy" % j["name"])), info[j["name"]]) for j in jobs}
 

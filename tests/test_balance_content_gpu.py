@@ -6,42 +6,24 @@ of another camera changes the oracle's image of every graded set, so an index of
 or a clamped step fails here.
 
 Tolerance 0 everywhere, against the CPU oracle on the frames (NV12 / YUYV / UYVY input: on the spec-converted frames; NV12 images: through
-_nv12_out_spec).  The stitch cases reuse Inputs, Expected, run_batches, stitch_handle and check_image of tests/test_batch_chunks_gpu.py
+_nv12_out_spec).  The stitch cases reuse Inputs, Expected, run_batches, stitch_handle and check_image of tests/_harness.py
 with this pool -- their 0x5A fill, their guard image and the reversed host-entry run -- with batches 33 (two slices of 16 and 17 frame
 sets, chunks of 2) and 9 (one slice, chunks of 1) in that order on one handle.  Run with `-m gpu` on an MI355X."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import _balance_content as BC
 from tests import _nv12_out_spec as SO
-from tests import test_batch_chunks_gpu as TB
-from tests import test_nv12_gpu as TI
+from tests import _harness as H
+from tests._harness import SB, ffi, run_child  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = BC.CFG
 BATCHES = (33, 9)
 OF = {"bgr": "bgr", "nv12": "nv12", "surfaces": "nv12", "yuyv": "yuyv", "uyvy": "uyvy"}   # input kind -> the form of the pool it reads
-
-
-@pytest.fixture(scope="module")
-def ffi():
-    from cameracalibration_amd import _ffi
-
-    _ffi.require_device()
-    return _ffi
-
-
-@pytest.fixture(scope="module")
-def SB():
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV
-
-    return surroundBEV
 
 
 @pytest.fixture(scope="module")
@@ -51,7 +33,7 @@ def car():
 
 @pytest.fixture(scope="module")
 def inputs(ffi, car):
-    i = TB.Inputs(ffi, BC.forms("nv12")[0], BC.bgr_pool(), car, yuv422={o: BC.forms(o)[0] for o in ("yuyv", "uyvy")})
+    i = H.Inputs(ffi, BC.forms("nv12")[0], BC.bgr_pool(), car, yuv422={o: BC.forms(o)[0] for o in ("yuyv", "uyvy")})
     yield i
     i.free()
 
@@ -64,7 +46,7 @@ def expected(oracle, car):
     def get(form):
         form = "yuyv" if form == "uyvy" else form   # the same texels (tests/test_balance_content_host.py asserts it)
         if form not in made:
-            made[form] = TB.Expected(oracle, BC.forms(form)[1], car, CFG, BC.N)
+            made[form] = H.Expected(oracle, BC.forms(form)[1], car, CFG, BC.N)
         return made[form]
 
     return get
@@ -77,13 +59,13 @@ def expected(oracle, car):
 @pytest.mark.parametrize("out", ["bgr", "nv12"])
 @pytest.mark.parametrize("inp", ["bgr", "nv12", "surfaces", "yuyv", "uyvy"])
 def test_tile_plan_matches_oracle(ffi, SB, inputs, expected, inp, out, blend):
-    bev = TB.stitch_handle(ffi, SB, inputs, expected(OF[inp])(blend, True), inp, out, blend, True, batches=BATCHES)   # (asserts the unit schedule)
+    bev = H.stitch_handle(ffi, SB, inputs, expected(OF[inp])(blend, True), inp, out, blend, True, batches=BATCHES)   # (asserts the unit schedule)
     assert bev.out_pitch == 256 and ffi.lib().bevw_input_format(bev._engine.h) == ffi.INPUT_FORMATS[OF[inp]]
 
 
 @pytest.mark.parametrize("blend", [False, True])
 def test_tile_plan_dense_layout(ffi, SB, inputs, expected, blend):
-    bev = TB.stitch_handle(ffi, SB, inputs, expected("bgr")(blend, True), "bgr", "bgr", blend, True, batches=BATCHES, output_pitch="dense")
+    bev = H.stitch_handle(ffi, SB, inputs, expected("bgr")(blend, True), "bgr", "bgr", blend, True, batches=BATCHES, output_pitch="dense")
     assert bev.out_pitch == CFG["BEV_WIDTH"]
 
 
@@ -94,12 +76,12 @@ def test_tile_plan_dense_layout(ffi, SB, inputs, expected, blend):
 @pytest.mark.parametrize("bh", [250, 251])
 def test_padded_scratch_one_slice_of_33(ffi, SB, oracle, inputs, bh):
     cfg = dict(CFG, BEV_WIDTH=250, BEV_HEIGHT=bh)
-    car = TI.random_car(np.random.default_rng(7250 + bh), cfg)
-    want_bgr, _, none = TB.Expected(oracle, BC.bgr_pool(), car, cfg, BC.N, nv12=False)(True, True)
-    padded = TB.Inputs(ffi, inputs.nv, inputs.bgr, car)
+    car = H.random_car(np.random.default_rng(7250 + bh), cfg)
+    want_bgr, _, none = H.Expected(oracle, BC.bgr_pool(), car, cfg, BC.N, nv12=False)(True, True)
+    padded = H.Inputs(ffi, inputs.nv, inputs.bgr, car)
     padded.bufs["bgr"] = inputs.packed("bgr")
     try:
-        bev = TB.stitch_handle(ffi, SB, padded, (want_bgr, None, none), "bgr", "bgr", True, True, batches=(33,), cfg=cfg, one_slice=True,
+        bev = H.stitch_handle(ffi, SB, padded, (want_bgr, None, none), "bgr", "bgr", True, True, batches=(33,), cfg=cfg, one_slice=True,
                                output_pitch="dense")
         assert bev.out_pitch == 250 and (250 * bh) % 4 == (0 if bh == 250 else 2)
     finally:
@@ -113,11 +95,11 @@ def test_padded_scratch_one_slice_of_33(ffi, SB, oracle, inputs, bh):
 @pytest.mark.parametrize("out", ["bgr", "nv12"])
 @pytest.mark.parametrize("inp", ["bgr", "nv12"])
 def test_per_pixel_schedule(ffi, SB, inputs, expected, inp, out, blend):
-    bev = TI.generator(SB, TI.small_rig(), CFG, blend=blend, balance=True, schedule=ffi.SCHED_PER_PIXEL, input_format=inp, output_format=out)
+    bev = H.generator(SB, H.small_rig(), CFG, blend=blend, balance=True, schedule=ffi.SCHED_PER_PIXEL, input_format=inp, output_format=out)
     assert bev.plan_info()["schedule"] == ffi.SCHED_PER_PIXEL
     d_in, d_car = inputs.packed(inp), inputs.car.ptr
     launch = lambda B, d_out: bev.run_device(d_in.ptr, B, d_car, d_out.ptr, out_bytes=d_out.nbytes)
-    TB.run_batches(ffi, launch, bev.sync, bev.out_image_bytes, out == "nv12", CFG["BEV_WIDTH"], CFG["BEV_HEIGHT"], bev.out_pitch, (9,),
+    H.run_batches(ffi, launch, bev.sync, bev.out_image_bytes, out == "nv12", CFG["BEV_WIDTH"], CFG["BEV_HEIGHT"], bev.out_pitch, (9,),
                    expected(inp)(blend, True), "per pixel, %s -> %s, blend %d" % (inp, out, blend))
 
 
@@ -127,18 +109,18 @@ def test_per_pixel_fallback_odd_frames(ffi, SB, oracle, out):
     no multiple of 4 or 12, so k_vsum takes single bytes and has tail texels, and the automatic schedule serves every tile per pixel."""
     cfg = dict(CFG, FRAME_WIDTH=321, FRAME_HEIGHT=255)
     frames = BC.graded(np.random.default_rng([BC.SEED, 321]), 5, 321, 255)
-    car = TI.random_car(np.random.default_rng([BC.SEED, 255]), cfg)
-    bev = TI.generator(SB, TI.small_rig(), cfg, blend=True, balance=True, output_format=out)
+    car = H.random_car(np.random.default_rng([BC.SEED, 255]), cfg)
+    bev = H.generator(SB, H.small_rig(), cfg, blend=True, balance=True, output_format=out)
     assert bev.plan_info()["tiles_staged"] == 0
-    ref = oracle.RefBevGenerator(TI.small_rig(), cfg, blend=True, balance=True)
-    none = TI.uncovered(ref)
+    ref = oracle.RefBevGenerator(H.small_rig(), cfg, blend=True, balance=True)
+    none = H.uncovered(ref)
     chain = BC.Chain(oracle, True, cfg)
     deltas = [chain.deltas(f) for f in frames]
     assert len(set(deltas)) == 5 and all(any(d) for d in deltas), deltas   # the content has teeth at this size too
     got = bev.batch(frames, car)
     for b in range(5):
         want = ref(*frames[b], car)
-        TB.check_image(got[b], want, SO.bgr_to_nv12(want) if out == "nv12" else None, none, out == "nv12", "321 x 255 frames -> %s, set %d of 5" % (out, b))
+        H.check_image(got[b], want, none, "321 x 255 frames -> %s, set %d of 5" % (out, b), out, want_nv12=SO.bgr_to_nv12(want) if out == "nv12" else None)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -163,15 +145,9 @@ def case_dir(expected, car, tmp_path_factory):
 
 @pytest.mark.parametrize("switch", sorted(SWITCHES))
 def test_balance_switches(case_dir, switch):
-    worker = os.path.join(ROOT, "tests", "_balance_content_worker.py")
     sw = SWITCHES[switch]
     args = ["%s=%s" % kv for kv in sorted(sw.items())]
-    env = {k: v for k, v in os.environ.items() if not k.startswith(("BEVW_BAL_", "BEVW_GAIN_", "BEVW_PLAN_"))}
-    env.update(sw)
-    p = subprocess.run([sys.executable, worker, case_dir] + args, env=env, cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-    print(p.stdout)
-    assert p.returncode == 0, "%s: worker exit %d\n%s\n%s" % (args, p.returncode, p.stdout[-4000:], p.stderr[-4000:])
-    assert "worker OK %s" % " ".join(args) in p.stdout
+    run_child("_balance_content_worker.py", [case_dir] + args, sw, ("BEVW_BAL_", "BEVW_GAIN_", "BEVW_PLAN_"), CHILD_TIMEOUT, "worker OK %s" % " ".join(args))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -184,9 +160,9 @@ def test_camera_shards(ffi, SB, oracle, expected, car, part):
 
     frames = np.ascontiguousarray(BC.bgr_pool()[:9])
     want = expected("bgr")(True, True)[0][:9]
-    full = TI.generator(SB, TI.small_rig(), CFG, blend=True, balance=True, output_pitch="dense")   # (also leaves CFG in the shared arguments)
+    full = H.generator(SB, H.small_rig(), CFG, blend=True, balance=True, output_pitch="dense")   # (also leaves CFG in the shared arguments)
     CS._sb.BevGenerator.init_args(None)
-    rig_list = [TI.small_rig()[n] for n in W.CAMERA_NAMES]
+    rig_list = [H.small_rig()[n] for n in W.CAMERA_NAMES]
     engines = [CS.HipShardEngine(rig_list, cams, True, True) for cams in part]
     try:
         vsums = np.zeros((9, 4), np.uint64)
@@ -239,7 +215,7 @@ def test_exported_helpers_batches(ffi, oracle, addweighted):
         pool, chain = BC.bgr_pool(), BC.Chain(oracle, False)
         for w, h in ((320, 256), (53, 37)):
             frames = np.ascontiguousarray(pool[list(LUM_SETS), :, :h, :w])
-            got = np.full_like(frames, TB.FILL)
+            got = np.full_like(frames, H.FILL)
             ffi.check(L.bevw_luminance_balance(0, ffi.ptr(frames), 5, w, h, ffi.ptr(got)))
             deltas = [chain.deltas(f) for f in frames]
             assert len(set(deltas)) == 5, deltas
@@ -250,14 +226,14 @@ def test_exported_helpers_batches(ffi, oracle, addweighted):
                         w, h, i, LUM_SETS[i], deltas[i], c)
         for w, h in ((64, 48), (77, 123)):
             imgs = balance_images(w, h, BC.SEED)
-            got = np.full_like(imgs, TB.FILL)
+            got = np.full_like(imgs, H.FILL)
             ffi.check(L.bevw_color_balance(0, ffi.ptr(imgs), 5, w, h, ffi.ptr(got)))
             gains = [chain.gains(im) for im in imgs]
             assert np.isinf(gains[0][0]) and 255 < gains[1][0] < np.inf and gains[4].tolist() == [1.5, 1.0, 0.75], gains
             for i, name in enumerate(("dead channel", "near-dead channel", "dark", "graded cast", "exact ties")):
                 want = oracle.color_balance(imgs[i])
                 assert np.array_equal(got[i], want), "bevw_color_balance %d x %d, addWeighted variant %d, image %d (%s): %s" % (
-                    w, h, addweighted, i, name, TB.first_difference(got[i], want))
+                    w, h, addweighted, i, name, H.first_difference(got[i], want))
     finally:
         L.bevw_set_compat(ffi.COMPAT_ADDWEIGHTED, 1)
         oracle.set_variant(oracle.VARIANT_ADDWEIGHTED, 1)

@@ -94,7 +94,7 @@ def test_pool_layout():
 def test_chain_equals_the_oracle_generator(oracle, case):
     fmt, a = case
     for blend in (False, True):
-        ref = oracle.RefBevGenerator(BC.TI.small_rig(), BC.CFG, blend=blend, balance=True)
+        ref = oracle.RefBevGenerator(BC.small_rig(), BC.CFG, blend=blend, balance=True)
         for b in range(BC.N):
             assert np.array_equal(a.image[blend][b], ref(*a.frames[b], a.car)), "%s, blend %d, set %d" % (fmt, blend, b)
         assert np.array_equal(a.chain[blend].finish(a.pre[blend][2], a.gains[blend][2]), ref(*a.frames[2])), "without the car"
@@ -147,7 +147,7 @@ def test_statistics_of_the_pool(oracle, case):
         assert np.abs(g[at["white"]] - 1.0).max() < 1e-12   # (x + x + x) / 3 / x in fp64
         assert np.isinf(g[at["dead"]][0]) and np.isfinite(g[at["dead"]][1:]).all() and (g[at["dead"]][1:] > 0).all()
         assert 255.0 < g[at["near_dead"]][0] < np.inf and np.isfinite(g[at["near_dead"]][1:]).all()
-        assert a.pre[blend][at["dead"]][..., 0].max() == 0 and a.pre[blend][at["dead"]].max(axis=-1).min(where=~BC.TI.uncovered(a.chain[blend].plain), initial=255) > 0
+        assert a.pre[blend][at["dead"]][..., 0].max() == 0 and a.pre[blend][at["dead"]].max(axis=-1).min(where=~BC.uncovered(a.chain[blend].plain), initial=255) > 0
     assert a.deltas[at["black"]] == a.deltas[at["white"]] == (0, 0, 0, 0)
     want = tuple(-191 if c == BC.WHITE_CAMERA else 64 for c in range(4))
     assert a.deltas[at["black_white"]] == want

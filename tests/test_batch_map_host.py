@@ -12,7 +12,7 @@ import subprocess
 
 import pytest
 
-from tests import test_batch_chunks_gpu as TB
+from tests import _harness as H
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -45,9 +45,9 @@ def plan_args(exe, batches):
 
 
 def test_gpu_batch_sizes_have_the_chunk_shapes_they_were_chosen_for(exe):
-    assert sorted(TB.PLAIN) == sorted(TB.SLICES) == sorted(TB.BATCHES)
-    got = plan_args(exe, sorted(TB.BATCHES))
-    assert got == TB.PLAIN, "the nb heuristic changed: choose the batch sizes of tests/test_batch_chunks_gpu.py again"
+    assert sorted(H.PLAIN) == sorted(H.SLICES) == sorted(H.BATCHES)
+    got = plan_args(exe, sorted(H.BATCHES))
+    assert got == H.PLAIN, "the nb heuristic changed: choose the batch sizes of tests/test_batch_chunks_gpu.py again"
     # what the list is for: nb of 1, 2, 3, 8 and 16; ragged chunks of more than one frame; odd full chunks; an XCD-affine launch with idle
     # chunk slots and one whose chunk count is no multiple of 8; the chunk-major map
     assert {v[0] for v in got.values()} == {1, 2, 3, 8, 16}
@@ -55,8 +55,8 @@ def test_gpu_batch_sizes_have_the_chunk_shapes_they_were_chosen_for(exe):
     assert any(nb % 2 == 1 and nb > 1 and last < nb for nb, _, last, _, _ in got.values())
     assert any(aff == 1 and n % 8 != 0 and idle > 0 for _, n, _, aff, idle in got.values()) and any(aff == 0 for _, _, _, aff, _ in got.values())
     # balance handles: the slices of balance_plan_run, each with a chunk size of its own
-    for batch, slices in TB.SLICES.items():
-        sizes = TB.balance_slices(batch)
+    for batch, slices in H.SLICES.items():
+        sizes = H.balance_slices(batch)
         assert sizes == [s[0] for s in slices] and sum(sizes) == batch, batch
         per = plan_args(exe, sizes)
         assert [(n,) + per[n][:3] for n in sizes] == list(slices), batch

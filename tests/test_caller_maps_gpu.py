@@ -8,9 +8,6 @@ maps) of the BGR frames the NumPy specifications (tests/_nv12_spec.py, tests/_yu
 tests/_nv12_out_spec.bgr_to_nv12 for NV12 images.  Every comparison is at tolerance 0 over all pixels, the ones whose footprint lies
 outside the frame included.  Which path of the plan a family takes is the host leg's statement.  Run with `-m gpu` on an MI355X."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -20,24 +17,15 @@ from tests import _nv12_out_spec as SO
 from tests import _nv12_spec as S
 from tests import _nv12_surfaces as SF
 from tests import _yuv422_spec as Y
+from tests._harness import Remapper, assert_equal, ffi, run_child  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INPUTS = ("bgr", "nv12", "yuyv", "uyvy")
 OUTPUTS = ("bgr", "nv12")
 BATCH = 3
 PATH_FAMILIES = ("scatter", "extremes", "corner", "transpose")   # the per-tap kernel's cases and one the units take whole
-CHILD_INPUTS = ("bgr", "nv12", "yuyv")
 CHILD_TIMEOUT = 180   # seconds: a library load and 16 x 3 small remappers take a few seconds
-
-
-@pytest.fixture(scope="module")
-def ffi():
-    from cameracalibration_amd import _ffi
-
-    _ffi.require_device()
-    return _ffi
 
 
 _frames, _want = {}, {}
@@ -79,64 +67,10 @@ def want_of(oracle, name, size, inp, out="bgr", variant=0):
     return SO.bgr_to_nv12(_want[key]) if out == "nv12" else _want[key]
 
 
-class Remapper:
-    """bevw_remapper_from_maps as a context: the remapper is destroyed on the way out, whatever happened inside."""
-
-    def __init__(self, ffi, name, size, inp="bgr", pitch=0):
-        self.ffi, self.L, self.size, self.r = ffi, ffi.lib(), size, C.c_void_p()
-        sw, sh, dw, dh = size
-        self.m1, self.m2 = CM.family(name, sw, sh, dw, dh)
-        self.inp, self.pitch = inp, pitch
-
-    def __enter__(self):
-        sw, sh, dw, dh = self.size
-        self.ffi.check(self.L.bevw_remapper_from_maps(0, sw, sh, self.ffi.ptr(self.m1), self.ffi.ptr(self.m2), dw, dh, C.byref(self.r)))
-        try:
-            self.ffi.check(self.L.bevw_remapper_set_input_format(self.r, self.ffi.INPUT_FORMATS[self.inp]))
-            if self.pitch:
-                self.ffi.check(self.L.bevw_remapper_set_input_pitch(self.r, self.pitch))
-        except Exception:
-            self.L.bevw_remapper_destroy(self.r)
-            raise
-        return self
-
-    def __exit__(self, *exc):
-        self.L.bevw_remapper_destroy(self.r)
-        return False
-
-    def out_shape(self, out, n=BATCH):
-        dw, dh = self.size[2:]
-        return (n, dh * 3 // 2, dw) if out == "nv12" else (n, dh, dw, 3)
-
-    def remap(self, raw, out="bgr"):
-        self.ffi.check(self.L.bevw_remapper_set_output_format(self.r, self.ffi.OUTPUT_NV12 if out == "nv12" else self.ffi.OUTPUT_BGR))
-        got = np.full(self.out_shape(out, raw.shape[0]), 0x5a, np.uint8)
-        self.ffi.check(self.L.bevw_remap(self.r, self.ffi.ptr(np.ascontiguousarray(raw)), raw.shape[0], self.ffi.ptr(got)))
-        return got
-
-    def remap_surfaces(self, table, out="bgr"):
-        self.ffi.check(self.L.bevw_remapper_set_output_format(self.r, self.ffi.OUTPUT_NV12 if out == "nv12" else self.ffi.OUTPUT_BGR))
-        shape = self.out_shape(out, table.shape[0])
-        d_out = self.ffi.DeviceBuffer(int(np.prod(shape)))
-        try:
-            d_out.fill(0x5a)
-            self.ffi.check(self.L.bevw_remap_surfaces_device(self.r, self.ffi.ptr(np.ascontiguousarray(table)), table.shape[0], d_out.ptr))
-            self.ffi.check(self.L.bevw_remapper_sync(self.r))
-            return d_out.download(shape)
-        finally:
-            d_out.free()
-
-
-def assert_equal(got, want, what):
-    assert got.shape == want.shape, what
-    assert np.array_equal(got, want), "%s: %d of %d bytes differ (first at %s)" % (what, int((got != want).sum()), got.size,
-                                                                                   tuple(int(i) for i in np.argwhere(got != want)[0]))
-
-
 def check_pairs(ffi, oracle, name, size, inputs, outputs):
     for inp in inputs:
         raw = frames_of(size[0], size[1], inp)[0]
-        with Remapper(ffi, name, size, inp) as r:
+        with Remapper(ffi, CM.family(name, *size), size, inp) as r:
             for out in outputs:
                 assert_equal(r.remap(raw, out), want_of(oracle, name, size, inp, out), "%s %s -> %s at %s" % (name, inp, out, size))
 
@@ -147,14 +81,14 @@ def check_pairs(ffi, oracle, name, size, inputs, outputs):
 @pytest.mark.parametrize("name", CM.FAMILIES)
 def test_maps_round_trip_and_bgr(ffi, oracle, name):
     size = CM.sizes(name)[0]
-    with Remapper(ffi, name, size) as r:
+    with Remapper(ffi, CM.family(name, *size), size, "bgr") as r:
         g1, g2 = np.full_like(r.m1, 0x5a5a), np.full_like(r.m2, 0x5a5a)
         ffi.check(r.L.bevw_remapper_get_maps(r.r, ffi.ptr(g1), ffi.ptr(g2)))
         assert g1.tobytes() == r.m1.tobytes() and g2.tobytes() == r.m2.tobytes()
         dims = (C.c_int32 * 4)()
         ffi.check(r.L.bevw_remapper_dims(r.r, dims))
         assert tuple(dims) == size
-        assert_equal(r.remap(frames_of(size[0], size[1], "bgr")[0]), want_of(oracle, name, size, "bgr"), name)
+        assert_equal(r.remap(frames_of(size[0], size[1], "bgr")[0], "bgr"), want_of(oracle, name, size, "bgr"), name)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -194,7 +128,7 @@ def test_nv12_surfaces_equal_packed_frames(ffi, oracle, name):
     raw = frames_of(sw, sh, "nv12")[0]
     surf = SF.Surfaces(ffi, raw, sw, sh, sw + 4, layout_seed=71, fill_seed=72, mode="shuffled")
     try:
-        with Remapper(ffi, name, size, "nv12") as packed, Remapper(ffi, name, size, "nv12", pitch=sw + 4) as r:
+        with Remapper(ffi, CM.family(name, *size), size, "nv12") as packed, Remapper(ffi, CM.family(name, *size), size, "nv12", pitch=sw + 4) as r:
             for out in OUTPUTS:
                 got = r.remap_surfaces(surf.table, out)
                 assert_equal(got, want_of(oracle, name, size, "nv12", out), "%s surfaces -> %s" % (name, out))
@@ -215,8 +149,8 @@ def test_tie_rule_half_to_even(ffi, oracle):
         for name in CM.FAMILIES:
             size = CM.sizes(name)[0]
             for inp in ("bgr", "nv12"):
-                with Remapper(ffi, name, size, inp) as r:
-                    got = r.remap(frames_of(size[0], size[1], inp)[0])
+                with Remapper(ffi, CM.family(name, *size), size, inp) as r:
+                    got = r.remap(frames_of(size[0], size[1], inp)[0], "bgr")
                 assert_equal(got, want_of(oracle, name, size, inp, variant=1), "%s %s, ties to even" % (name, inp))
                 if not np.array_equal(got, want_of(oracle, name, size, inp)):
                     seen_tie.append(name)
@@ -229,20 +163,11 @@ def test_tie_rule_half_to_even(ffi, oracle):
 # ---------------------------------------------------------------------------------------------------------------
 # 6. the plan switched off (BEVW_REMAP_PLAN=0, read once per process): k_remap_lut on the whole catalogue, in a fresh child
 # ---------------------------------------------------------------------------------------------------------------
-def child_cases():
-    return [(name, CM.sizes(name)[0], inp) for name in CM.FAMILIES for inp in CHILD_INPUTS]
-
-
 def test_plan_switched_off(oracle, tmp_path):
     z = {}
-    for name, size, inp in child_cases():
+    for name, size, inp in CM.child_cases():
         z["raw_%d_%d_%s" % (size[0], size[1], inp)] = frames_of(size[0], size[1], inp)[0]
         z["want_%s_%s" % (name, inp)] = want_of(oracle, name, size, inp)
     case_file = str(tmp_path / "case.npz")
     np.savez(case_file, **z)
-    env = dict(os.environ, BEVW_REMAP_PLAN="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_caller_maps_worker.py"), case_file], env=env, cwd=ROOT, capture_output=True,
-                       text=True, timeout=CHILD_TIMEOUT)
-    print(p.stdout)
-    assert p.returncode == 0, "worker exit %d\n%s\n%s" % (p.returncode, p.stdout[-4000:], p.stderr[-4000:])
-    assert "worker OK %d cases" % len(child_cases()) in p.stdout
+    run_child("_caller_maps_worker.py", [case_file], {"BEVW_REMAP_PLAN": "0"}, timeout=CHILD_TIMEOUT, expect="worker OK %d cases" % len(CM.child_cases()))

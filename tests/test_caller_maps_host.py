@@ -19,7 +19,7 @@ import pytest
 from oracle import oracle as O
 from tests import _caller_maps as CM
 from tests import _native_build
-from tests.test_unit_schedule import _run
+from tests._native_build import run_units as _run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.skipif(not _native_build.hipcc_path(), reason="hipcc not available")

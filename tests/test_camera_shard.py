@@ -11,9 +11,9 @@ import sys
 import numpy as np
 import pytest
 
-import _shard_common as SC
 from conftest import ROOT
-from test_dist_cpu import free_port
+from tests import _shard_common as SC
+from tests._shard_common import free_port
 
 
 def reference_bevs(oracle, blend, balance, with_car):
@@ -45,7 +45,7 @@ def test_camera_assignment():
 def test_stand_in_engine_matches_reference_single_rank(oracle, blend, balance):
     """Pins the checker: the oracle-built shard engine, world 1, equals the monolithic oracle generator."""
     from cameracalibration_amd.SurroundBirdEyeView import cameraShard as CS
-    from _shard_oracle import OracleShardEngine
+    from tests._shard_oracle import OracleShardEngine
 
     SC.apply_cfg()
     gen = CS.CameraShardedBev(blend, balance, rig=SC.rig(), rank=0, world_size=1, engine_factory=OracleShardEngine)
@@ -147,7 +147,7 @@ def test_hip_shards_with_a_bev_width_that_is_not_a_multiple_of_4(oracle, bw):
 def test_hip_shard_box_and_errors():
     from cameracalibration_amd import _ffi
     from cameracalibration_amd.SurroundBirdEyeView import cameraShard as CS
-    from _shard_oracle import OracleShardEngine
+    from tests._shard_oracle import OracleShardEngine
 
     SC.apply_cfg()
     CS._sb.BevGenerator.init_args(None)
@@ -247,7 +247,7 @@ def rccl_world_n_parity(out_dir, world, extra_env=None):
     """Spawns one worker per GPU (tests/_rccl_worker.py, the product's native RCCL transport, no torch) and compares what the stitch ranks
     wrote with BevGenerator(blend=True, balance=True) on the same 4K frame sets -- bit-exact.  Also used by bench.py before it times the
     camera-shard workload on more than one GPU."""
-    import _rccl_worker as RW
+    from tests import _rccl_worker as RW
     from cameracalibration_amd.SurroundBirdEyeView import surroundBEV as SB
 
     port = free_port()

@@ -1,18 +1,10 @@
 """The N>1 path of bench.py on CPU: world_size 2 over gloo (one process per rank, as the driver launches it)."""
 import os
-import socket
 import subprocess
 import sys
 
 from conftest import ROOT
-
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from tests._shard_common import free_port
 
 
 def test_two_rank_barrier_max_and_sharding(tmp_path):

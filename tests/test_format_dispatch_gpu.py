@@ -5,24 +5,19 @@
   BEVW_REMAP_PLAN=0   remap_launch (k_remap_lut) on an aligned remapper that would otherwise run its plan; the per-pixel stitch is untouched
 
 The library reads the switches once per process, so each runs in a fresh child (tests/_format_dispatch_worker.py), one after the other,
-each under its own timeout; the first child that does not exit 0 ends the test.  Every child runs the small rig of tests/test_nv12_gpu.py
+each under its own timeout; the first child that does not exit 0 ends the test.  Every child runs the small rig of tests/_harness.py
 (320 x 256 frames, 248 x 250 BEV, batch 3) over packed BGR, packed NV12 and NV12 surfaces at pitch FW + 4, BGR and NV12 images, all four
 (blend, balance) modes, each with a car; the BEVW_REMAP_PLAN=0 child also the fisheye undistorter at batch 3.  Expected values: the CPU
 oracle on the _nv12_spec-converted frames (through _nv12_out_spec for NV12 images), computed once here and shared through a file;
 tolerance 0, pixels no camera covers included.  Run with `-m gpu` on an MI355X."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from tests import _nv12_spec as S
-from tests import test_nv12_gpu as TI
+from tests import _harness as H
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SWITCHES = ("BEVW_BAL_MODE", "BEVW_PLAN_UNITS", "BEVW_REMAP_PLAN")
 MODES = ((0, 0), (1, 0), (0, 1), (1, 1))   # (blend, balance), as in the worker
 CHILD_TIMEOUT = 180   # seconds: a library load, 24 small handles (+ 6 remappers) and their steps take a few seconds
@@ -30,20 +25,20 @@ CHILD_TIMEOUT = 180   # seconds: a library load, 24 small handles (+ 6 remappers
 
 @pytest.fixture(scope="module")
 def case_file(oracle, tmp_path_factory):
-    cfg = TI.SMALL_CFG
+    cfg = H.SMALL_CFG
     fw, fh = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"]
     rng = np.random.default_rng(4100)
     nv = S.random_nv12(rng, (3, 4), fw, fh)
     bgr = np.stack([np.stack(S.nv12_to_bgr(nv[b])) for b in range(3)])
-    car = TI.random_car(rng, cfg)
+    car = H.random_car(rng, cfg)
     z = dict(nv=nv, bgr=bgr, car=car)
     for m, (blend, balance) in enumerate(MODES):
-        ref = oracle.RefBevGenerator(TI.small_rig(), cfg, blend=bool(blend), balance=bool(balance))
-        z["none%d" % m] = TI.uncovered(ref)
+        ref = oracle.RefBevGenerator(H.small_rig(), cfg, blend=bool(blend), balance=bool(balance))
+        z["none%d" % m] = H.uncovered(ref)
         assert z["none%d" % m].any()
         z["want%d" % m] = np.stack([ref(*bgr[b], car) for b in range(3)])
     # the fisheye undistorter of the front camera, default scales: the output has the frame's size
-    K, D, _ = TI.small_rig()["front"]
+    K, D, _ = H.small_rig()["front"]
     o1, o2 = oracle.fisheye_init_undistort_rectify_map(K, D, oracle.camera_mat_dst(K, fw, fh, 1.0, 1.0), (fw, fh))
     z["und_size"] = np.array([fw, fh])
     z["und_outside"] = (o1[..., 0] < -1) | (o1[..., 0] >= fw) | (o1[..., 1] < -1) | (o1[..., 1] >= fh)
@@ -54,11 +49,5 @@ def case_file(oracle, tmp_path_factory):
 
 
 def test_switched_branches_match_oracle(case_file):
-    worker = os.path.join(ROOT, "tests", "_format_dispatch_worker.py")
     for switch in SWITCHES:
-        env = {k: v for k, v in os.environ.items() if k not in SWITCHES}
-        env[switch] = "0"
-        p = subprocess.run([sys.executable, worker, case_file, switch], env=env, cwd=ROOT, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-        print(p.stdout)
-        assert p.returncode == 0, "%s=0: worker exit %d\n%s\n%s" % (switch, p.returncode, p.stdout[-4000:], p.stderr[-4000:])
-        assert "worker OK " + switch in p.stdout
+        H.run_child("_format_dispatch_worker.py", [case_file, switch], {switch: "0"}, SWITCHES, CHILD_TIMEOUT, "worker OK " + switch)

@@ -19,24 +19,14 @@ from cameracalibration_amd import workloads as W
 from tests import _nv12_spec as S
 from tests import _nv12_surfaces as SF
 from tests import _yuv422_spec as Y
-from tests import test_nv12_gpu as TI
-from tests import test_nv12_out_gpu as TO
+from tests._harness import SMALL_CFG as CFG, check_image, ffi, random_car, small_rig, uncovered  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-CFG = TI.SMALL_CFG
 FW, FH, BW, BH = CFG["FRAME_WIDTH"], CFG["FRAME_HEIGHT"], CFG["BEV_WIDTH"], CFG["BEV_HEIGHT"]
 BATCH = 3
 # (input kind, input pitch of the surfaces): one step after every change
 WALK = (("bgr", 0), ("nv12", 0), ("surfaces", FW + 4), ("surfaces", FW + 64), ("nv12", 0), ("yuyv", 0), ("uyvy", 0), ("nv12", 0), ("bgr", 0))
-
-
-@pytest.fixture(scope="module")
-def ffi():
-    from cameracalibration_amd import _ffi
-
-    _ffi.require_device()
-    return _ffi
 
 
 def make_inputs(rng, cams):
@@ -91,10 +81,7 @@ def check_images(walker, sync, nv12_out, shape, want, none, what, black):
     else:
         got = walker.out.download((BATCH, shape[0], shape[1], 3))
     for b in range(BATCH):
-        if nv12_out:
-            TO.assert_nv12(got[b], want[b], none, "%s, set %d" % (what, b), black=black)
-        else:
-            TI.assert_same(got[b], want[b], none, "%s, set %d" % (what, b))
+        check_image(got[b], want[b], none, "%s, set %d" % (what, b), "nv12" if nv12_out else "bgr", black)
 
 
 @pytest.mark.parametrize("blend,balance", [(0, 0), (1, 1)])
@@ -102,10 +89,10 @@ def test_one_handle_through_every_input_layout(ffi, oracle, blend, balance):
     L = ffi.lib()
     rng = np.random.default_rng(9100 + blend)
     raw, bgr = make_inputs(rng, 4)
-    car = TI.random_car(rng, CFG)
-    rig = TI.small_rig()
+    car = random_car(rng, CFG)
+    rig = small_rig()
     ref = oracle.RefBevGenerator(rig, CFG, blend=bool(blend), balance=bool(balance))
-    none = TI.uncovered(ref)
+    none = uncovered(ref)
     assert none.any()
     want = {k: [ref(*v[b], car) for b in range(BATCH)] for k, v in bgr.items()}   # once per kind of input, shared by the steps
     cfg = ffi.bevw_config(FW, FH, BW, BH, CFG["CAR_WIDTH"], CFG["CAR_HEIGHT"], CFG["FOCAL_SCALE"], CFG["SIZE_SCALE"], blend, balance, 0, ffi.SCHED_AUTO)
@@ -144,7 +131,7 @@ def test_one_remapper_through_every_input_layout(ffi, oracle):
     L = ffi.lib()
     rng = np.random.default_rng(9200)
     raw, bgr = make_inputs(rng, 1)
-    K, D, _ = TI.small_rig()["front"]
+    K, D, _ = small_rig()["front"]
     r = C.c_void_p()
     K9, D4 = ffi.f64(K, 9), ffi.f64(D, 4)   # (held until the call returns)
     ffi.check(L.bevw_fisheye_remapper_create(0, FW, FH, ffi.ptr(K9), ffi.ptr(D4), 1.0, 1.0, 0.0, 0.0, C.byref(r)))

@@ -8,31 +8,11 @@ import numpy as np
 import pytest
 
 from cameracalibration_amd import workloads as W
+from tests._harness import SMALL_CFG, SB, ffi, random_rig_case, set_args, small_rig  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 CAMS = W.CAMERA_NAMES
-
-
-@pytest.fixture(scope="module")
-def ffi():
-    from cameracalibration_amd import _ffi
-
-    _ffi.require_device()
-    return _ffi
-
-
-@pytest.fixture(scope="module")
-def SB():
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV
-
-    return surroundBEV
-
-
-def set_args(SB, cfg):
-    ns = SB.BevGenerator.get_args()
-    for k, v in cfg.items():
-        setattr(ns, k, v)
 
 
 def make_pair(SB, oracle, rig, cfg, blend, balance, schedule=0):
@@ -44,21 +24,6 @@ def make_pair(SB, oracle, rig, cfg, blend, balance, schedule=0):
 
 def maxdiff(a, b):
     return int(np.abs(a.astype(np.int32) - b.astype(np.int32)).max())
-
-
-# A small rig whose geometry exercises every path quickly: the repo rig scaled to 320x256 frames -> 250x250 BEV.
-SMALL_CFG = dict(FRAME_WIDTH=320, FRAME_HEIGHT=256, BEV_WIDTH=248, BEV_HEIGHT=250, CAR_WIDTH=62, CAR_HEIGHT=100,
-                 FOCAL_SCALE=1.0, SIZE_SCALE=2.0)
-
-
-def small_rig():
-    out = {}
-    A = np.diag([0.25, 0.25, 1.0])  # raw frame scaled by 1/4
-    for n, (K, D, H) in W.repo_rig().items():
-        Ks = A @ K
-        # undistorted grid also scales by 1/4; BEV by 1/4: H_s = A . H . A^-1
-        out[n] = (Ks, D.copy(), A @ H @ np.linalg.inv(A))
-    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -508,35 +473,6 @@ def test_scale_image_mirror(ffi, oracle, repo_rig, square):
     assert got.shape == img.shape and np.array_equal(got, want)
 
 
-def random_rig_case(seed):
-    """The seeded geometry fuzz of test_random_rigs_modes_and_batches (shared with tests/test_analytic_gpu.py): frame / BEV / car sizes
-    (odd ones included), focal and size scales, modes, batch size, frames, an optional car and a schedule."""
-    rng = np.random.default_rng(1000 + seed)
-    fw = int(rng.choice([160, 200, 236, 320, 322, 400]))
-    fh = int(rng.choice([128, 150, 256, 258]))
-    bw = int(rng.choice([96, 124, 125, 200, 248, 250]))
-    bh = int(rng.choice([96, 130, 201, 250]))
-    cw, ch = int(rng.integers(0, bw // 3 + 1)), int(rng.integers(0, bh // 2 + 1))
-    cfg = dict(FRAME_WIDTH=fw, FRAME_HEIGHT=fh, BEV_WIDTH=bw, BEV_HEIGHT=bh, CAR_WIDTH=cw, CAR_HEIGHT=ch,
-               FOCAL_SCALE=float(rng.choice([0.8, 1.0, 1.25])), SIZE_SCALE=float(rng.choice([1.0, 1.5, 2.0])))
-    # the repo rig scaled to the frame (raw frame by fw/1280, fh/1024) and to the BEV (by bw/1000, bh/1000)
-    A = np.diag([fw / 1280.0, fh / 1024.0, 1.0])
-    U = np.diag([fw * cfg["SIZE_SCALE"] / 2560.0, fh * cfg["SIZE_SCALE"] / 2048.0, 1.0])   # undistorted grid scale
-    Bm = np.diag([bw / 1000.0, bh / 1000.0, 1.0])
-    rig = {n: (A @ K, D.copy(), Bm @ H @ np.linalg.inv(U)) for n, (K, D, H) in W.repo_rig().items()}
-    blend, balance = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
-    batch = int(rng.integers(1, 6))
-    frames = rng.integers(0, 256, (batch, 4, fh, fw, 3), dtype=np.uint8)
-    frames[:, 1] //= 2                       # unequal brightness: non-trivial luminance deltas
-    car = None
-    if rng.integers(0, 2) and cw and ch:
-        car = np.zeros((bh, bw, 3), np.uint8)
-        t, l = (bh - ch) // 2, (bw - cw) // 2
-        car[t:t + ch, l:l + cw] = rng.integers(0, 256, (ch, cw, 3), dtype=np.uint8)
-    schedule = int(rng.choice([0, 0, 1]))
-    return dict(cfg=cfg, rig=rig, blend=blend, balance=balance, batch=batch, frames=frames, car=car, schedule=schedule)
-
-
 @pytest.mark.parametrize("seed", range(48))
 def test_random_rigs_modes_and_batches(ffi, SB, oracle, seed):
     """Seeded fuzz over the geometry: frame / BEV / car sizes (odd ones included, so every schedule and every alignment
@@ -790,11 +726,11 @@ def test_balance_slices_with_ring_buffers(ffi, parts, ring):
     from conftest import ROOT
     code = (
         "import numpy as np, sys\n"
-        "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+        "sys.path.insert(0, %r)\n"
         "from cameracalibration_amd import workloads as W\n"
         "from cameracalibration_amd.SurroundBirdEyeView import surroundBEV as SB\n"
         "from oracle import oracle as O\n"
-        "import test_gpu_parity as T\n"
+        "from tests import _harness as T\n"
         "rig = T.small_rig(); T.set_args(SB, T.SMALL_CFG)\n"
         "frames = W.synthetic_frames(40, T.SMALL_CFG['FRAME_WIDTH'], T.SMALL_CFG['FRAME_HEIGHT'], kind='random')\n"
         "car = np.random.default_rng(5).integers(0, 200, (T.SMALL_CFG['BEV_HEIGHT'], T.SMALL_CFG['BEV_WIDTH'], 3), dtype=np.uint8)\n"
@@ -804,7 +740,7 @@ def test_balance_slices_with_ring_buffers(ffi, parts, ring):
         "    got = bev.batch(frames, car if rnd else None)\n"
         "    assert bev.plan_info()['schedule'] == 2\n"
         "    assert all(np.array_equal(got[b], ref(*frames[b], car if rnd else None)) for b in range(40)), rnd\n"
-        "print('balance slices ok')\n") % (ROOT, os.path.join(ROOT, "tests"))
+        "print('balance slices ok')\n") % ROOT
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, BEVW_BAL_PARTS=str(parts), BEVW_BAL_RING=str(ring)), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "balance slices ok" in r.stdout, r.stdout + r.stderr
 

@@ -4,54 +4,23 @@ image) on the GPU: k_units_gray on the unit schedule, k_stitch_plan_gray for the
 The expected value is always oracle.remap on the 2-D array, compared with tolerance 0 over all pixels.  Pixels the map sends wholly outside
 the frame are asserted to be 0 on their own first.  Which kernels served a step is asked of the library (bevw_remapper_last_path) and
 asserted, so that no case passes through the fall-back unnoticed.  Run with `-m gpu` on an MI355X."""
-import ctypes as C
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from cameracalibration_amd import workloads as W
 from tests import _caller_maps as CM
 from tests import _gray_maps as GM
+from tests._harness import Remapper, assert_batch_gray as assert_batch, assert_same_gray as assert_same, ffi, outside_of, run_child  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHILD_TIMEOUT = 120   # seconds: a library load and one small remapper take a few seconds
 FOCAL_SCALE = 0.1     # the fisheye view zoomed out until its rim leaves the frame (at the benchmark's 0.5 every pixel samples inside)
-
-
-@pytest.fixture(scope="module")
-def ffi():
-    from cameracalibration_amd import _ffi
-
-    _ffi.require_device()
-    return _ffi
 
 
 def gray_frames(sw, sh, n, seed):
     """n frames of uniform random bytes."""
     return np.random.default_rng([seed, sw, sh]).integers(0, 256, (n, sh, sw), dtype=np.uint8)
-
-
-def outside_of(m1, sw, sh):
-    """Pixels whose whole 2 x 2 footprint lies outside the frame."""
-    return (m1[..., 0] < -1) | (m1[..., 0] >= sw) | (m1[..., 1] < -1) | (m1[..., 1] >= sh)
-
-
-def assert_same(got, want, outside, what):
-    assert got.shape == want.shape and got.dtype == np.uint8, what
-    assert not got[outside].any(), "%s: a pixel whose footprint lies outside the frame is not 0" % what
-    assert np.array_equal(got, want), "%s: %d of %d bytes differ (first at %s)" % (what, int((got != want).sum()), got.size,
-                                                                                   tuple(int(i) for i in np.argwhere(got != want)[0]))
-
-
-def assert_batch(got, want, outside, what):
-    assert got.shape == want.shape, what
-    for b in range(got.shape[0]):
-        assert_same(got[b], want[b], outside, "%s, image %d" % (what, b))
 
 
 def want_of(oracle, frames, m1, m2, variant=0):
@@ -61,47 +30,6 @@ def want_of(oracle, frames, m1, m2, variant=0):
         return np.stack([oracle.remap(f, m1, m2) for f in frames])
     finally:
         oracle.set_variant(oracle.VARIANT_REMAP, before)
-
-
-class Remapper:
-    """bevw_remapper_from_maps (+ bevw_remapper_set_channels) as a context: destroyed on the way out, whatever happened inside."""
-
-    def __init__(self, ffi, maps, size, channels=1):
-        self.ffi, self.L, self.size, self.r, self.channels = ffi, ffi.lib(), size, C.c_void_p(), channels
-        self.m1, self.m2 = maps
-
-    def __enter__(self):
-        sw, sh, dw, dh = self.size
-        self.ffi.check(self.L.bevw_remapper_from_maps(0, sw, sh, self.ffi.ptr(self.m1), self.ffi.ptr(self.m2), dw, dh, C.byref(self.r)))
-        try:
-            if self.channels != 3:
-                self.set_channels(self.channels)
-        except Exception:
-            self.L.bevw_remapper_destroy(self.r)
-            raise
-        return self
-
-    def __exit__(self, *exc):
-        self.L.bevw_remapper_destroy(self.r)
-        return False
-
-    def set_channels(self, n):
-        self.ffi.check(self.L.bevw_remapper_set_channels(self.r, n))
-        assert self.L.bevw_remapper_channels(self.r) == n
-        self.channels = n
-
-    def last_path(self):
-        return self.L.bevw_remapper_last_path(self.r)
-
-    def remap(self, frames):
-        dw, dh = self.size[2:]
-        got = np.full((frames.shape[0], dh, dw) + ((3,) if self.channels == 3 else ()), 0x5a, np.uint8)
-        self.ffi.check(self.L.bevw_remap(self.r, self.ffi.ptr(np.ascontiguousarray(frames)), frames.shape[0], self.ffi.ptr(got)))
-        return got
-
-    def remap_device(self, d_src, batch, d_dst):
-        self.ffi.check(self.L.bevw_remap_device(self.r, d_src, batch, d_dst))
-        self.ffi.check(self.L.bevw_remapper_sync(self.r))
 
 
 def replicate(frames):
@@ -173,7 +101,7 @@ def test_caller_maps(ffi, oracle, name, size):
     if name in OUTSIDE_FAMILIES:
         assert outside.any()
     want = want_of(oracle, frames, *maps)
-    with Remapper(ffi, maps, size) as g, Remapper(ffi, maps, size, channels=3) as c:
+    with Remapper(ffi, maps, size, channels=1) as g, Remapper(ffi, maps, size, channels=3) as c:
         got = g.remap(frames)
         gray_path = g.last_path()
         c.remap(replicate(frames))
@@ -213,7 +141,7 @@ def test_ragged_batch_19_on_exact_device_buffers(ffi, oracle, name):
     d_in, d_out = ffi.DeviceBuffer(19 * sw * sh).upload(frames), ffi.DeviceBuffer(19 * dw * dh)
     try:
         d_out.fill(0x5a)
-        with Remapper(ffi, maps, size) as g:
+        with Remapper(ffi, maps, size, channels=1) as g:
             g.remap_device(d_in.ptr, 19, d_out.ptr)
             path = g.last_path()
         print("%s: path %d" % (name, path))
@@ -242,7 +170,7 @@ def test_fall_back_triggers(ffi, oracle, trigger):
     try:
         d_in.upload(frames, offset=so)
         d_out.fill(0x5a)
-        with Remapper(ffi, maps, size) as g:
+        with Remapper(ffi, maps, size, channels=1) as g:
             if trigger != "dst_w_158":   # the same remapper on aligned pointers runs the units: the trigger is the pointer alone
                 d_al = ffi.DeviceBuffer(frames.nbytes).upload(frames)
                 try:
@@ -269,12 +197,7 @@ def test_plan_switched_off(ffi, oracle, tmp_path):
     assert outside_of(maps[0], sw, sh).any()
     case_file = str(tmp_path / "case.npz")
     np.savez(case_file, frames=frames, want=want_of(oracle, frames, *maps))
-    env = dict(os.environ, BEVW_REMAP_PLAN="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_gray_worker.py"), case_file], env=env, cwd=ROOT, capture_output=True,
-                       text=True, timeout=CHILD_TIMEOUT)
-    print(p.stdout)
-    assert p.returncode == 0, "worker exit %d\n%s\n%s" % (p.returncode, p.stdout[-4000:], p.stderr[-4000:])
-    assert "worker OK" in p.stdout
+    run_child("_gray_worker.py", [case_file], {"BEVW_REMAP_PLAN": "0"}, timeout=CHILD_TIMEOUT)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -284,7 +207,7 @@ def test_gray_equals_a_channel_of_the_bgr_remapper(ffi):
     size = CM.SMALL
     maps = CM.family("swirl", *size)
     frames = gray_frames(size[0], size[1], 4, 980)
-    with Remapper(ffi, maps, size) as g, Remapper(ffi, maps, size, channels=3) as c:
+    with Remapper(ffi, maps, size, channels=1) as g, Remapper(ffi, maps, size, channels=3) as c:
         got, bgr = g.remap(frames), c.remap(replicate(frames))
         assert g.last_path() == ffi.PATH_UNITS and c.last_path() == ffi.PATH_UNITS
     assert np.array_equal(got, bgr[..., 0]) and np.array_equal(bgr[..., 0], bgr[..., 1]) and np.array_equal(bgr[..., 0], bgr[..., 2])
@@ -365,7 +288,7 @@ def test_refusals(ffi):
         assert np.array_equal(r.remap(frames)[0], CM.numpy_remap(replicate(frames)[0], *maps)[..., 0])
     # an odd source size: the channel count is named before NV12's own size rule; an unknown format keeps its own message
     odd = (255, 191, 160, 120)
-    with Remapper(ffi, CM.family("transpose", *odd), odd) as r:
+    with Remapper(ffi, CM.family("transpose", *odd), odd, channels=1) as r:
         for fmt in (ffi.INPUT_NV12, ffi.INPUT_YUYV, ffi.INPUT_UYVY):
             refused(ffi, L.bevw_remapper_set_input_format(r.r, fmt))
         assert L.bevw_remapper_set_input_format(r.r, 2) == -1 and b"unknown input format" in L.bevw_last_error()

@@ -196,12 +196,12 @@ def test_the_route_of_a_one_channel_step(tmp_path):
 @pytest.fixture(scope="module")
 def units(tmp_path_factory):
     from cameracalibration_amd import build
-    from tests import test_translation_units as TU
+    from tests import _native_build as TU
 
     build.build()
     tmp = str(tmp_path_factory.mktemp("gray_units"))
     every = build.UNITS + build.FORMAT_UNITS + build.CHANNEL_UNITS
-    return {u: TU._kernels(os.path.join(build.OBJ, u.replace(".hip", ".o")), tmp) for u in every}, tmp, TU
+    return {u: TU.kernels_of(os.path.join(build.OBJ, u.replace(".hip", ".o")), tmp) for u in every}, tmp, TU
 
 
 @needs_hipcc

@@ -13,73 +13,11 @@ import pytest
 from cameracalibration_amd import workloads as W
 from tests import _nv12_out_spec as S
 from tests import _nv12_spec as SI
+from tests._harness import SAMPLED, SMALL_CFG, SB, assert_nv12, ffi, generator, random_car, raw_handle, small_rig, uncovered  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-# the small rig of the GPU parity tests: the repo rig scaled to 320 x 256 frames -> 248 x 250 BEV
-SMALL_CFG = dict(FRAME_WIDTH=320, FRAME_HEIGHT=256, BEV_WIDTH=248, BEV_HEIGHT=250, CAR_WIDTH=62, CAR_HEIGHT=100,
-                 FOCAL_SCALE=1.0, SIZE_SCALE=2.0)
 E_INVALID = -1
-
-
-def small_rig():
-    A = np.diag([0.25, 0.25, 1.0])
-    return {n: (A @ K, D.copy(), A @ H @ np.linalg.inv(A)) for n, (K, D, H) in W.repo_rig().items()}
-
-
-@pytest.fixture(scope="module")
-def ffi():
-    from cameracalibration_amd import _ffi
-
-    _ffi.require_device()
-    return _ffi
-
-
-@pytest.fixture(scope="module")
-def SB():
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV
-
-    return surroundBEV
-
-
-def generator(SB, rig, cfg, **kw):
-    ns = SB.BevGenerator.get_args()
-    for k, v in cfg.items():
-        setattr(ns, k, v)
-    return SB.BevGenerator(rig=rig, **kw)
-
-
-def uncovered(ref):
-    """BEV pixels whose masks are all zero: no camera contributes there."""
-    return np.all([np.asarray(m) == 0 for m in ref.masks], axis=0)
-
-
-def assert_nv12(got, want_bgr, none, what, black=True):
-    """got: NV12 [BH*3//2, BW]; want_bgr: the oracle's BGR image; none: pixels no camera covers (black there unless a car is given)."""
-    bh, bw = want_bgr.shape[:2]
-    want = S.bgr_to_nv12(want_bgr)
-    assert got.shape == want.shape == (bh * 3 // 2, bw), what
-    y, uv = S.planes(got)
-    wy, wuv = S.planes(want)
-    cnone = np.repeat(none[0::2, 0::2], 2, axis=1)   # U / V bytes of blocks whose top-left pixel no camera covers
-    bad_y, bad_uv = y[none] != wy[none], uv[cnone] != wuv[cnone]
-    assert not bad_y.any() and not bad_uv.any(), (
-        "%s: %d Y / %d U,V bytes of pixels no camera covers differ (got Y %s U,V %s, want Y %s U,V %s) -- zeros stored instead of NV12 black?"
-        % (what, int(bad_y.sum()), int(bad_uv.sum()), y[none][bad_y][:3].tolist(), uv[cnone][bad_uv][:4].tolist(), wy[none][bad_y][:3].tolist(),
-           wuv[cnone][bad_uv][:4].tolist()))
-    if black:
-        assert (y[none] == 16).all() and (uv[cnone] == 128).all(), what + ": NV12 black is (16, 128, 128)"
-    d = np.abs(got.astype(np.int16) - want.astype(np.int16))
-    assert int(d.max()) == 0, "%s: max |HIP - spec(oracle)| = %d over %d bytes (Y rows: %s)" % (
-        what, int(d.max()), int(np.count_nonzero(d)), sorted(set(np.nonzero(d)[0].tolist()))[:5])
-
-
-def random_car(rng, cfg):
-    car = np.zeros((cfg["BEV_HEIGHT"], cfg["BEV_WIDTH"], 3), np.uint8)
-    h, w = cfg["CAR_HEIGHT"], cfg["CAR_WIDTH"]
-    y0, x0 = (cfg["BEV_HEIGHT"] - h) // 2, (cfg["BEV_WIDTH"] - w) // 2
-    car[y0:y0 + h, x0:x0 + w] = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-    return car
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -123,9 +61,6 @@ def test_small_rig_matches_spec_of_oracle(ffi, SB, oracle, blend, balance, sched
 # ---------------------------------------------------------------------------------------------------------------
 # 2. BASELINE config 3 / config 4 geometry at batch 256 through run_device, all-random frames, pitched and dense; NV12 in -> NV12 out
 # ---------------------------------------------------------------------------------------------------------------
-SAMPLED = (0, 1, 15, 16, 17, 127, 128, 200, 254, 255)   # frame sets checked: chunk edges of 16-frame blocks, the ends
-
-
 @pytest.fixture(scope="module")
 def batches(ffi):
     cfg = W.CONFIG_S
@@ -269,13 +204,6 @@ def test_run_device_pitched_planes(ffi, SB, oracle):
 # ---------------------------------------------------------------------------------------------------------------
 # 6. refusals
 # ---------------------------------------------------------------------------------------------------------------
-def raw_handle(ffi, bw=248, bh=250):
-    cfg = ffi.bevw_config(320, 256, bw, bh, 62, 100, 1.0, 2.0, 0, 0, 0, 0)
-    h = C.c_void_p()
-    ffi.check(ffi.lib().bevw_create(C.byref(cfg), C.byref(h)))
-    return h
-
-
 def test_refusals(ffi, SB):
     L = ffi.lib()
     # analytic projection, in both orders
@@ -284,7 +212,7 @@ def test_refusals(ffi, SB):
     bev = generator(SB, small_rig(), SMALL_CFG, projection="analytic_f32")
     assert L.bevw_set_output_format(bev._engine.h, ffi.OUTPUT_NV12) == E_INVALID and b"analytic" in L.bevw_last_error()
     # camera-shard handles, in both orders; the combine step
-    h = raw_handle(ffi)
+    h = raw_handle(ffi, 320, 256, 248, 250)
     try:
         ffi.check(L.bevw_set_output_format(h, ffi.OUTPUT_NV12))
         assert L.bevw_output_format(h) == ffi.OUTPUT_NV12
@@ -311,7 +239,7 @@ def test_refusals(ffi, SB):
         d_img.free()
     # odd BEV sizes
     for bw, bh in ((247, 250), (248, 249)):
-        h = raw_handle(ffi, bw, bh)
+        h = raw_handle(ffi, 320, 256, bw, bh)
         try:
             assert L.bevw_set_output_format(h, ffi.OUTPUT_NV12) == E_INVALID and b"even" in L.bevw_last_error()
         finally:

@@ -19,6 +19,8 @@ from cameracalibration_amd import workloads as W
 from conftest import ROOT
 from oracle import oracle as O
 from tests import _nv12_out_spec as S
+from tests._harness import SMALL_CFG, small_rig
+from tests._native_build import mask2d as _mask2d
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 needs_hipcc = pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc not available")
@@ -105,19 +107,6 @@ def test_conversion_of_every_bgr_triple(native, tmp_path):
 # ---------------------------------------------------------------------------------------------------------------
 # the unit kernel's NV12 store stage over real plans
 # ---------------------------------------------------------------------------------------------------------------
-SMALL_CFG = dict(FRAME_WIDTH=320, FRAME_HEIGHT=256, BEV_WIDTH=248, BEV_HEIGHT=250, CAR_WIDTH=62, CAR_HEIGHT=100,
-                 FOCAL_SCALE=1.0, SIZE_SCALE=2.0)
-
-
-def small_rig():
-    A = np.diag([0.25, 0.25, 1.0])
-    return {n: (A @ K, D.copy(), A @ H @ np.linalg.inv(A)) for n, (K, D, H) in W.repo_rig().items()}
-
-
-def _mask2d(m):
-    return m[..., 0] if m.ndim == 3 else m
-
-
 def _emulate(exe, tmp_path, gen, frames, car, cfg, blend, pitch):
     fw, fh, bw, bh = cfg["FRAME_WIDTH"], cfg["FRAME_HEIGHT"], cfg["BEV_WIDTH"], cfg["BEV_HEIGHT"]
     inp, outp = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")

@@ -14,60 +14,12 @@ from cameracalibration_amd import workloads as W
 from tests import _nv12_out_spec as SO
 from tests import _nv12_spec as S
 from tests import _nv12_surfaces as SF
-from tests import test_nv12_gpu as TI
-from tests import test_nv12_out_gpu as TO
+from tests._harness import (SAMPLED, SMALL_CFG, SB, assert_same, check_image, fetch, ffi, generator, random_car, raw_handle, run_table,  # noqa: F401
+                            small_rig, uncovered)
 
 pytestmark = pytest.mark.gpu
 
-SMALL_CFG = TI.SMALL_CFG
-small_rig, generator, uncovered, assert_same, random_car = TI.small_rig, TI.generator, TI.uncovered, TI.assert_same, TI.random_car
-assert_nv12 = TO.assert_nv12
 E_INVALID = -1
-
-
-@pytest.fixture(scope="module")
-def ffi():
-    from cameracalibration_amd import _ffi
-
-    _ffi.require_device()
-    return _ffi
-
-
-@pytest.fixture(scope="module")
-def SB():
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV
-
-    return surroundBEV
-
-
-def fetch(ffi, bev, d_out, cfg, b):
-    """Image b of a device buffer of the generator's images -> dense host array: BGR [BH, BW, 3] or NV12 [BH * 3 // 2, BW]."""
-    bh, bw = cfg["BEV_HEIGHT"], cfg["BEV_WIDTH"]
-    if bev.output_format == "nv12":
-        return d_out.download((bh * 3 // 2, bev.out_pitch), offset=b * bev.out_image_bytes)[:, :bw]
-    return d_out.download((bh, bev.out_pitch, 3), offset=b * bev.out_image_bytes)[:, :bw]
-
-
-def check_image(bev, got, want_bgr, none, what, car):
-    if bev.output_format == "nv12":
-        assert_nv12(got, want_bgr, none, what, black=car is None)
-    else:
-        assert_same(got, want_bgr, none, what)
-
-
-def run_table(ffi, bev, table, car, cfg):
-    """run_surfaces on a host table [B, 4, 2]; returns the device output buffer (caller frees) after the step finished."""
-    B = table.shape[0]
-    d_out = ffi.DeviceBuffer(B * bev.out_image_bytes)
-    d_out.fill(0x5a)
-    d_car = ffi.DeviceBuffer(car.nbytes).upload(car) if car is not None else None
-    try:
-        bev.run_surfaces(table, d_car.ptr if d_car else None, d_out.ptr, out_bytes=d_out.nbytes)
-        bev.sync()
-    finally:
-        if d_car:
-            d_car.free()
-    return d_out
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -102,7 +54,7 @@ def test_small_rig_matches_oracle_and_packed_handle(ffi, SB, oracle, blend, bala
             packed = generator(SB, small_rig(), cfg, **kw).batch(nv, car)   # the packed handle on the same frames: an additional assertion
             for b in range(3):
                 got = fetch(ffi, bev, d_out, cfg, b)
-                check_image(bev, got, ref(*S.nv12_to_bgr(nv[b]), car), none, "set %d" % b, car)
+                check_image(got, ref(*S.nv12_to_bgr(nv[b]), car), none, "set %d" % b, bev.output_format, car=car)
                 assert np.array_equal(got, packed[b]), "set %d differs from the packed handle" % b
         finally:
             d_out.free()
@@ -203,7 +155,6 @@ def test_ring_reuse(ffi, SB, oracle):
 # ---------------------------------------------------------------------------------------------------------------
 # 4. BASELINE config 3 / config 4 geometry, batch 256, device-resident table, four per-camera regions
 # ---------------------------------------------------------------------------------------------------------------
-SAMPLED = TI.SAMPLED
 POOL = 12   # surfaces per camera: the 256 x 4 table draws from 48 surfaces through a permutation (keeps the upload at ~100 MB per pitch)
 
 
@@ -389,7 +340,7 @@ def test_refusals(ffi, SB):
     # analytic projection and camera shards, in both orders where an order exists
     with pytest.raises(ffi.BevwError, match="analytic"):
         generator(SB, small_rig(), cfg, projection="analytic", input_format="nv12", input_pitch=512)
-    hh = TI.raw_handle(ffi)
+    hh = raw_handle(ffi, 320, 256, 248, 250)
     try:
         assert L.bevw_set_input_pitch(hh, 512) == E_INVALID and b"NV12" in err()        # BGR still
         ffi.check(L.bevw_set_input_format(hh, ffi.INPUT_NV12))

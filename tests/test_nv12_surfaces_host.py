@@ -21,18 +21,10 @@ from cameracalibration_amd import workloads as W
 from conftest import ROOT
 from oracle import oracle as O
 from tests import _nv12_surfaces as SF
+from tests._harness import SMALL_CFG, small_rig
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 needs_hipcc = pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc not available")
-
-SMALL_CFG = dict(FRAME_WIDTH=320, FRAME_HEIGHT=256, BEV_WIDTH=248, BEV_HEIGHT=250, CAR_WIDTH=62, CAR_HEIGHT=100,
-                 FOCAL_SCALE=1.0, SIZE_SCALE=2.0)
-
-
-def small_rig():
-    A = np.diag([0.25, 0.25, 1.0])
-    return {n: (A @ K, D.copy(), A @ H @ np.linalg.inv(A)) for n, (K, D, H) in W.repo_rig().items()}
-
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
@@ -168,11 +160,11 @@ def test_surface_kernels_have_names_of_their_own(tmp_path):
     """k_units_surf / k_units_out_surf live in the plan's translation unit beside the four k_plan_units instantiations, and the surface
     instantiations of the per-pixel, remap and V-sum kernels in the library's main unit."""
     from cameracalibration_amd import build
-    from tests import test_translation_units as TU
+    from tests import _native_build as TU
 
     build.build()
-    plan = TU._kernels(os.path.join(build.OBJ, "bevwarp_plan.o"), str(tmp_path))
-    main = TU._kernels(os.path.join(build.OBJ, "bevwarp.o"), str(tmp_path))
+    plan = TU.kernels_of(os.path.join(build.OBJ, "bevwarp_plan.o"), str(tmp_path))
+    main = TU.kernels_of(os.path.join(build.OBJ, "bevwarp.o"), str(tmp_path))
     assert len({k for k in plan if "k_units_surf" in k}) == 2 and len({k for k in plan if "k_units_out_surf" in k}) == 2
     assert len({k for k in plan if "k_plan_units" in k}) == 4
     assert not {k for k in main if "k_units" in k}
@@ -187,10 +179,10 @@ def test_surface_table_is_read_with_scalar_loads(tmp_path):
     load whose s_waitcnt vmcnt(0) would drain the group loads in flight: the surface kernels hold more scalar 16-byte loads than their
     packed twin and not one more vector global load or v_readfirstlane."""
     from cameracalibration_amd import build
-    from tests import test_translation_units as TU
+    from tests import _native_build as TU
 
     build.build()
-    TU._kernels(os.path.join(build.OBJ, "bevwarp_plan.o"), str(tmp_path))
+    TU.kernels_of(os.path.join(build.OBJ, "bevwarp_plan.o"), str(tmp_path))
     dis = subprocess.run([os.path.join(TU.LLVM_BIN, "llvm-objdump"), "-d", "--no-show-raw-insn", str(tmp_path / "bevwarp_plan.o.co")],
                          check=True, capture_output=True, text=True, timeout=600).stdout
     count = {}

@@ -18,34 +18,18 @@ Run with `-m gpu` on an MI355X."""
 import numpy as np
 import pytest
 
-import _analytic_common as AC
-import _rigs as R
-from test_analytic_gpu import check_batch
-from test_gpu_parity import set_args
+from tests import _analytic_common as AC
+from tests import _harness as H
 from tests import _nv12_spec as SN
+from tests import _rigs as R
 from tests import _yuv422_spec as SY
-from tests.test_nv12_gpu import assert_same, uncovered
-from tests.test_nv12_out_gpu import assert_nv12
+from tests._analytic_common import check_batch
+from tests._harness import SB, assert_nv12, assert_same, ffi, uncovered  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 BATCH = 3
 MODES = {"direct": (False, False), "blend": (True, False), "balance": (False, True), "blend_balance": (True, True)}
-
-
-@pytest.fixture(scope="module")
-def ffi():
-    from cameracalibration_amd import _ffi
-
-    _ffi.require_device()
-    return _ffi
-
-
-@pytest.fixture(scope="module")
-def SB():
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV
-
-    return surroundBEV
 
 
 _frames, _wants = {}, {}
@@ -72,9 +56,7 @@ def expected(name, blend, balance):
 
 
 def generator(SB, name, **kw):
-    rig, cfg = R.family(name)
-    set_args(SB, cfg)
-    return SB.BevGenerator(rig=rig, **kw)
+    return H.generator(SB, *R.family(name), **kw)
 
 
 # ---------------------------------------------------------------------------------------------------------------

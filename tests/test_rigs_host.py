@@ -14,10 +14,11 @@ import os
 import numpy as np
 import pytest
 
-import _rigs as R
+from tests import _rigs as R
 from oracle import np_twin, oracle as O
 from tests import _native_build
-from tests.test_unit_schedule import _mask2d, _run
+from tests._analytic_common import psnr
+from tests._native_build import mask2d as _mask2d, run_units as _run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 needs_hipcc = pytest.mark.skipif(not _native_build.hipcc_path(), reason="hipcc not available")
@@ -148,7 +149,6 @@ def test_analytic_specification_shows_the_same_picture_as_the_table_path(repo_ri
     frames' gradient per pixel: the frames are the centre 320 x 256 of the reference's own frames, which keeps the texture per pixel of the
     frames the bar was set on (reduced 4 x 4 instead, every edge is four times as steep and the small rig itself gives 37.5 dB)."""
     from oracle import np_analytic
-    from test_analytic import psnr
 
     O.build()
     rig, cfg = (R.small_rig(), dict(R.SMALL_CFG)) if name == "small" else R.family(name)

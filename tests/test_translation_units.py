@@ -3,26 +3,10 @@ declarations of bevw_planapi.h, and bevwarp_plan.hip does not include bevw_kerne
 unit's kernels, and no templated kernel is registered from two code objects under one host stub.  Checked on the gfx950 code object of
 each unit's object file (no GPU needed)."""
 import os
-import re
-import subprocess
 
 import pytest
 
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-LLVM_BIN = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))), "llvm", "bin")
-TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-
-
-def _kernels(obj: str, tmp: str) -> set:
-    """Names of the kernels (their kernel descriptors, `<name>.kd`) in the gfx950 code object of a unit's object file."""
-    stem = os.path.join(tmp, os.path.basename(obj))
-    subprocess.run([os.path.join(LLVM_BIN, "llvm-objcopy"), "--dump-section=.hip_fatbin=" + stem + ".fatbin", obj, stem + ".host"],
-                   check=True, capture_output=True, timeout=120)
-    subprocess.run([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o", "--targets=" + TARGET,
-                    "--input=" + stem + ".fatbin", "--output=" + stem + ".co"], check=True, capture_output=True, timeout=120)
-    syms = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "-s", stem + ".co"], check=True, capture_output=True, text=True,
-                          timeout=120).stdout
-    return set(re.findall(r"\s(\S+)\.kd$", syms, flags=re.M))
+from tests._native_build import kernels_of
 
 
 @pytest.fixture(scope="module")
@@ -31,7 +15,7 @@ def kernels(tmp_path_factory):
 
     build.build()
     tmp = str(tmp_path_factory.mktemp("units"))
-    return {u: _kernels(os.path.join(build.OBJ, u.replace(".hip", ".o")), tmp) for u in build.UNITS}
+    return {u: kernels_of(os.path.join(build.OBJ, u.replace(".hip", ".o")), tmp) for u in build.UNITS}
 
 
 def test_no_kernel_in_two_units(kernels):

@@ -10,7 +10,6 @@ stored pixel with cv2.remap's fixed-point formula evaluated from the LUT.  Here 
     section 4 quotes."""
 import os
 import shutil
-import struct
 import subprocess
 
 import numpy as np
@@ -18,6 +17,7 @@ import pytest
 
 from cameracalibration_amd import workloads as W
 from oracle import oracle as O
+from tests._native_build import mask2d as _mask2d, run_units as _run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -59,34 +59,6 @@ def test_units_with_the_16_byte_store_format(tmp_path, pitch):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
-def _run(exe, tmp_path, luts, masks, frames, car, fw, fh, bw, bh, blend=False, fracs=None, env=None):
-    """luts: [(int16 [bh,bw,2], uint16 [bh,bw])], masks: [uint8 [bh,bw]], frames: uint8 [n, ncams, fh, fw, 3];
-    fracs: [uint32 [bh,bw,2]] 21-bit fractions -> a wide plan (the analytic projection mode); env: the emulator's environment"""
-    inp, outp = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
-    with open(inp, "wb") as f:
-        f.write(struct.pack("<8i", fw, fh, bw, bh, len(luts), frames.shape[0], int(car is not None), int(blend) | (2 if fracs is not None else 0)))
-        for i, ((m1, m2), mk) in enumerate(zip(luts, masks)):
-            f.write(np.ascontiguousarray(m1, np.int16).tobytes())
-            f.write(np.ascontiguousarray(m2, np.uint16).tobytes())
-            f.write(np.ascontiguousarray(mk, np.uint8).tobytes())
-            if fracs is not None:
-                f.write(np.ascontiguousarray(fracs[i], np.uint32).tobytes())
-        f.write(np.ascontiguousarray(frames, np.uint8).tobytes())
-        if car is not None:
-            f.write(np.ascontiguousarray(car, np.uint8).tobytes())
-    r = subprocess.run([exe, inp, outp], capture_output=True, text=True, timeout=900, env=env)
-    assert r.returncode == 0, r.stdout + r.stderr
-    raw = open(outp, "rb").read()
-    nunits, claimed, lines, sectors = struct.unpack("<4i", raw[:16])
-    written = np.frombuffer(raw, np.uint8, bw * bh, 16).reshape(bh, bw)
-    img = np.frombuffer(raw, np.uint8, frames.shape[0] * bh * bw * 3, 16 + bw * bh).reshape(frames.shape[0], bh, bw, 3)
-    return dict(units=nunits, claimed=claimed, lines=lines, sectors=sectors, written=written, img=img, log=r.stdout)
-
-
-def _mask2d(m):
-    return m[..., 0] if m.ndim == 3 else m
-
-
 @pytest.mark.parametrize("name,cfg,rig,blend,max_requests", [
     # requests per frame = distinct source lines + write sectors of the partition; every base tile of config 3 is a unit tile; round 2 paid ~136 k
     ("config3_direct", W.CONFIG_S, W.rig_s, False, 112_000),
@@ -126,7 +98,7 @@ def test_small_rig_holds_both_kinds_of_frame_loop(exe, tmp_path, blend, pitch):
     device layouts the batch tests run.)"""
     import re
 
-    from tests.test_nv12_gpu import SMALL_CFG as cfg, random_car, small_rig
+    from tests._harness import SMALL_CFG as cfg, random_car, small_rig
 
     O.build()
     gen = O.RefBevGenerator(small_rig(), cfg, blend=blend, balance=False)

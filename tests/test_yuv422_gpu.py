@@ -17,26 +17,10 @@ import pytest
 from cameracalibration_amd import workloads as W
 from tests import _nv12_out_spec as SO
 from tests import _yuv422_spec as S
-from tests.test_nv12_gpu import SMALL_CFG, assert_same, generator, random_car, raw_handle, small_rig, uncovered
-from tests.test_nv12_out_gpu import assert_nv12
+from tests._harness import SMALL_CFG, SB, assert_nv12, assert_same, check_image, ffi, generator, random_car, raw_handle, small_rig, uncovered  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 E_INVALID = -1
-
-
-@pytest.fixture(scope="module")
-def ffi():
-    from cameracalibration_amd import _ffi
-
-    _ffi.require_device()
-    return _ffi
-
-
-@pytest.fixture(scope="module")
-def SB():
-    from cameracalibration_amd.SurroundBirdEyeView import surroundBEV
-
-    return surroundBEV
 
 
 @pytest.fixture(scope="module")
@@ -55,13 +39,6 @@ def refs(oracle):
         return made[key]
 
     return get
-
-
-def check_image(got, want_bgr, none, what, out, black):
-    if out == "nv12":
-        assert_nv12(got, want_bgr, none, what, black=black)
-    else:
-        assert_same(got, want_bgr, none, what)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -237,7 +214,7 @@ def test_refusals(ffi, SB, order):
     bev = generator(SB, small_rig(), SMALL_CFG, projection="analytic_f32")
     assert L.bevw_set_input_format(bev._engine.h, fmt) == E_INVALID and b"analytic" in L.bevw_last_error()
     # camera-shard handles, in both orders; the values that are no formats; the round trip
-    h = raw_handle(ffi)
+    h = raw_handle(ffi, 320, 256, 248, 250)
     try:
         ffi.check(L.bevw_set_input_format(h, fmt))
         assert L.bevw_input_format(h) == fmt
@@ -255,12 +232,12 @@ def test_refusals(ffi, SB, order):
     finally:
         L.bevw_destroy(h)
     # an odd frame width is refused, an odd height is not
-    h = raw_handle(ffi, 321, 256)
+    h = raw_handle(ffi, 321, 256, 248, 250)
     try:
         assert L.bevw_set_input_format(h, fmt) == E_INVALID and b"even" in L.bevw_last_error()
     finally:
         L.bevw_destroy(h)
-    h = raw_handle(ffi, 320, 257)
+    h = raw_handle(ffi, 320, 257, 248, 250)
     try:
         ffi.check(L.bevw_set_input_format(h, fmt))
     finally:

@@ -116,12 +116,12 @@ YUV422_FAMILIES = {"k_units_yuv422": 2, "k_units_out_yuv422": 2, "k_stitch_plan_
 @pytest.fixture(scope="module")
 def units(tmp_path_factory):
     from cameracalibration_amd import build
-    from tests import test_translation_units as TU
+    from tests import _native_build as TU
 
     build.build()
     tmp = str(tmp_path_factory.mktemp("yuv422_units"))
     assert build.FORMAT_UNITS == ["bevwarp_yuv422.hip"] and not set(build.FORMAT_UNITS) & set(build.UNITS)
-    kernels = {u: TU._kernels(os.path.join(build.OBJ, u.replace(".hip", ".o")), tmp) for u in build.UNITS + build.FORMAT_UNITS}
+    kernels = {u: TU.kernels_of(os.path.join(build.OBJ, u.replace(".hip", ".o")), tmp) for u in build.UNITS + build.FORMAT_UNITS}
     return kernels, tmp, TU
 
 
