@@ -875,6 +875,7 @@ int bevw_warp_perspective_u8c3(int device, const uint8_t *src, int src_w, int sr
     if (!src || !dst || !H || src_w <= 0 || src_h <= 0 || dst_w <= 0 || dst_h <= 0 || batch < 0)
         return fail(BEVW_E_INVALID, "bad argument");
     if (batch == 0) return BEVW_OK;
+    if (dst_h > 65535) return fail(BEVW_E_INVALID, "destination height > 65535");   // grid.y
     BEVW_TRY(use_device(device));
     Mat3 Minv;
     invert3x3(H, Minv.m);
@@ -900,7 +901,7 @@ int bevw_translate_u8c3(int device, const uint8_t *src, int width, int height, i
 {
     if (!src || !dst || width <= 0 || height <= 0 || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
     if (batch == 0) return BEVW_OK;
-    if (batch > 65535) return fail(BEVW_E_INVALID, "batch > 65535");
+    if (batch > 65535 || height > 65535) return fail(BEVW_E_INVALID, "batch or height > 65535");   // grid.z, grid.y
     BEVW_TRY(use_device(device));
     const size_t n = (size_t)batch * width * height * 3;
     DevBuf d_src, d_dst;

@@ -398,12 +398,14 @@ int bevw_remapper_timer_between(bevw_remapper *r, int slot_a, int slot_b, float 
 void bevw_remapper_destroy(bevw_remapper *r);
 
 /* ---- cv2.warpPerspective(src_8UC3, H, (dst_w, dst_h)): ExCalibrator.warp (extrinsicCalib.py:166-169) ------ */
+/* Refused with BEVW_E_INVALID before any device work: dst_h > 65535. */
 int bevw_warp_perspective_u8c3(int device, const uint8_t *src, int src_w, int src_h, const double H[9], int dst_w,
                                int dst_h, int batch, uint8_t *dst);
 
 /* ---- ExCalibrator pre-processing warps --------------------------------------------------------------------- */
 /* CenterImage.translate (extrinsicCalib.py:54-59): cv2.warpAffine(img, [[1,0,shift_x],[0,1,shift_y]], (w, h)) with the
- * integer shifts the reference builds (image centre minus the picked point): dst(x,y) = src(x-shift_x, y-shift_y) or 0. */
+ * integer shifts the reference builds (image centre minus the picked point): dst(x,y) = src(x-shift_x, y-shift_y) or 0.
+ * Refused with BEVW_E_INVALID before any device work: height or batch > 65535 (as bevw_resize_linear_u8c3 refuses a destination height). */
 int bevw_translate_u8c3(int device, const uint8_t *src, int width, int height, int shift_x, int shift_y, int batch,
                         uint8_t *dst);
 /* cv2.resize(img, (0,0), fx=fx, fy=fy), INTER_LINEAR, 8UC3 (ScaleImage.__call__, extrinsicCalib.py:125).
