@@ -63,7 +63,9 @@ class HipShardEngine:
         _ffi.require_device()
         self.cams = tuple(int(c) for c in cams)
         self.device = int(device)
-        self.cfg = _sb._snapshot_config(blend, balance, device, _ffi.SCHED_TILE_PLAN)
+        # AUTO: the tile plan wherever the owned cameras allow it; a shard with more than two of its cameras on some pixel (a BEV without
+        # a car) stitches per pixel, as the full generator does there
+        self.cfg = _sb._snapshot_config(blend, balance, device, _ffi.SCHED_AUTO)
         self.blend, self.balance = bool(blend), bool(balance)
         h = C.c_void_p()
         check(lib().bevw_create(C.byref(self.cfg), C.byref(h)))
@@ -124,6 +126,12 @@ class HipShardEngine:
 
     def sync(self):
         check(lib().bevw_sync(self.h))
+
+    def schedule(self) -> int:
+        """_ffi.SCHED_TILE_PLAN or _ffi.SCHED_PER_PIXEL: what bevw_shard_run_device runs on this handle"""
+        info = np.zeros(8, np.int32)
+        check(lib().bevw_plan_info(self.h, ptr(info)))
+        return int(info[2])
 
     # ---- host-array calls ---------------------------------------------------------------------------------------
     def _upload_frames(self, frames):

@@ -971,6 +971,40 @@ static __global__ void k_delta_select(const int *__restrict__ deltas, ShardCams 
     out[i] = k < sc.n ? deltas[b * 4 + sc.cam[k]] : 0;
 }
 
+// A shard whose own cameras put more than two contributors on one pixel (a BEV without a car: the masks meet in the centre) has no tile
+// plan, as the full generator has none there.  One thread per pixel over the owned cameras, the arithmetic of k_stitch_pp: frame sets of
+// `ncams` BGR frames, deltas[b][k] of k_delta_select, no car and no channel sums (the stitch rank adds the car and balances the colours).
+// grid = (ceil(bw / 256), bh, batch)
+template <bool BLEND, bool BAL>
+static __global__ void k_shard_pp(const uint8_t *__restrict__ frames, int fw, int fh, StitchTables T, int ncams, int bw, int bh,
+                                  const int *__restrict__ deltas, const HsvTables *__restrict__ tab, uint8_t *__restrict__ out)
+{
+    __shared__ HsvTables hsv;
+    if (BAL) {
+        hsv_tables_to_lds(hsv, tab);
+        __syncthreads();
+    }
+    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= bw) return;
+    const size_t b = blockIdx.z, o = (size_t)y * bw + x, frame_bytes = (size_t)fw * fh * 3;
+    int acc[3] = {0, 0, 0};
+#pragma unroll 1
+    for (int c = 0; c < ncams; ++c) {
+        const int m = T.mask[c][o];
+        if (m == 0) continue;
+        int v[3];
+        remap_u8c3_px<BAL>(frames + (b * ncams + c) * frame_bytes, fw, fh, T.lut1[c][o * 2], T.lut1[c][o * 2 + 1], T.lut2[c][o] & (kQTab2 - 1), v,
+                           BAL ? deltas[b * 4 + c] : 0, &hsv);
+        if (BLEND) {
+            const float wgt = blend_weight_f32(m);
+            v[0] = blend_mul(v[0], wgt); v[1] = blend_mul(v[1], wgt); v[2] = blend_mul(v[2], wgt);
+        }
+        acc[0] = min(255, acc[0] + v[0]); acc[1] = min(255, acc[1] + v[1]); acc[2] = min(255, acc[2] + v[2]);
+    }
+    uint8_t *d = out + (b * bw * bh + o) * 3;
+    d[0] = (uint8_t)acc[0]; d[1] = (uint8_t)acc[1]; d[2] = (uint8_t)acc[2];
+}
+
 // full BEV [batch][bh][bw][3] -> packed box [batch][y1-y0][x1-x0][3].  U = uint32_t when every row start is dword
 // aligned (bw % 4 == 0 and x0 % 4 == 0), else uint8_t.  grid = (ceil(row units / 256), box rows, batch)
 template <typename U>

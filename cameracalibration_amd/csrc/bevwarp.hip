@@ -1499,7 +1499,7 @@ int bevw_build(bevw_handle *h)
     BEVW_TRY(plan_build(h->plan, st, T, cfg.frame_width, cfg.frame_height, bw, bh, ncams, h->pitch_px != bw ? h->pitch_px : 0, cfg.blend != 0));
     BEVW_TRY(h->apply_format());   // (with them the group lists of NV12 surfaces: bevw_run_surfaces_device)
     if (h->shard_n) {
-        if (!h->plan.usable) return fail(BEVW_E_INVALID, "camera shard needs the tile plan: %d contributors on some pixel", h->plan.max_contrib);
+        // (a shard without a usable tile plan -- more than two of its own cameras on some pixel -- stitches per pixel: shard_per_pixel)
         // bounding box of the owned masks, widened to multiples of 4 pixels in x so that packed rows stay dword aligned
         std::vector<uint8_t> m(bpx);
         int x0 = bw, y0 = bh, x1 = 0, y1 = 0;
@@ -1861,6 +1861,22 @@ int bevw_set_camera_shard(bevw_handle *h, const int32_t *cams, int ncams)
     return BEVW_OK;
 }
 
+// bevw_shard_run_device of a shard that has no tile plan (k_shard_pp); deltas: [batch][4] of k_delta_select with balance, else null
+static int shard_per_pixel(bevw_handle *h, const uint8_t *d_frames, int batch, const int *deltas, uint8_t *d_out)
+{
+    const bevw_config &c = h->cfg;
+    const StitchTables T = stitch_tables(h);
+    const size_t set_bytes = (size_t)c.frame_width * c.frame_height * 3 * h->shard_n, image_bytes = (size_t)c.bev_width * c.bev_height * 3;
+    for_each_chunk(batch, [&](int b0, int nb) {
+        with_flags([&](auto bl, auto ba) {
+            hipLaunchKernelGGL((k_shard_pp<bl, ba>), dim3((c.bev_width + 255) / 256, c.bev_height, nb), dim3(256), 0, h->stream, d_frames + b0 * set_bytes,
+                               c.frame_width, c.frame_height, T, h->shard_n, c.bev_width, c.bev_height, deltas ? deltas + b0 * 4 : nullptr,
+                               h->hsv.as<HsvTables>(), d_out + b0 * image_bytes);
+        }, c.blend != 0, deltas != nullptr);
+    });
+    return launch_check("k_shard_pp");
+}
+
 static int need_shard(bevw_handle *h)
 {
     BEVW_TRY(need_built(h));
@@ -1898,7 +1914,8 @@ int bevw_shard_run_device(bevw_handle *h, const void *d_frames, int batch, const
     if (batch == 0) return BEVW_OK;
     PlanStep step;
     step.src = h->source((const uint8_t *)d_frames, nullptr); step.batch = batch; step.blend = c.blend != 0; step.out = (uint8_t *)d_out;
-    if (!c.balance) return plan_stitch(h->plan, h->stream, step);
+    const bool per_pixel = h->schedule_in_use != BEVW_SCHED_TILE_PLAN;
+    if (!c.balance) return per_pixel ? shard_per_pixel(h, (const uint8_t *)d_frames, batch, nullptr, step.out) : plan_stitch(h->plan, h->stream, step);
     // luminance_balance (surroundBEV.py:57-79) with the means of ALL four cameras, applied to the owned ones
     BEVW_TRY(ensure_stats(h, batch));
     BEVW_TRY(h->sdeltas.reserve(sizeof(int) * 4 * (size_t)batch));
@@ -1911,6 +1928,7 @@ int bevw_shard_run_device(bevw_handle *h, const void *d_frames, int batch, const
                        h->sdeltas.as<int>());
     BEVW_TRY(launch_check("k_lum_delta/k_delta_select"));
     step.deltas = h->sdeltas.as<int>(); step.tab = h->hsv.as<HsvTables>();
+    if (per_pixel) return shard_per_pixel(h, (const uint8_t *)d_frames, batch, step.deltas, step.out);
     if (bal_mode() == 1 && h->plan.compact_stride != 0) {
         BEVW_TRY(h->tmp.reserve(h->plan.compact_stride * (size_t)batch));
         BEVW_TRY(plan_lum_groups(h->plan, h->stream, step.src, h->tmp.as<uint8_t>(), batch, step.deltas, step.tab));

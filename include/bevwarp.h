@@ -288,7 +288,9 @@ int bevw_shard_box(bevw_handle *h, int32_t box[4]);
 int bevw_shard_vsums_device(bevw_handle *h, const void *d_frames, int batch, void *d_vsums);
 /* Partial BevGenerator.__call__ (surroundBEV.py:312-320): luminance shift with the global means (balance = 1,
  * d_all_vsums[batch][4] uint64, else NULL), raw2bev, mask / blend weight and cv2.add over the owned cameras.
- * d_out: full-size [batch][BH][BW][3], zero outside the owned masks.  No white balance, no car: bevw_combine_device. */
+ * d_out: full-size [batch][BH][BW][3], zero outside the owned masks.  No white balance, no car: bevw_combine_device.
+ * Runs the tile plan; a shard without one (schedule BEVW_SCHED_AUTO and more than two of its own cameras on some pixel, or
+ * BEVW_SCHED_PER_PIXEL) stitches one thread per pixel, as a full handle does.  BEVW_SCHED_TILE_PLAN refuses such a build. */
 int bevw_shard_run_device(bevw_handle *h, const void *d_frames, int batch, const void *d_all_vsums, void *d_out);
 /* d_full [batch][BH][BW][3] -> d_packed [batch][y1-y0][x1-x0][3] (the bevw_shard_box window). */
 int bevw_shard_pack_device(bevw_handle *h, const void *d_full, int batch, void *d_packed);

@@ -33,6 +33,16 @@ def frames(batch=2, seed=77, cfg=None):
     return f
 
 
+def content(cfg=None):
+    """Three frame sets of one batch: the random set of frames(), an all-255 set and an all-0 set (with car(): the car alone)."""
+    f = np.repeat(frames(batch=1, cfg=cfg), 3, axis=0)
+    f[1], f[2] = 255, 0
+    return f
+
+
+CONTENT = ("random", "white", "black")   # the frame sets of content(), by position
+
+
 def car(cfg=None):
     c = cfg or CFG
     rng = np.random.default_rng(5)
