@@ -667,6 +667,11 @@ class BevGenerator:
         self._check_out_bytes(batch, out_bytes)
         check(lib().bevw_run_surface_table_device(self._engine.h, d_table, int(batch), d_car, d_out))
 
+    def last_path(self) -> int:
+        """Which kernels served the last step: _ffi.PATH_NONE / PATH_UNITS (the tile plan) / PATH_PER_PIXEL (bevw_last_path).  A step with
+        d_frames, d_car or d_out off a 4-byte boundary runs per pixel on a dense generator and is refused by a pitched one."""
+        return int(lib().bevw_last_path(self._engine.h))
+
     def sync(self) -> None:
         check(lib().bevw_sync(self._engine.h))
 

@@ -41,7 +41,7 @@ def frame_shape(name, height: int, width: int):
     if name == 'nv12':
         return (height * 3 // 2, width)
     return (height, width, 2 if name in ('yuyv', 'uyvy') else 3)
-PATH_NONE, PATH_UNITS, PATH_PER_PIXEL = 0, 1, 2      # bevw_remapper_last_path
+PATH_NONE, PATH_UNITS, PATH_PER_PIXEL = 0, 1, 2      # bevw_last_path, bevw_remapper_last_path
 OUTPUT_BGR, OUTPUT_NV12 = 0, 1                       # bevw_set_output_format, bevw_remapper_set_output_format
 COMPAT_FILLPOLY, COMPAT_ADDWEIGHTED, COMPAT_WARP, COMPAT_REMAP = 0, 1, 2, 3   # bevw_set_compat keys (include/bevwarp.h)
 
@@ -84,6 +84,7 @@ SIGNATURES = {
     "bevw_set_projection": (_i, [_vp, _i]),
     "bevw_run": (_i, [_vp, _vp, _i, _vp, _vp]),
     "bevw_run_device": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "bevw_last_path": (_i, [_vp]),
     "bevw_set_output_pitch": (_i, [_vp, _i]),
     "bevw_output_pitch": (_i, [_vp]),
     "bevw_set_input_format": (_i, [_vp, _i]),

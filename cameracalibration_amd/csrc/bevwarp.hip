@@ -964,6 +964,7 @@ struct bevw_handle : EngineCore {
     DevBuf pre;           // balance: the pre-gain BEV (the gain pass runs out of place)
     int schedule_in_use = BEVW_SCHED_PER_PIXEL;
     int projection = BEVW_PROJ_LUT;   // bevw_set_projection
+    int last_path = BEVW_PATH_NONE;   // which kernels served the last step (bevw_last_path)
     size_t set_bytes() const { return frame_bytes_of(cfg.frame_width, cfg.frame_height, fmt()) * 4; }   // one camera frame set as the handle reads it
     int compat[BEVW_COMPAT_KEYS] = {1, 1, 0, 0};   // bevw_set_compat values at bevw_build: a handle keeps the arithmetic it was built with
     int pitch_request = BEVW_PITCH_DENSE;   // bevw_set_output_pitch
@@ -1099,9 +1100,11 @@ static int stitch_analytic(bevw_handle *h, const uint8_t *d_frames, int batch, c
     const bevw_config &c = h->cfg;
     const uint32_t *left_tiles = nullptr;
     int n_left = 0;
+    h->last_path = BEVW_PATH_PER_PIXEL;   // the full-grid kernel, unless the wide unit plan takes the step
     if (!c.balance && ((((uintptr_t)d_out | (uintptr_t)d_car | (uintptr_t)d_frames) & 3u) == 0)) {
         if (h->aplan_mode != h->projection) BEVW_TRY(analytic_units_build(h));
         if (h->aplan.n_un_all) {
+            h->last_path = BEVW_PATH_UNITS;   // (the base tiles the wide plan leaves go to k_stitch_analytic below: still the unit schedule's step)
             BEVW_TRY(plan_stitch_wide(h->aplan, h->stream, d_frames, batch, c.blend != 0, d_car, d_out));
             if (h->aplan.n_slow == 0) return BEVW_OK;
             left_tiles = static_cast<const uint32_t *>(h->aplan.list_slow);
@@ -1332,8 +1335,10 @@ static int run_device(bevw_handle *h, const FrameSource &src, int batch, const u
     const bool aligned4 = (((uintptr_t)d_out | (uintptr_t)d_car) & 3u) == 0 && src.aligned4();
     if (pitched && (h->projection != BEVW_PROJ_LUT || h->schedule_in_use != BEVW_SCHED_TILE_PLAN || !aligned4))
         return fail(BEVW_E_INVALID, "an output pitch needs the tile-plan schedule, the table projection and 4-byte aligned buffers");
-    if (h->projection == BEVW_PROJ_LUT && h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && c.balance && bal_mode() == 1 && h->plan.compact_stride != 0)
+    if (h->projection == BEVW_PROJ_LUT && h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && c.balance && bal_mode() == 1 && h->plan.compact_stride != 0) {
+        h->last_path = BEVW_PATH_UNITS;
         return balance_plan_run(h, src, batch, d_car, d_out);
+    }
     if (c.balance) {
         BEVW_TRY(ensure_stats(h, batch));
         BEVW_TRY(luminance_stats(h->stream, src, batch, c.frame_width, c.frame_height, h->vsums.as<unsigned long long>(), h->deltas.as<int>()));
@@ -1353,8 +1358,10 @@ static int run_device(bevw_handle *h, const FrameSource &src, int batch, const u
         PlanStep step;
         step.src = src; step.batch = batch; step.blend = c.blend != 0; step.balance = c.balance != 0; step.car = d_car; step.out = st_out;
         step.deltas = h->deltas.as<int>(); step.tab = h->hsv.as<HsvTables>(); step.chsums = h->chsums.as<unsigned long long>();
+        h->last_path = BEVW_PATH_UNITS;
         BEVW_TRY(plan_stitch(h->plan, h->stream, step));
     } else {
+        h->last_path = BEVW_PATH_PER_PIXEL;
         BEVW_TRY(stitch_per_pixel(h, src, batch, d_car, st_out));
     }
     if (c.balance) {
@@ -1708,6 +1715,12 @@ static int download_images(bevw_handle *h, uint8_t *out, const void *d_src, size
     if (src_pitch == row_bytes) HIP_TRY(hipMemcpyAsync(out, d_src, row_bytes * rows, hipMemcpyDeviceToHost, h->stream));
     else HIP_TRY(hipMemcpy2DAsync(out, row_bytes, d_src, src_pitch, row_bytes, rows, hipMemcpyDeviceToHost, h->stream));
     return BEVW_OK;
+}
+
+int bevw_last_path(bevw_handle *h)
+{
+    if (!h) return fail(BEVW_E_INVALID, "null handle");
+    return h->last_path;
 }
 
 int bevw_run_device(bevw_handle *h, const void *d_frames, int batch, const void *d_car, void *d_out)

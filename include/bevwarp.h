@@ -150,6 +150,18 @@ int bevw_plan_info(bevw_handle *h, int32_t info[8]);
 /* frames: [batch][4][FH][FW][3]; car: [BH][BW][3] or NULL (already padded, surroundBEV.py:28-41); out: [batch][BH][BW][3] */
 int bevw_run(bevw_handle *h, const uint8_t *frames, int batch, const uint8_t *car, uint8_t *out);
 int bevw_run_device(bevw_handle *h, const void *d_frames, int batch, const void *d_car, void *d_out);
+/* Alignment of device buffers.  On a handle with dense images (BEVW_PITCH_DENSE) d_frames, d_car and d_out of bevw_run_device (and d_car,
+ * d_out of the surface entry points) may have ANY byte alignment and lie any distance apart: a step with one of them off a 4-byte boundary
+ * is served by the per-pixel kernels instead of the tile plan (same bytes, slower), and the next aligned step is back on the plan.  A handle
+ * with an output pitch refuses such a step with BEVW_E_INVALID ("4-byte aligned") before anything is written.  The same holds for d_src /
+ * d_dst of bevw_remap_device (the k_remap_lut family serves them), for d_out, image_stride_bytes and row_pitch_bytes of
+ * bevw_jpeg_decode_run_device, and for d_bgr and both strides of bevw_jpeg_encode_run_device: any value is accepted.  Plane pointers of
+ * NV12 surfaces must be 4-byte aligned (bevw_set_input_pitch below).
+ * bevw_last_path: which kernels served the last bevw_run* step of the handle, so that tests assert the path instead of assuming it --
+ * BEVW_PATH_NONE before any step, BEVW_PATH_UNITS when the tile plan served it (the table plan, its balance schedule, or the wide plan of an
+ * analytic projection), BEVW_PATH_PER_PIXEL otherwise (the per-pixel stitch, the full-grid analytic kernel).  The constants are those of
+ * bevw_remapper_last_path below.  A refused step and the camera-shard entry points leave it unchanged. */
+int bevw_last_path(bevw_handle *h);
 /* Row pitch of the DEVICE-side BEV images (cv::cuda::GpuMat's `step`; the reference's host arrays, surroundBEV.py:312-325, stay dense).
  * A 1080-pixel row is 3240 bytes: in a dense image only one row in eight starts on a 64-byte memory sector, every other row run a
  * kernel block writes starts and ends inside a sector it shares with its neighbour, and partially written sectors are what the
@@ -360,6 +372,7 @@ int bevw_remapper_get_maps(bevw_remapper *r, int16_t *map1, uint16_t *map2);
 /* src [batch][src_h][src_w][3] -> dst [batch][dst_h][dst_w][3]; INTER_LINEAR, BORDER_CONSTANT 0 */
 int bevw_remap(bevw_remapper *r, const uint8_t *src, int batch, uint8_t *dst);
 int bevw_remap_device(bevw_remapper *r, const void *d_src, int batch, void *d_dst);
+/* (d_src and d_dst may have any byte alignment: off a 4-byte boundary the k_remap_lut family serves the step, bevw_remapper_last_path tells.) */
 /* BEVW_INPUT_NV12 (bevw_set_input_format has the layout and the arithmetic): bevw_remap and bevw_remap_device read src as
  * [batch][src_h*3/2][src_w] NV12 frames and write what cv2.remap writes for cv2.cvtColor(src, cv2.COLOR_YUV2BGR_NV12), in either
  * BEVW_COMPAT_REMAP mode.  Refused (BEVW_E_INVALID) for an odd src_w or src_h.
@@ -449,7 +462,10 @@ int bevw_resize_linear_u8c3(int device, const uint8_t *src, int src_w, int src_h
  *   bevw_jpeg_wait_engine / bevw_wait_jpeg   order the codec's stream behind an engine's stream / the engine's behind the codec's without the
  *                              host: decode -> bevw_run_device -> encode as one asynchronous chain (BevGenerator.jpeg_stream)
  *   bevw_jpeg_encode           host images in, files out (out + i * cap_each, sizes[i]); cap_each >= bevw_jpeg_encode_bound
- * All "run" calls are asynchronous on the context's own stream; bevw_jpeg_sync waits; timer marks as for handles. */
+ * All "run" calls are asynchronous on the context's own stream; bevw_jpeg_sync waits; timer marks as for handles.
+ * d_out of bevw_jpeg_decode_run_device and d_bgr of bevw_jpeg_encode_run_device may have any byte alignment, row_pitch_bytes any value >= 3 *
+ * width and image_stride_bytes any value >= row_pitch_bytes * height: the dword paths are taken only where pointer, pitch and stride allow
+ * them, and bytes of the padding columns and of the gaps between images are neither written by a decode nor let into a file by an encode. */
 #define BEVW_JPEG_420 0x22
 #define BEVW_JPEG_422 0x21
 #define BEVW_JPEG_444 0x11
