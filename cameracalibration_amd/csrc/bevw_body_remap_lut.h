@@ -1,19 +1,19 @@
 // bevw_body_remap_lut.h -- the body of k_remap_lut and k_remap_lut_yuv422 (bevw_kernels.h).
 // Included inside a kernel's braces, NOT a device function: the kernels that existed before the packed 4:2:2 formats stay the functions the
 // compiler saw then and compile to the same instructions (the same body inlined from a device function schedules differently).  In scope at
-// the point of inclusion: the kernel's parameters, the flags NV12, OUT_NV12, SURF, P422, and `ypos` (bit 0 of the byte order's Y selector; P422 only).
+// the point of inclusion: the kernel's parameters, the layout SRC of the sources, the flag OUT_NV12, and `ypos` (the Y byte's position; 4:2:2 only).
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
     if (x >= dw) return;
     const size_t o = (size_t)y * dw + x;
-    const uint8_t *s = src + (P422 ? (size_t)blockIdx.z * sw * sh * 2 : NV12 ? (size_t)blockIdx.z * frame_bytes_of(sw, sh, true) : (size_t)blockIdx.z * sw * sh * 3);
+    const uint8_t *s = src + (size_t)blockIdx.z * Src<SRC>::frame_bytes((size_t)sw * sh);
     const int sx = map1[o * 2], sy = map1[o * 2 + 1];
     int out[3];
-    if constexpr (SURF) {
+    if constexpr (Src<SRC>::surf) {
         const Nv12Surface sf = surf[blockIdx.z];
-        remap_u8c3_px<false, true, true>(sf.y, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even, sf.uv, src_pitch);
+        remap_u8c3_px<false, SRC>(sf.y, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even, sf.uv, src_pitch);
     } else {
-        remap_u8c3_px<false, NV12, false, P422>(s, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even, nullptr, 0, ypos);
+        remap_u8c3_px<false, SRC>(s, sw, sh, sx, sy, map2[o] & (kQTab2 - 1), out, 0, nullptr, ties_even, nullptr, 0, ypos);
     }
     if (OUT_NV12) {
         nv12_store_px(dst + (size_t)blockIdx.z * image_bytes_of(dw, dh, true), dw, dh, x, y,

@@ -1,9 +1,7 @@
 // bevw_body_stitch_plan.h -- the body of k_stitch_plan and k_stitch_plan_yuv422 (bevw_plan.h).
 // Included inside a kernel's braces, NOT a device function: the kernels that existed before the packed 4:2:2 formats stay the functions the
 // compiler saw then and compile to the same instructions (the same body inlined from a device function schedules differently).  In scope at
-// the point of inclusion: `a` (PlanArgs) and the flags BLEND, LUM, SUMS, NV12, OUT_NV12, SURF, P422.
-    static_assert(!SURF || NV12, "surfaces are NV12");
-    static_assert(!(P422 && NV12), "one source format");
+// the point of inclusion: `a` (PlanArgs), the layout SRC of its frames (SrcLayout) and the flags BLEND, LUM, SUMS, OUT_NV12.
     constexpr bool BAL = LUM;
     __shared__ __attribute__((aligned(16))) uint32_t hsv_words[BAL ? sizeof(HsvTables) / 4 : 1];   // (no LDS for the variants without the luminance round trip)
     const HsvTables &hsv = *reinterpret_cast<const HsvTables *>(hsv_words);
@@ -24,7 +22,7 @@
     const int x0 = (tx * kPlanLX + lane % kPlanLX) * 4, y = ty * kPlanLY + lane / kPlanLX;
     const bool inimg = x0 < a.bw && y < a.bh;
     const uint32_t frame_bytes = (uint32_t)a.fw * a.fh * 3, row_bytes = (uint32_t)a.fw * 3;
-    const uint32_t src_frame = P422 ? frame_bytes / 3 * 2 : NV12 ? frame_bytes / 2 : frame_bytes;   // bytes of one camera frame as the kernel reads it (NV12: fw even)
+    const uint32_t src_frame = Src<SRC>::frame_bytes_of_bgr(frame_bytes);   // bytes of one camera frame as the kernel reads it
     const size_t set_bytes = (size_t)src_frame * a.ncams, img_bytes = (size_t)a.pitch * a.bh * 3;
     const uint32_t ooff = ((uint32_t)y * a.pitch + x0) * 3;
 
@@ -33,7 +31,7 @@
     for (int j = 0; j < 4; ++j) {
         e0[j] = decode_entry(a.plan[((size_t)tile * 8 + j) * 64 + lane], BLEND);
         e1[j] = decode_entry(second ? a.plan[((size_t)tile * 8 + 4 + j) * 64 + lane] : make_uint2(0, 0), BLEND);
-        if (NV12 || P422) { entry_to_taps(e0[j], a.fw, frame_bytes); entry_to_taps(e1[j], a.fw, frame_bytes); }
+        if (Src<SRC>::yuv) { entry_to_taps(e0[j], a.fw, frame_bytes); entry_to_taps(e1[j], a.fw, frame_bytes); }
     }
     uint32_t car0 = 0, car1 = 0, car2 = 0;
     if (!SUMS && a.car != nullptr && inimg) {
@@ -45,8 +43,8 @@
     const int b_begin = (int)chunk * a.nb, b_end = min(a.batch, b_begin + a.nb);
 #pragma unroll 1
     for (int b = b_begin; b < b_end; ++b) {
-        const uint8_t *fb = SURF ? nullptr : a.frames + (size_t)b * set_bytes;
-        const Nv12Surface *fs = SURF ? a.surf + (size_t)b * a.ncams : nullptr;
+        const uint8_t *fb = Src<SRC>::surf ? nullptr : a.frames + (size_t)b * set_bytes;
+        const Nv12Surface *fs = Src<SRC>::surf ? a.surf + (size_t)b * a.ncams : nullptr;
         const int *fdeltas = BAL ? a.deltas + b * 4 : nullptr;
         int px[4][3];
         if (hdr & kHdrEmpty) {
@@ -55,13 +53,13 @@
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                eval_entry<BLEND, BAL, NV12, SURF, P422>(fb, e0[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, px[j], fs, a.src_pitch, a.yuv422.ysel & 1u);
+                eval_entry<BLEND, BAL, SRC>(fb, e0[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, px[j], fs, a.src_pitch, a.yuv422.ysel & 1u);
             }
             if (second) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     int w[3];
-                    eval_entry<BLEND, BAL, NV12, SURF, P422>(fb, e1[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, w, fs, a.src_pitch, a.yuv422.ysel & 1u);
+                    eval_entry<BLEND, BAL, SRC>(fb, e1[j], row_bytes, a.fw, a.fh, src_frame, tile_slow, fdeltas, hsv, w, fs, a.src_pitch, a.yuv422.ysel & 1u);
                     px[j][0] = min(255, px[j][0] + w[0]); px[j][1] = min(255, px[j][1] + w[1]); px[j][2] = min(255, px[j][2] + w[2]);
                 }
             }

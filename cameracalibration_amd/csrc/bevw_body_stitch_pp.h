@@ -1,7 +1,7 @@
 // bevw_body_stitch_pp.h -- the body of k_stitch_pp and k_stitch_pp_yuv422 (bevw_kernels.h).
 // Included inside a kernel's braces, NOT a device function: the kernels that existed before the packed 4:2:2 formats stay the functions the
 // compiler saw then and compile to the same instructions (the same body inlined from a device function schedules differently).  In scope at
-// the point of inclusion: the kernel's parameters, the flags BLEND, BAL, NV12, OUT_NV12, SURF, P422, and `ypos` (bit 0 of the byte order's Y selector; P422 only).
+// the point of inclusion: the kernel's parameters, the layout SRC of the frames, the flags BLEND, BAL, OUT_NV12, and `ypos` (the Y byte's position; 4:2:2 only).
     __shared__ HsvTables hsv;
     __shared__ unsigned long long part[3][4];
     if (BAL) {
@@ -11,7 +11,7 @@
     const int x = blockIdx.x * blockDim.x + threadIdx.x;
     const int y = blockIdx.y;
     const int b = blockIdx.z;
-    const size_t frame_bytes = P422 ? (size_t)fw * fh * 2 : NV12 ? frame_bytes_of(fw, fh, true) : (size_t)fw * fh * 3;
+    const size_t frame_bytes = Src<SRC>::frame_bytes((size_t)fw * fh);
     int acc[3] = {0, 0, 0};
     if (x < bw) {
         const size_t o = (size_t)y * bw + x;
@@ -22,12 +22,12 @@
             const uint8_t *src = frames + ((size_t)b * 4 + c) * frame_bytes;
             const int sx = T.lut1[c][o * 2], sy = T.lut1[c][o * 2 + 1];
             int v[3];
-            if constexpr (SURF) {
+            if constexpr (Src<SRC>::surf) {
                 const Nv12Surface sf = surf[(size_t)b * 4 + c];
-                remap_u8c3_px<BAL, true, true>(sf.y, fw, fh, sx, sy, T.lut2[c][o] & (kQTab2 - 1), v, BAL ? deltas[b * 4 + c] : 0, &hsv, ties_even, sf.uv,
+                remap_u8c3_px<BAL, SRC>(sf.y, fw, fh, sx, sy, T.lut2[c][o] & (kQTab2 - 1), v, BAL ? deltas[b * 4 + c] : 0, &hsv, ties_even, sf.uv,
                                                src_pitch);
             } else
-            remap_u8c3_px<BAL, NV12, false, P422>(src, fw, fh, sx, sy, T.lut2[c][o] & (kQTab2 - 1), v, BAL ? deltas[b * 4 + c] : 0, &hsv, ties_even, nullptr, 0, ypos);
+            remap_u8c3_px<BAL, SRC>(src, fw, fh, sx, sy, T.lut2[c][o] & (kQTab2 - 1), v, BAL ? deltas[b * 4 + c] : 0, &hsv, ties_even, nullptr, 0, ypos);
             if (BLEND) {
                 const float wgt = blend_weight_f32(m);
                 v[0] = blend_mul(v[0], wgt); v[1] = blend_mul(v[1], wgt); v[2] = blend_mul(v[2], wgt);

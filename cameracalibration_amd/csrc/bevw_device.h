@@ -310,6 +310,26 @@ __host__ __device__ __forceinline__ size_t frame_bytes_of(int fw, int fh, SrcFor
     if (f == SrcFormat::GRAY) return (size_t)fw * fh;
     return src_is_yuv422(f) ? (size_t)fw * fh * 2 : frame_bytes_of(fw, fh, f == SrcFormat::NV12);
 }
+// How the memory a kernel or a group list reads is laid out.  The first four are the layouts of camera frames, and the one template
+// parameter (SRC) of every format-templated kernel and device function:
+//   kLayoutBGR     dense frame sets of 3 bytes per texel: the reference's frames
+//   kLayoutNV12    dense NV12 frame sets (nv12_texel): a Y plane and an interleaved U / V plane of half the rows, rows of fw bytes
+//   kLayoutSurf    NV12 surfaces read in place (Nv12Surface, nv12_texel_planes): a plane pair per camera and a row pitch (`surf`, `uvp`, `src_pitch`, `pitch`)
+//   kLayoutYuv422  dense packed 4:2:2 frame sets (yuv422_texel), YUYV or UYVY: the byte order is a kernel argument (`order`, `ypos`, a.yuv422)
+// Every texel of the three YUV layouts is converted to BGR where it is fetched, before the balance step.  The others exist on the host only,
+// as slots of a plan's group lists (bevw_planapi.h); kLayoutGray stands behind kSrcLayouts, the layouts of three-channel sources.
+enum SrcLayout { kLayoutBGR = 0, kLayoutNV12, kLayoutSurf, kLayoutYuv422, kLayoutCompact, kSrcLayouts, kLayoutGray = kSrcLayouts, kPlanLayouts };
+// what the code under a SRC parameter asks about it
+template <SrcLayout L> struct Src {
+    static_assert(L <= kLayoutYuv422, "device code is instantiated for the four frame layouts");
+    static constexpr bool nv12 = L == kLayoutNV12 || L == kLayoutSurf;   // NV12, packed or surfaces
+    static constexpr bool surf = L == kLayoutSurf, p422 = L == kLayoutYuv422;
+    static constexpr bool yuv = nv12 || p422;                            // converted per fetched texel: no BGR fast paths
+    // bytes of one frame: of `texels` texels, and from the BGR frame's bytes in the plan's 32-bit arithmetic (fw even; k_stitch_plan_yuv422
+    // compiles to other instructions when spelled through the first)
+    __host__ __device__ static constexpr size_t frame_bytes(size_t texels) { return p422 ? texels * 2 : nv12 ? texels * 3 / 2 : texels * 3; }
+    __host__ __device__ static constexpr uint32_t frame_bytes_of_bgr(uint32_t bgr_bytes) { return p422 ? bgr_bytes / 3 * 2 : nv12 ? bgr_bytes / 2 : bgr_bytes; }
+};
 // The byte order as the kernels take it: the v_perm_b32 selectors that pick, from the 8 bytes of four texels {hi, lo}, their four Y bytes
 // and their U V U V bytes -- a wave-uniform kernel argument, so UYVY is no kernel of its own.  Bit 0 of the Y selector is the position of
 // a texel's Y byte inside its two bytes (0: YUYV, 1: UYVY), which is all the per-tap fetch needs.
@@ -418,21 +438,18 @@ __device__ __forceinline__ int remap_round10(int S, int ties_even)
     if (ties_even && (S & 1023) == 512 && (r & 1)) --r;
     return r;
 }
-// NV12: `src` is an NV12 frame (nv12_texel), the texels are converted before the balance step
-// SURF (with NV12): `src` is the Y plane and `uvp` the U / V plane of a surface with rows of `pitch` bytes (nv12_texel_planes)
-// P422 (not with NV12): `src` is a packed 4:2:2 frame (yuv422_texel) and `ypos` bit 0 of its Y selector (Yuv422Order)
-template <bool LUM, bool NV12 = false, bool SURF = false, bool P422 = false>
+// SRC (SrcLayout): `src` is one frame of that layout; surfaces: `src` is the Y plane and `uvp` the U / V plane, rows of `pitch` bytes; packed
+// 4:2:2: `ypos` is bit 0 of the byte order's Y selector (Yuv422Order)
+template <bool LUM, SrcLayout SRC = kLayoutBGR>
 __device__ __forceinline__ void remap_u8c3_px(const uint8_t *__restrict__ src, int sw, int sh, int sx, int sy,
                                               unsigned code, int out[3], int delta, const HsvTables *hsv, int ties_even = 0,
                                               const uint8_t *__restrict__ uvp = nullptr, int pitch = 0, uint32_t ypos = 0)
 {
-    static_assert(!SURF || NV12, "surfaces are NV12");
-    static_assert(!(P422 && NV12), "one source format");
     const int fx = code & 31, fy = (code >> 5) & 31;
     const int ax = kQOne - fx, ay = kQOne - fy;
     const int w00 = ax * ay, w01 = fx * ay, w10 = ax * fy, w11 = fx * fy;
     const unsigned xlim = sw > 1 ? sw - 1 : 0, ylim = sh > 1 ? sh - 1 : 0;
-    if constexpr (NV12 || P422) {
+    if constexpr (Src<SRC>::yuv) {
         // one path for interior and border footprints: a tap outside the frame is 0 (BORDER_CONSTANT, after the balance step)
         if (sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0) { out[0] = out[1] = out[2] = 0; return; }
         int t[4][3];
@@ -440,7 +457,7 @@ __device__ __forceinline__ void remap_u8c3_px(const uint8_t *__restrict__ src, i
         for (int q = 0; q < 4; ++q) {
             const int x = sx + (q & 1), y = sy + (q >> 1);
             if ((unsigned)x < (unsigned)sw && (unsigned)y < (unsigned)sh) {
-                const uint32_t p = P422 ? yuv422_texel(src, sw, x, y, ypos) : SURF ? nv12_texel_planes(src, uvp, pitch, x, y) : nv12_texel(src, sw, sh, x, y);
+                const uint32_t p = Src<SRC>::p422 ? yuv422_texel(src, sw, x, y, ypos) : Src<SRC>::surf ? nv12_texel_planes(src, uvp, pitch, x, y) : nv12_texel(src, sw, sh, x, y);
                 t[q][0] = (int)(p & 255u); t[q][1] = (int)((p >> 8) & 255u); t[q][2] = (int)(p >> 16);
                 if (LUM) luminance_shift_px(t[q][0], t[q][1], t[q][2], delta, *hsv);
             } else {

@@ -5,6 +5,7 @@
 // launch helpers (batch chunks, compile-time flags, compile-time pixel formats).
 #pragma once
 #include "../../include/bevwarp.h"
+#include "bevw_device.h"   // SrcLayout
 
 #include <hip/hip_runtime.h>
 
@@ -84,20 +85,19 @@ static inline void with_flags(F &&f, bool b, B... rest)
     else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
-// What a format-templated kernel reads, as a compile-time constant: packed BGR frames, packed NV12 frames or NV12 surfaces -- surfaces are
-// NV12, so a kernel's <NV12, SURF> pair is one of these three.  with_input: f(in) launches k<.., in.nv12, in.surf>.
-template <bool NV12, bool SURF> struct InputKind { static constexpr bool nv12 = NV12, surf = SURF; };
+// What a format-templated kernel reads, as a compile-time constant (SrcLayout): f(in) launches k<.., in> for NV12 surfaces, packed NV12 frames,
+// or BGR frames (every other layout: packed 4:2:2 and one-channel frames have launchers of their own, which the caller picks first).
 template <typename F>
-static inline void with_input(bool nv12, bool surf, F &&f)
+static inline void with_layout(bevw::SrcLayout lay, F &&f)
 {
-    if (surf) f(InputKind<true, true>{});
-    else if (nv12) f(InputKind<true, false>{});
-    else f(InputKind<false, false>{});
+    if (lay == bevw::kLayoutSurf) f(std::integral_constant<bevw::SrcLayout, bevw::kLayoutSurf>{});
+    else if (lay == bevw::kLayoutNV12) f(std::integral_constant<bevw::SrcLayout, bevw::kLayoutNV12>{});
+    else f(std::integral_constant<bevw::SrcLayout, bevw::kLayoutBGR>{});
 }
-// ... x BGR / NV12 images: f(in, out_nv12) launches k<.., in.nv12, out_nv12, in.surf>.  Flags that exist with BGR images only (luminance
-// round trip, channel sums) stay with the caller: fixed under `if constexpr (out_nv12)`, walked by with_flags otherwise.
+// ... x BGR / NV12 images: f(in, out_nv12) launches k<.., in, out_nv12>.  Flags that exist with BGR images only (luminance round trip,
+// channel sums) stay with the caller: fixed under `if constexpr (out_nv12)`, walked by with_flags otherwise.
 template <typename F>
-static inline void with_formats(bool nv12, bool surf, bool out_nv12, F &&f) { with_input(nv12, surf, [&](auto in) { with_flags([&](auto on) { f(in, on); }, out_nv12); }); }
+static inline void with_layout_out(bevw::SrcLayout lay, bool out_nv12, F &&f) { with_layout(lay, [&](auto in) { with_flags([&](auto on) { f(in, on); }, out_nv12); }); }
 
 // Lap timer: HIP events recorded on an engine's own stream WITHOUT synchronising, read back after the caller's final sync
 // (bench.py: one mark in front of every step -> per-step durations, median instead of one mean over a 13 ms region).

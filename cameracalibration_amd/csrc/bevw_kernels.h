@@ -252,16 +252,15 @@ static __global__ void k_blend_weights(uint8_t *__restrict__ maskA, const uint8_
 // =============================================================================================================
 
 // cv2.remap(src, map1, map2, INTER_LINEAR) for a batch: one thread per destination pixel.
-// grid = (ceil(dw / 256), dh, batch).  NV12: the sources are NV12 frames (bevw_remapper_set_input_format), converted per tap.
+// grid = (ceil(dw / 256), dh, batch).  SRC: the layout of the sources (bevw_remapper_set_input_format), converted per tap; surfaces
+// (bevw_remap_surfaces_device): surf[image] with rows of src_pitch bytes, `src` is not read; packed 4:2:2: k_remap_lut_yuv422 (ypos: bit 0 of
+// the byte order's Y selector)
 // OUT_NV12: dst holds dense NV12 images (bevw_remapper_set_output_format, dw and dh even): the pixel's Y, and U / V on even rows and columns
-// SURF: the sources are NV12 surfaces (bevw_remap_surfaces_device): surf[image] with rows of src_pitch bytes, `src` is not read
-// P422: the sources are packed 4:2:2 frames (YUYV / UYVY; ypos: bit 0 of the byte order's Y selector), converted per tap (k_remap_lut_yuv422)
-template <bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
+template <SrcLayout SRC, bool OUT_NV12>
 static __global__ void k_remap_lut(const uint8_t *__restrict__ src, int sw, int sh, const int16_t *__restrict__ map1,
                             const uint16_t *__restrict__ map2, int dw, int dh, uint8_t *__restrict__ dst, int ties_even = 0,
                             const Nv12Surface *__restrict__ surf = nullptr, int src_pitch = 0)
 {
-    constexpr bool P422 = false;
     constexpr uint32_t ypos = 0;
 #include "bevw_body_remap_lut.h"
 }
@@ -302,26 +301,25 @@ __device__ __forceinline__ unsigned vsum_piece(const VsumPiece &p)
 }
 // part_stride 0: the blocks of a frame add their sums atomically into sums[frame] (zeroed by the caller); > 0: block x of frame y stores
 // its sum at sums[y * part_stride + x] -- no atomics, no zeroing pass in front of the kernel; k_lum_delta adds the parts.
-// NV12: NV12 frames of fw texels per row (frame_bytes = fw * fh * 3 / 2), V of the converted texels: the blocks of a frame take its rows
-// round-robin, a lane a horizontal texel pair (two Y bytes and the U / V pair they share) per trip.
-// SURF: NV12 surfaces -- surf[frame] with rows of src_pitch bytes, of which the first fw are texels (the padding columns are not summed)
-template <bool NV12 = false, bool SURF = false>
+// SRC (BGR, NV12 or surfaces; packed 4:2:2: k_vsum_yuv422).  NV12: frames of fw texels per row (frame_bytes = fw * fh * 3 / 2), V of the
+// converted texels: the blocks of a frame take its rows round-robin, a lane a horizontal texel pair (two Y bytes and the U / V pair they
+// share) per trip.  Surfaces: surf[frame] with rows of src_pitch bytes, of which the first fw are texels (the padding columns are not summed)
+template <SrcLayout SRC>
 static __global__ void k_vsum(const uint8_t *__restrict__ frames, size_t frame_bytes, int vec_ok,
                        unsigned long long *__restrict__ sums, int part_stride = 0, int fw = 0,
                        const Nv12Surface *__restrict__ surf = nullptr, int src_pitch = 0)
 {
-    static_assert(!SURF || NV12, "surfaces are NV12");
-    const uint8_t *f = SURF ? nullptr : frames + (size_t)blockIdx.y * frame_bytes;
-    const size_t npieces = (vec_ok && !NV12) ? frame_bytes / 12 : 0;
+    const uint8_t *f = Src<SRC>::surf ? nullptr : frames + (size_t)blockIdx.y * frame_bytes;
+    const size_t npieces = (vec_ok && !Src<SRC>::nv12) ? frame_bytes / 12 : 0;
     const VsumPiece *fp = reinterpret_cast<const VsumPiece *>(f);
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (size_t)gridDim.x * blockDim.x;
     unsigned acc = 0;
-    if (NV12) {
+    if (Src<SRC>::nv12) {
         auto v = [](uint32_t t) { return max(t & 255u, max((t >> 8) & 255u, t >> 16)); };
         const int fh = (int)(frame_bytes / 3 * 2 / (size_t)fw), npairs = fw / 2;
         const uint8_t *yp = f, *uvp = f + (size_t)fw * fh;
         int rb = fw;   // bytes between rows
-        if constexpr (SURF) {
+        if constexpr (Src<SRC>::surf) {
             const Nv12Surface sf = surf[blockIdx.y];
             yp = sf.y; uvp = sf.uv; rb = src_pitch;
         }
@@ -348,7 +346,7 @@ static __global__ void k_vsum(const uint8_t *__restrict__ frames, size_t frame_b
     }
     for (; i < npieces; i += nthreads) acc += vsum_piece(fp[i]);
     // texels not covered by whole pieces
-    for (size_t t = npieces * 4 + tid; !NV12 && t * 3 + 2 < frame_bytes; t += nthreads)
+    for (size_t t = npieces * 4 + tid; !Src<SRC>::nv12 && t * 3 + 2 < frame_bytes; t += nthreads)
         acc += max((unsigned)f[t * 3], max((unsigned)f[t * 3 + 1], (unsigned)f[t * 3 + 2]));
     __shared__ unsigned long long part[16];
     unsigned long long s = wave_sum_u64(acc);
@@ -404,17 +402,16 @@ static __global__ void k_lum_shift(const uint8_t *__restrict__ frames, size_t fr
 // sprite is added here; with balance the pre-gain value is stored and per-frame channel sums are accumulated
 // (integer, so the result does not depend on the order of the atomics).
 // grid = (ceil(bw / 256), bh, batch)
-// NV12: NV12 frame sets (bevw_set_input_format), every tap converted where it is fetched (remap_u8c3_px)
+// SRC: the layout of the frame sets (bevw_set_input_format), every tap converted where it is fetched (remap_u8c3_px); surfaces
+// (bevw_run_surfaces_device): surf[frame set][camera] with rows of src_pitch bytes, `frames` is not read; packed 4:2:2: k_stitch_pp_yuv422
+// (ypos: bit 0 of the byte order's Y selector)
 // OUT_NV12 (not with BAL, whose pre-gain image is BGR): dense NV12 BEV images (bevw_set_output_format), converted after the car
-// SURF: NV12 surfaces (bevw_run_surfaces_device) -- surf[frame set][camera] with rows of src_pitch bytes, `frames` is not read
-// P422: packed 4:2:2 frame sets (YUYV / UYVY; ypos: bit 0 of the byte order's Y selector), every tap converted where it is fetched (k_stitch_pp_yuv422)
-template <bool BLEND, bool BAL, bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
+template <bool BLEND, bool BAL, SrcLayout SRC, bool OUT_NV12>
 static __global__ void k_stitch_pp(const uint8_t *__restrict__ frames, int fw, int fh, StitchTables T, int bw, int bh,
                             const int *__restrict__ deltas, const HsvTables *__restrict__ tab,
                             const uint8_t *__restrict__ car, unsigned long long *__restrict__ chsums,
                             uint8_t *__restrict__ out, int ties_even = 0, const Nv12Surface *__restrict__ surf = nullptr, int src_pitch = 0)
 {
-    constexpr bool P422 = false;
     constexpr uint32_t ypos = 0;
 #include "bevw_body_stitch_pp.h"
 }

@@ -8,19 +8,19 @@
 namespace bevw {
 
 // ---- the unit kernel (bevw_unit.h) --------------------------------------------------------------------------------------------------
-// Packed 4:2:2 frame sets (bevw_set_input_format: YUYV, UYVY): the same launch over the P422 instantiation of plan_unit_run, writing BGR
+// Packed 4:2:2 frame sets (bevw_set_input_format: YUYV, UYVY): the same launch over the kLayoutYuv422 instantiation of plan_unit_run, writing BGR
 // (k_units_yuv422) or NV12 images (k_units_out_yuv422); the byte order rides in a.yuv422.
 template <bool BLEND>
 __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_yuv422(PlanArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
-    plan_unit_any<BLEND, false, false, false, false, true>(a, blockIdx.x, patch, nullptr);
+    plan_unit_any<BLEND, false, kLayoutYuv422, false>(a, blockIdx.x, patch, nullptr);
 }
 template <bool BLEND>
 __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_out_yuv422(PlanArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
-    plan_unit_any<BLEND, false, false, true, false, true>(a, blockIdx.x, patch, nullptr);
+    plan_unit_any<BLEND, false, kLayoutYuv422, true>(a, blockIdx.x, patch, nullptr);
 }
 
 // ---- the per-tap tile kernel and the balance scratch (bevw_plan.h) ------------------------------------------------------------------------
@@ -28,7 +28,7 @@ __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_
 template <bool BLEND, bool LUM, bool SUMS, bool OUT_NV12>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) k_stitch_plan_yuv422(PlanArgs a)
 {
-    constexpr bool NV12 = false, SURF = false, P422 = true;
+    constexpr SrcLayout SRC = kLayoutYuv422;
 #include "bevw_body_stitch_plan.h"
 }
 
@@ -38,7 +38,7 @@ static __global__ void __launch_bounds__(256) k_lum_groups_yuv422(const uint8_t 
                                                                    const int *__restrict__ deltas, const HsvTables *__restrict__ tab,
                                                                    uint32_t blocks_per_frame, uint32_t nframes, Yuv422Order order)
 {
-    constexpr bool NV12 = false, SURF = false, P422 = true;
+    constexpr SrcLayout SRC = kLayoutYuv422;
     const Nv12Surface *const surf = nullptr;
 #include "bevw_body_lum_groups.h"
 }
@@ -51,7 +51,7 @@ static __global__ void k_stitch_pp_yuv422(const uint8_t *__restrict__ frames, in
                                           const uint8_t *__restrict__ car, unsigned long long *__restrict__ chsums,
                                           uint8_t *__restrict__ out, int ties_even, uint32_t ypos)
 {
-    constexpr bool NV12 = false, SURF = false, P422 = true;
+    constexpr SrcLayout SRC = kLayoutYuv422;
     const Nv12Surface *const surf = nullptr;
     constexpr int src_pitch = 0;
 #include "bevw_body_stitch_pp.h"
@@ -62,7 +62,7 @@ template <bool OUT_NV12>
 static __global__ void k_remap_lut_yuv422(const uint8_t *__restrict__ src, int sw, int sh, const int16_t *__restrict__ map1,
                                           const uint16_t *__restrict__ map2, int dw, int dh, uint8_t *__restrict__ dst, int ties_even, uint32_t ypos)
 {
-    constexpr bool NV12 = false, SURF = false, P422 = true;
+    constexpr SrcLayout SRC = kLayoutYuv422;
     const Nv12Surface *const surf = nullptr;
     constexpr int src_pitch = 0;
 #include "bevw_body_remap_lut.h"

@@ -169,21 +169,18 @@ static __global__ void k_plan_touch(const uint2 *__restrict__ plan, int ntiles, 
 // sector, and the units then re-read that sparse layout.)  A block takes kLumTrips x 256 consecutive groups of one frame set (the 4 KB of
 // tables in LDS are paid once per block); the offsets and the texels of all its trips are requested before the first one is converted.
 // grid = xcd_frame_grid(ceil(ngroups / (256 kLumTrips)), batch); block = 256.
-// NV12: the raw frames are NV12 frame sets (bevw_set_input_format), `groups` holds two offsets per group (Y, U / V: unit_gsrc_nv12, in the
-// same order) and frame_bytes is an NV12 frame's; a lane loads 4 Y and 4 U / V bytes and converts its texels (nv12_row_bgr) before the shift.
-// The scratch is BGR either way.
-// SURF: NV12 surfaces (bevw_run_surfaces_device): surf[frame set][4], `groups` holds the offsets inside the camera's own planes and the camera
-// in the low bits of the second one (unit_gsrc_surf); `frames` is not read.
-// P422: packed 4:2:2 frame sets (YUYV / UYVY), `groups` holds one offset per group (unit_gsrc_yuv422) and frame_bytes is a 4:2:2 frame's; a
-// lane loads the 8 bytes of its 4 texels and splits them by the byte order's selectors (`order`) into the Y and U / V words of the NV12 path.
+// SRC: the layout of the raw frames, whose `groups` and frame_bytes these are; the scratch is BGR whatever it is.  NV12: two offsets per group
+// (Y, U / V: unit_gsrc_nv12, in the same order), a lane loads 4 Y and 4 U / V bytes and converts its texels (nv12_row_bgr) before the shift.
+// Surfaces: surf[frame set][4], the offsets lie inside the camera's own planes with the camera in the low bits of the second one
+// (unit_gsrc_surf); `frames` is not read.  Packed 4:2:2: one offset per group (unit_gsrc_yuv422), a lane loads the 8 bytes of its 4 texels
+// and splits them by the byte order's selectors (`order`) into the Y and U / V words of the NV12 path.
 constexpr int kLumTrips = 8;
-template <bool NV12 = false, bool SURF = false>
+template <SrcLayout SRC>
 static __global__ void __launch_bounds__(256) k_lum_groups(const uint8_t *__restrict__ frames, uint8_t *__restrict__ scratch, size_t set_bytes,
                                                             size_t scratch_stride, uint32_t frame_bytes, const uint32_t *__restrict__ groups, int ngroups,
                                                             const int *__restrict__ deltas, const HsvTables *__restrict__ tab,
                                                             uint32_t blocks_per_frame, uint32_t nframes, const Nv12Surface *__restrict__ surf = nullptr)
 {
-    constexpr bool P422 = false;
     constexpr Yuv422Order order = {};
 #include "bevw_body_lum_groups.h"
 }
@@ -241,26 +238,23 @@ __device__ __forceinline__ void entry_to_taps(EntryRegs &e, int fw, uint32_t fra
     }
 }
 
-// NV12: `fb` is an NV12 frame set, frame_bytes an NV12 frame's, every valid entry on the per-tap path (entry_to_taps) with the conversion per
-// fetched texel (remap_u8c3_px); an entry without a contributor adds 0
-// SURF: `fs` holds the surfaces of the frame set's cameras (rows of src_pitch bytes), `fb` is not read
-// P422: `fb` is a packed 4:2:2 frame set, frame_bytes a 4:2:2 frame's, ypos bit 0 of the byte order's Y selector; evaluated as NV12 is
-template <bool BLEND, bool BAL, bool NV12 = false, bool SURF = false, bool P422 = false>
+// SRC: `fb` is a frame set of that layout and frame_bytes one frame's (surfaces: `fs` holds the surfaces of the frame set's cameras, rows of
+// src_pitch bytes, and `fb` is not read; packed 4:2:2: ypos is bit 0 of the byte order's Y selector).  The YUV layouts have every valid entry
+// on the per-tap path (entry_to_taps) with the conversion per fetched texel (remap_u8c3_px); an entry without a contributor adds 0
+template <bool BLEND, bool BAL, SrcLayout SRC = kLayoutBGR>
 __device__ __forceinline__ void eval_entry(const uint8_t *__restrict__ fb, const EntryRegs &e, uint32_t row_bytes, int fw,
                                            int fh, uint32_t frame_bytes, bool tile_slow, const int *__restrict__ fdeltas,
                                            const HsvTables &hsv, int v[3], const Nv12Surface *__restrict__ fs = nullptr, int src_pitch = 0, uint32_t ypos = 0)
 {
     const int cam = (e.meta >> 18) & 3;
-    if (NV12 || P422) {
+    if (Src<SRC>::yuv) {
         if (e.meta & kMetaValid) {
             const int sx = (int)(int16_t)(e.off & 0xffffu), sy = (int)(int16_t)(e.off >> 16);
-            if constexpr (P422) {
-                remap_u8c3_px<BAL, false, false, true>(fb + (size_t)cam * frame_bytes, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv, 0, nullptr, 0, ypos);
-            } else if constexpr (SURF) {
+            if constexpr (Src<SRC>::surf) {
                 const Nv12Surface sf = fs[cam];
-                remap_u8c3_px<BAL, true, true>(sf.y, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv, 0, sf.uv, src_pitch);
+                remap_u8c3_px<BAL, SRC>(sf.y, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv, 0, sf.uv, src_pitch);
             } else
-            remap_u8c3_px<BAL, true>(fb + (size_t)cam * frame_bytes, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv);
+            remap_u8c3_px<BAL, SRC>(fb + (size_t)cam * frame_bytes, fw, fh, sx, sy, e.meta & 1023u, v, BAL ? fdeltas[cam] : 0, &hsv, 0, nullptr, 0, ypos);
         } else {
             v[0] = v[1] = v[2] = 0;
         }
@@ -314,11 +308,11 @@ struct PlanArgs {
     // channel sums (balance): psums[frame][nsum][3], ONE writer per entry and frame -- unit u writes entry u, the per-tap kernel entry
     // sum_base + its position in the tile list (sum_base = number of units; 0 when it serves every tile)
     int nsum, sum_base;
-    // NV12 surfaces (bevw_run_surfaces_device; the SURF instantiations): surf[frame set][ncams] instead of `frames`, rows of src_pitch bytes;
+    // NV12 surfaces (bevw_run_surfaces_device; the kLayoutSurf instantiations): surf[frame set][ncams] instead of `frames`, rows of src_pitch bytes;
     // un_gsrc then holds the units' group lists relative to the camera's own planes (unit_gsrc_surf)
     const Nv12Surface *surf;
     int src_pitch;
-    // packed 4:2:2 frame sets (the P422 instantiations): the byte order of `frames` (YUYV / UYVY); un_gsrc then holds unit_gsrc_yuv422's list
+    // packed 4:2:2 frame sets (the kLayoutYuv422 instantiations): the byte order of `frames` (YUYV / UYVY); un_gsrc then holds unit_gsrc_yuv422's list
     Yuv422Order yuv422;
 };
 
@@ -358,15 +352,13 @@ static inline unsigned plan_grid(const PlanArgs &a)
 // The per-tap tile kernel.  grid: blocks of 4 waves = 4 base tiles of the list; one tile per wave.
 // LUM: luminance round trip per fetched texel (raw frames); SUMS: emit per-tile channel sums and leave the car to the gain pass
 // (two waves per SIMD: the 128-VGPR budget of rounds 1 - 3 spilled 0.5 - 1.2 KB per lane to scratch -- tools/kernel_resources.sh)
-// NV12: NV12 frame sets (bevw_set_input_format), every tap converted where it is fetched (eval_entry)
+// SRC: the layout of a.frames (surfaces: a.surf, a.src_pitch instead; packed 4:2:2: a.yuv422, k_stitch_plan_yuv422); the YUV layouts have
+// every tap converted where it is fetched (eval_entry)
 // OUT_NV12: NV12 BEV images (bevw_set_output_format; a.pitch % 4 == 0, no SUMS: the balance modes store BGR for the gain pass) -- a lane's
 // quad as one Y dword and, on even rows, one U / V dword (nv12_quad), after the car
-// SURF: NV12 surfaces (a.surf, a.src_pitch) instead of a.frames
-// P422: packed 4:2:2 frame sets (a.yuv422), on the per-tap path as NV12 is (k_stitch_plan_yuv422)
-template <bool BLEND, bool LUM, bool SUMS = LUM, bool NV12 = false, bool OUT_NV12 = false, bool SURF = false>
+template <bool BLEND, bool LUM, bool SUMS, SrcLayout SRC, bool OUT_NV12>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 8))) k_stitch_plan(PlanArgs a)
 {
-    constexpr bool P422 = false;
 #include "bevw_body_stitch_plan.h"
 }
 }  // namespace bevw
@@ -607,13 +599,12 @@ static inline void plan_launch_units(const PlanArgs &a, hipStream_t st, bool ble
 {
     if (lay == kLayoutYuv422) return yuv422_launch_units(a, st, blend, out_nv12);   // (k_units_yuv422 / k_units_out_yuv422: bevwarp_yuv422.hip)
     const dim3 grid(plan_grid(a)), block(256);
-    with_formats(lay == kLayoutNV12 || lay == kLayoutSurf, lay == kLayoutSurf, out_nv12, [&](auto in, auto on) {
-        constexpr bool NV12 = decltype(in)::nv12, SURF = decltype(in)::surf, OUT_NV12 = decltype(on)::value;
+    with_layout_out(lay == kLayoutCompact ? kLayoutBGR : lay, out_nv12, [&](auto in, auto on) {   // (the compact scratch holds BGR groups)
         with_flags([&](auto bl) {
-            if constexpr (SURF && OUT_NV12) hipLaunchKernelGGL((k_units_out_surf<bl>), grid, block, 0, st, a);
-            else if constexpr (SURF) hipLaunchKernelGGL((k_units_surf<bl>), grid, block, 0, st, a);
-            else if constexpr (OUT_NV12) hipLaunchKernelGGL((k_units_out_nv12<bl, NV12>), grid, block, 0, st, a);
-            else if constexpr (NV12) hipLaunchKernelGGL((k_units_nv12<bl>), grid, block, 0, st, a);
+            if constexpr (in == kLayoutSurf && on) hipLaunchKernelGGL((k_units_out_surf<bl>), grid, block, 0, st, a);
+            else if constexpr (in == kLayoutSurf) hipLaunchKernelGGL((k_units_surf<bl>), grid, block, 0, st, a);
+            else if constexpr (on) hipLaunchKernelGGL((k_units_out_nv12<bl, in>), grid, block, 0, st, a);
+            else if constexpr (in == kLayoutNV12) hipLaunchKernelGGL((k_units_nv12<bl>), grid, block, 0, st, a);
             else with_flags([&](auto sm) { hipLaunchKernelGGL((k_plan_units<bl, sm>), grid, block, 0, st, a); }, sums);
         }, blend);
     });
@@ -722,11 +713,10 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
         a.frames = s.src.packed; a.set_stride = 0;   // the per-tap kernel reads whole frames: RAW ones in the balance modes
         // (packed 4:2:2: k_stitch_plan_yuv422, bevwarp_yuv422.hip)
         if (rt.frames == kLayoutYuv422) yuv422_launch_stitch_plan(a, st, s.blend, rt.lum, rt.tap_sums, out_nv12);
-        else with_formats(rt.frames != kLayoutBGR, rt.frames == kLayoutSurf, out_nv12, [&](auto in, auto on) {
-            constexpr bool NV12 = decltype(in)::nv12, SURF = decltype(in)::surf, OUT_NV12 = decltype(on)::value;
-            auto launch = [&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm, NV12, OUT_NV12, SURF>), dim3(plan_grid(a)), dim3(256), 0, st, a); };
+        else with_layout_out(rt.frames, out_nv12, [&](auto in, auto on) {
+            auto launch = [&](auto bl, auto lum, auto sm) { hipLaunchKernelGGL((k_stitch_plan<bl, lum, sm, in, on>), dim3(plan_grid(a)), dim3(256), 0, st, a); };
             // (neither LUM nor SUMS exists with NV12 images: plan_route)
-            if constexpr (OUT_NV12) with_flags([&](auto bl) { launch(bl, std::false_type{}, std::false_type{}); }, s.blend);
+            if constexpr (on) with_flags([&](auto bl) { launch(bl, std::false_type{}, std::false_type{}); }, s.blend);
             else with_flags(launch, s.blend, rt.lum, rt.tap_sums);
         });
         if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -764,18 +754,19 @@ static inline hipError_t plan_lum_band(const Plan &p, hipStream_t st, const Fram
 {
     if (p.n_groups == 0 || p.compact_stride == 0) return hipSuccess;
     // the sampled groups as this kind of source addresses them (surfaces: relative to the camera's own planes)
-    const void *groups = p.sampled[frames_layout(src.fmt, src.is_surf())];
+    const SrcLayout lay = frames_layout(src.fmt, src.is_surf());
+    const void *groups = p.sampled[lay];
     if (!groups || src.fmt != p.fmt || src.cams != p.ncams || (src.is_surf() && src.pitch != p.src_pitch)) return hipErrorInvalidValue;
     const size_t frame_bytes = frame_bytes_of(p.fw, p.fh, src.fmt);
     const unsigned bpf = (unsigned)(p.n_groups + 256 * kLumTrips - 1) / (256 * kLumTrips);
     for_each_chunk(batch, [&](int b0, int nb) {
         const FrameSource fr = src.from(b0, p.fw, p.fh);
-        if (src.yuv422())   // (k_lum_groups_yuv422: bevwarp_yuv422.hip)
+        if (lay == kLayoutYuv422)   // (k_lum_groups_yuv422: bevwarp_yuv422.hip)
             yuv422_launch_lum_groups(st, dim3(xcd_frame_grid(bpf, (unsigned)nb)), fr.packed, d_scratch + (size_t)b0 * p.compact_stride, src.set_bytes(p.fw, p.fh),
                                      p.compact_stride, (uint32_t)frame_bytes, static_cast<const uint32_t *>(groups), p.n_groups, d_deltas + (size_t)b0 * 4,
                                      d_tab, bpf, (uint32_t)nb, yuv422_order(src.fmt));
-        else with_input(src.nv12(), src.is_surf(), [&](auto in) {
-            hipLaunchKernelGGL((k_lum_groups<decltype(in)::nv12, decltype(in)::surf>), dim3(xcd_frame_grid(bpf, (unsigned)nb)), dim3(256), 0, st, fr.packed,
+        else with_layout(lay, [&](auto in) {
+            hipLaunchKernelGGL((k_lum_groups<in>), dim3(xcd_frame_grid(bpf, (unsigned)nb)), dim3(256), 0, st, fr.packed,
                                d_scratch + (size_t)b0 * p.compact_stride, src.set_bytes(p.fw, p.fh), p.compact_stride, (uint32_t)frame_bytes,
                                static_cast<const uint32_t *>(groups), p.n_groups, d_deltas + (size_t)b0 * 4, d_tab, bpf, (uint32_t)nb, fr.surf);
         });

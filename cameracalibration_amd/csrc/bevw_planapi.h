@@ -2,7 +2,7 @@
 // entry points with their arguments (FrameSource, PlanStep).  No kernels: the plan kernels (bevw_plan.h, bevw_unit.h) are compiled in
 // bevwarp_plan.hip alone, which defines every function declared here.  Every plan_* function that returns an int returns a BEVW_* status and leaves its message in bevw_last_error().
 #pragma once
-#include "bevw_device.h"   // Nv12Surface, HsvTables, SrcFormat, frame_bytes_of
+#include "bevw_device.h"   // Nv12Surface, HsvTables, SrcFormat, SrcLayout, frame_bytes_of
 #include "bevw_host.h"
 
 namespace bevw {
@@ -37,13 +37,12 @@ struct FrameSource {
     }
 };
 
-// What a group list addresses.  Every list of the plan -- the units' group lists and the sampled groups of the balance schedule -- exists once
-// per layout of the memory it is read against: packed BGR, packed NV12, NV12 surfaces at Plan::src_pitch, packed 4:2:2, the compact scratch
-// (DESIGN.md section 8 has the table: what a slot holds, when a list is made, when it is missing).  A missing list is nullptr, which sends
-// the step to the per-tap kernel and is never an error.
-// kLayoutGray: the one-channel frames of a remapper (SrcFormat::GRAY), 1 byte per texel.  It stands behind kSrcLayouts, the layouts of
-// three-channel sources: the units' list alone, no sampled list (no balance schedule), and routed by the format alone.
-enum SrcLayout { kLayoutBGR = 0, kLayoutNV12, kLayoutSurf, kLayoutYuv422, kLayoutCompact, kSrcLayouts, kLayoutGray = kSrcLayouts, kPlanLayouts };
+// What a group list addresses (SrcLayout, bevw_device.h).  Every list of the plan -- the units' group lists and the sampled groups of the
+// balance schedule -- exists once per layout of the memory it is read against: packed BGR, packed NV12, NV12 surfaces at Plan::src_pitch,
+// packed 4:2:2, the compact scratch (DESIGN.md section 8 has the table: what a slot holds, when a list is made, when it is missing).  A
+// missing list is nullptr, which sends the step to the per-tap kernel and is never an error.
+// kLayoutGray: the one-channel frames of a remapper (SrcFormat::GRAY), 1 byte per texel: the units' list alone, no sampled list (no balance
+// schedule), and routed by the format alone.
 
 // a compiled tile plan: its device buffers and the geometry they were built for (plan_build / plan_build_wide)
 struct Plan {

@@ -844,14 +844,11 @@ __device__ __forceinline__ void unit_store_dword(uint32_t v, __amdgpu_buffer_rsr
     if (streaming) __builtin_amdgcn_raw_buffer_store_b32(v, ro, off, 0, kPairStreamAux);
     else __builtin_amdgcn_raw_buffer_store_b32(v, ro, off, 0, kPairStoreAux);
 }
-// NV12: the frames are NV12 frame sets (bevw_set_input_format) and a.un_gsrc holds two offsets per group slot (unit_gsrc_nv12); the group
-// is fetched as two 8-byte loads and converted to BGR where it lands (pair_convert_nv12).  The patch, the plan entries, the interpolation and
-// the stores are the BGR kernel's.  (The balance schedule's units read the compact scratch, which is BGR: no NV12 variant with SUMS.)
-// OUT_NV12: a.out holds NV12 images (bevw_set_output_format; a.pitch % 4 == 0): each lane converts its final quad (nv12_quad, after the car)
-// and stores one Y dword and, on even rows, one U / V dword -- the chroma of the two 2 x 2 blocks whose top-left pixels it holds.  Quads start
-// at x % 4 == 0 (unit left edges and the skew are multiples of 4), so no unit needs another unit's pixels and the plan is the BGR one.
-// The 16-byte store format does not apply (a quad is 4 bytes of Y).  ooff_masked holds the quad's Y offset; the car (BGR) is read at 3 times it.
-// SURF (with NV12): the frames are NV12 surfaces -- a.surf[frame set][camera] = the two plane pointers, rows of a.src_pitch bytes -- and
+// SRC: the layout of the frames (SrcLayout) and of the group list a.un_gsrc.  The patch, the plan entries, the interpolation and the stores are
+// the BGR kernel's whatever it is.  (The balance schedule's units read the compact scratch, which is BGR: SUMS with kLayoutBGR only.)
+// kLayoutNV12: a.un_gsrc holds two offsets per group slot (unit_gsrc_nv12); the group is fetched as two 8-byte loads and converted to BGR where
+// it lands (pair_convert_nv12).
+// kLayoutSurf: the frames are NV12 surfaces -- a.surf[frame set][camera] = the two plane pointers, rows of a.src_pitch bytes -- and
 // a.un_gsrc holds offsets inside the camera's own planes with the camera in the low bits (unit_gsrc_surf).  A unit samples one camera or
 // two, and its group slots are dealt in ascending frame-set order (unit_gsrc_surf verifies both): a wave's lanes name camera A, or -- from
 // one lane of one round on -- camera B.  Per FRAME the wave reads the two cameras' plane pointers from the table with two scalar loads
@@ -861,17 +858,19 @@ __device__ __forceinline__ void unit_store_dword(uint32_t v, __amdgpu_buffer_rsr
 // once; the one mixed instruction of a unit is issued twice, under the execution masks lane < split and lane >= split: the masked-off lanes
 // issue no request, so every group is requested exactly once, and nothing is kept per lane beyond the two offsets the packed NV12 kernel
 // keeps.  (Option (b) of the three in DESIGN.md "NV12 surfaces".)
-// P422 (not with NV12): the frames are packed 4:2:2 frame sets (YUYV / UYVY) and a.un_gsrc holds one offset per group slot (unit_gsrc_yuv422):
+// kLayoutYuv422: the frames are packed 4:2:2 frame sets (YUYV / UYVY) and a.un_gsrc holds one offset per group slot (unit_gsrc_yuv422):
 // the group is ONE 16-byte load through the frame set's range-checked descriptor, as for BGR, split by the byte order's selectors
 // (a.yuv422: a kernel argument, so both orders run the same kernel) and converted where it lands (pair_convert_yuv422).
-template <bool BLEND, bool SUMS, int NQ, int GR, int NCON, bool WIDE = false, bool NV12 = false, bool OUT_NV12 = false, bool SURF = false, bool P422 = false>
+// OUT_NV12: a.out holds NV12 images (bevw_set_output_format; a.pitch % 4 == 0): each lane converts its final quad (nv12_quad, after the car)
+// and stores one Y dword and, on even rows, one U / V dword -- the chroma of the two 2 x 2 blocks whose top-left pixels it holds.  Quads start
+// at x % 4 == 0 (unit left edges and the skew are multiples of 4), so no unit needs another unit's pixels and the plan is the BGR one.
+// The 16-byte store format does not apply (a quad is 4 bytes of Y).  ooff_masked holds the quad's Y offset; the car (BGR) is read at 3 times it.
+template <bool BLEND, bool SUMS, int NQ, int GR, int NCON, bool WIDE = false, SrcLayout SRC = kLayoutBGR, bool OUT_NV12 = false>
 __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk, uint32_t unit, uint8_t *lds, uint4 *wave_sums = nullptr)
 {
-    static_assert(!SURF || NV12, "surfaces are NV12");
-    static_assert(!(P422 && (NV12 || SUMS || WIDE)), "4:2:2 units: table projection, raw frames");
     static_assert(NQ >= 1 && NQ <= kUnitMaxNQ && GR >= 1 && GR <= kUnitMaxGR && (NCON == 1 || NCON == 2), "unit class");
     static_assert(!(WIDE && SUMS), "wide plans carry no channel sums");
-    static_assert(!(NV12 && (SUMS || WIDE)), "NV12 units: table projection, raw frames");
+    static_assert(!(Src<SRC>::yuv && (SUMS || WIDE)), "NV12 and 4:2:2 units: table projection, raw frames");
     static_assert(!(OUT_NV12 && (SUMS || WIDE)), "NV12 images: table projection, no channel sums (balance stores BGR for the gain pass)");
     constexpr int kFPart = NCON == 2 ? 3 : 1;          // narrow part: the entries of each contributor (+ the blend weights)
     constexpr int kParts = kFPart + (WIDE ? NCON : 0); // uint4 per lane and quad slot in the plan
@@ -995,7 +994,7 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
     }
 #pragma unroll
     for (int r = 0; r < GR; ++r) {
-        if (NV12) {
+        if (Src<SRC>::nv12) {
             const pair_u32x2 g = once_load<BEVW_PLAN_NT>(reinterpret_cast<const pair_u32x2 *>(a.un_gsrc) + ((size_t)gs_off + r) * kUnitThreads + threadIdx.x);
             gs[r] = g.x;
             gc[r] = g.y;
@@ -1003,11 +1002,11 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
             gs[r] = once_load<BEVW_PLAN_NT>(a.un_gsrc + ((size_t)gs_off + r) * kUnitThreads + threadIdx.x);
         }
     }
-    // SURF: the wave's two cameras -- A = its first lane's, B = the other one its lanes name (B == A: one camera) -- and per round r the
+    // surfaces: the wave's two cameras -- A = its first lane's, B = the other one its lanes name (B == A: one camera) -- and per round r the
     // first lane of camera B (split_bits byte r; 64: the round is all A, 0: all B).  A unit's list names at most two cameras, in ascending
     // order (unit_gsrc_surf checks it), so "lane < split" is "camera A" in every round.  The camera bits leave the lanes' offsets here.
     uint32_t cam_a = 0, cam_b = 0, split_bits = 0;
-    if (SURF) {
+    if (Src<SRC>::surf) {
         {
             const unsigned long long act = __builtin_amdgcn_ballot_w64(gs[0] != kPairNoGroup);
             cam_a = cam_b = (uint32_t)__builtin_amdgcn_readlane((int)unit_surf_cam(gc[0]), act ? (int)__builtin_ctzll(act) : 0);
@@ -1026,8 +1025,8 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
         cam_b = __builtin_amdgcn_readfirstlane(cam_b);
         split_bits = __builtin_amdgcn_readfirstlane(split_bits);
     }
-    const uint32_t y_plane = (uint32_t)a.src_pitch * (uint32_t)a.fh, uv_plane = y_plane / 2;   // SURF: bytes of a surface's planes
-    // SURF: the plane pointers of cameras A and B of ONE frame set, in scalar registers: sp[0..3] = A's Y and U / V pointer, sp[4..7] = B's.
+    const uint32_t y_plane = (uint32_t)a.src_pitch * (uint32_t)a.fh, uv_plane = y_plane / 2;   // surfaces: bytes of their planes
+    // surfaces: the plane pointers of cameras A and B of ONE frame set, in scalar registers: sp[0..3] = A's Y and U / V pointer, sp[4..7] = B's.
     // The table is read through the constant address space with a wave-uniform index: two s_load_dwordx4 per frame, nothing per round or
     // lane.  They are fetched one frame AHEAD of the group loads that use them (behind the stores of the frame before), so no vector load
     // ever waits for a scalar load.
@@ -1054,7 +1053,7 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
     static_assert(D >= 2 && D % 2 == 0, "the patch halves alternate with the ring");
     pair_u32x4 pf[D][GR];
     auto issue = [&](int b, int ring) {
-        if constexpr (SURF) {
+        if constexpr (Src<SRC>::surf) {
             // (sp holds the pointers of frame b: surf_fetch ran a frame earlier)
             __amdgpu_buffer_rsrc_t ry, rc;
 #pragma unroll
@@ -1086,7 +1085,7 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), 0, (uint32_t)set_bytes, kBufferWord3);
 #pragma unroll
         for (int r = 0; r < GR; ++r) {
-            if (NV12) {
+            if (Src<SRC>::nv12) {
                 // Y bytes x .. x+7 and U / V bytes x .. x+7 of the group (x .. x+4 / x+5 are used).  The last group of a frame's last chroma
                 // row reaches 4 bytes past the frame, and for the last camera past the frame set: those bytes are never used (texel x+4 lies
                 // outside the frame, so no unit pixel samples it: such footprints are frame-border tiles of the per-tap kernel), and the
@@ -1095,7 +1094,7 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
                 const pair_u32x2 cv = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)gc[r], 0, kPairLoadAux);
                 pf[ring][r] = pair_u32x4{yv.x, yv.y, cv.x, cv.y};
             } else {
-                // (P422: texels x .. x+7, of which x .. x+4 are used.  A row's last group reaches 8 bytes into the next row, the last group of
+                // (packed 4:2:2: texels x .. x+7, of which x .. x+4 are used.  A row's last group reaches 8 bytes into the next row, the last group of
                 // the set's last row 8 bytes past the set: two whole dwords outside the descriptor -- zeros, no memory touched -- and texel
                 // x+4 of such a group is never sampled, by the argument of the NV12 comment above.)
                 pf[ring][r] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)gs[r], 0, kPairLoadAux);
@@ -1106,8 +1105,8 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
 #pragma unroll
         for (int r = 0; r < GR; ++r) {
             uint4 A, B;
-            if (NV12) pair_convert_nv12(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, gs[r] != kPairNoGroup, A, B);
-            else if (P422) pair_convert_yuv422(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, a.yuv422, gs[r] != kPairNoGroup, A, B);
+            if (Src<SRC>::nv12) pair_convert_nv12(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, gs[r] != kPairNoGroup, A, B);
+            else if (Src<SRC>::p422) pair_convert_yuv422(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, a.yuv422, gs[r] != kPairNoGroup, A, B);
             else pair_convert(pf[ring][r].x, pf[ring][r].y, pf[ring][r].z, pf[ring][r].w, A, B);
             uint4 *sp = reinterpret_cast<uint4 *>(lds + (DB ? (ring & 1) * kPatch : 0)) + (r * kUnitThreads + (int)threadIdx.x) * 2;
             sp[0] = A;
@@ -1215,7 +1214,7 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
                 else store_slot(j, d[j][0], d[j][1], d[j][2], ro);
             }
         }
-        if constexpr (SURF) surf_fetch(b + D + 1);   // the pointers of the frame whose groups the NEXT step issues
+        if constexpr (Src<SRC>::surf) surf_fetch(b + D + 1);   // the pointers of the frame whose groups the NEXT step issues
         block_lds_barrier();       // DB: half[ring ^ 1] complete for everybody, half[ring] free for frame b+2; else: the patch is free
         if (SUMS && wave == 0 && lane < 3 && b < b_end) {
             // (slot ring & 1 is written again in frame b + 2, behind the barrier of frame b + 1, which this wave passes after these reads)
@@ -1226,10 +1225,10 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
 #endif
 #pragma unroll
     for (int u = 0; u < D; ++u) {
-        if constexpr (SURF) surf_fetch(b_begin + u);
+        if constexpr (Src<SRC>::surf) surf_fetch(b_begin + u);
         issue(b_begin + u, u);
     }
-    if constexpr (SURF) surf_fetch(b_begin + D);
+    if constexpr (Src<SRC>::surf) surf_fetch(b_begin + D);
 #ifndef BEVW_EXPERIMENT_FRAME
     if (DB) {
         land(0);
@@ -1245,14 +1244,14 @@ __device__ __forceinline__ void plan_unit_run(const PlanArgs &a, uint32_t chunk,
 
 // block -> (chunk, unit) of the list of ALL units in the partition's own (spatial) order, class in bits 28..31: neighbouring units run
 // at the same time on the same XCD, whatever their class, so the two halves of a sector that two units share meet in the L2
-template <bool BLEND, bool SUMS, bool NV12, bool OUT_NV12 = false, bool SURF = false, bool P422 = false>
+template <bool BLEND, bool SUMS, SrcLayout SRC, bool OUT_NV12 = false>
 __device__ __forceinline__ void plan_unit_any(const PlanArgs &a, uint32_t block_id, uint8_t *lds, uint4 *wave_sums)
 {
     uint32_t chunk, group;
     if (!plan_block_map(a, block_id, chunk, group)) return;
     if ((int)group >= a.nlist) return;
     const uint32_t e = __builtin_amdgcn_readfirstlane(a.tile_list[group]), unit = e & 0x0fffffffu;
-#define BEVW_UNIT_CASE(C) case C: plan_unit_run<BLEND, SUMS, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C], false, NV12, OUT_NV12, SURF, P422>(a, chunk, unit, lds, wave_sums); break;
+#define BEVW_UNIT_CASE(C) case C: plan_unit_run<BLEND, SUMS, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C], false, SRC, OUT_NV12>(a, chunk, unit, lds, wave_sums); break;
     switch (e >> 28) {
         BEVW_UNIT_CASE(0) BEVW_UNIT_CASE(1) BEVW_UNIT_CASE(2) BEVW_UNIT_CASE(3)
         // class 4 (two quads per lane, two contributors): with float blend weights (rounds 3 - 5) its blend variant needed 177 .. 197 VGPRs and
@@ -1262,7 +1261,7 @@ __device__ __forceinline__ void plan_unit_any(const PlanArgs &a, uint32_t block_
 #if !BEVW_UNIT_NO_BIG   // (experiment builds without the (4, 4) class: every other class fits 128 VGPRs = 4 waves per SIMD; plans then need BEVW_UNIT_BIG=0)
         BEVW_UNIT_CASE(7)
 #endif
-        default: plan_unit_run<BLEND, SUMS, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6], false, NV12, OUT_NV12, SURF, P422>(a, chunk, unit, lds, wave_sums); break;
+        default: plan_unit_run<BLEND, SUMS, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6], false, SRC, OUT_NV12>(a, chunk, unit, lds, wave_sums); break;
     }
 #undef BEVW_UNIT_CASE
 }
@@ -1279,44 +1278,44 @@ __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_
 #ifdef BEVW_EXPERIMENT_TRACE_BEGIN
     BEVW_EXPERIMENT_TRACE_BEGIN();
 #endif
-    plan_unit_any<BLEND, SUMS, false>(a, blockIdx.x, patch, wave_sums);
+    plan_unit_any<BLEND, SUMS, kLayoutBGR>(a, blockIdx.x, patch, wave_sums);
 #ifdef BEVW_EXPERIMENT_TRACE_END
     BEVW_EXPERIMENT_TRACE_END(a)
 #endif
 }
 
-// NV12 frame sets (bevw_set_input_format): the same launch over the NV12 instantiation of plan_unit_run -- no channel sums (the balance
+// NV12 frame sets (bevw_set_input_format): the same launch over the kLayoutNV12 instantiation of plan_unit_run -- no channel sums (the balance
 // schedule's units read the BGR compact scratch).  A kernel name of its own keeps k_plan_units the four BGR instantiations.
 template <bool BLEND>
 __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_nv12(PlanArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
-    plan_unit_any<BLEND, false, true>(a, blockIdx.x, patch, nullptr);
+    plan_unit_any<BLEND, false, kLayoutNV12>(a, blockIdx.x, patch, nullptr);
 }
 
 // NV12 BEV images (bevw_set_output_format): the same launch over the OUT_NV12 instantiation of plan_unit_run, for BGR or NV12 frame sets
-// (IN_NV12: a.un_gsrc holds the NV12 group lists).  No channel sums: the balance modes store the BGR pre-gain image and convert in the gain
+// (SRC: a.un_gsrc holds that layout's group lists).  No channel sums: the balance modes store the BGR pre-gain image and convert in the gain
 // pass.  Named apart from k_plan_units (the four BGR instantiations) and k_units_nv12.
-template <bool BLEND, bool IN_NV12>
+template <bool BLEND, SrcLayout SRC>
 __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_out_nv12(PlanArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
-    plan_unit_any<BLEND, false, IN_NV12, true>(a, blockIdx.x, patch, nullptr);
+    plan_unit_any<BLEND, false, SRC, true>(a, blockIdx.x, patch, nullptr);
 }
 
-// NV12 surfaces (bevw_run_surfaces_device): the same launch over the SURF instantiation of plan_unit_run, writing BGR (k_units_surf) or NV12
+// NV12 surfaces (bevw_run_surfaces_device): the same launch over the kLayoutSurf instantiation of plan_unit_run, writing BGR (k_units_surf) or NV12
 // images (k_units_out_surf).  Names of their own: k_plan_units stays the four BGR instantiations, k_units_nv12 / k_units_out_nv12 the packed ones.
 template <bool BLEND>
 __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_surf(PlanArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
-    plan_unit_any<BLEND, false, true, false, true>(a, blockIdx.x, patch, nullptr);
+    plan_unit_any<BLEND, false, kLayoutSurf, false>(a, blockIdx.x, patch, nullptr);
 }
 template <bool BLEND>
 __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_out_surf(PlanArgs a)
 {
     __shared__ __attribute__((aligned(16))) uint8_t patch[kUnitMaxGroups * 32];
-    plan_unit_any<BLEND, false, true, true, true>(a, blockIdx.x, patch, nullptr);
+    plan_unit_any<BLEND, false, kLayoutSurf, true>(a, blockIdx.x, patch, nullptr);
 }
 
 // wide plans (analytic projection): every unit class in one launch, partition order, as plan_unit_any

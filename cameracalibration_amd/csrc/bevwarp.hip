@@ -553,8 +553,8 @@ static int remap_launch(hipStream_t st, const FrameSource &src, int sw, int sh, 
         else if (src.yuv422())   // (k_remap_lut_yuv422: bevwarp_yuv422.hip)
             yuv422_launch_remap_lut(st, dim3((dw + 255) / 256, dh, nb), out_nv12, fr.packed, sw, sh, m1, m2, dw, dh,
                                     d_dst + (size_t)b0 * image_bytes_of(dw, dh, out_nv12), ties_even, yuv422_order(src.fmt));
-        else with_formats(src.nv12(), src.is_surf(), out_nv12, [&](auto in, auto on) {
-            hipLaunchKernelGGL((k_remap_lut<decltype(in)::nv12, on, decltype(in)::surf>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, fr.packed, sw, sh,
+        else with_layout_out(frames_layout(src.fmt, src.is_surf()), out_nv12, [&](auto in, auto on) {
+            hipLaunchKernelGGL((k_remap_lut<in, on>), dim3((dw + 255) / 256, dh, nb), dim3(256), 0, st, fr.packed, sw, sh,
                                m1, m2, dw, dh, d_dst + (size_t)b0 * image_bytes_of(dw, dh, on), ties_even, fr.surf, fr.pitch);
         });
     });
@@ -1045,9 +1045,9 @@ static int stitch_per_pixel(bevw_handle *h, const FrameSource &src, int batch, c
             yuv422_launch_stitch_pp(h->stream, grid, c.blend != 0, c.balance != 0, out_nv12, fr.packed, c.frame_width, c.frame_height, T, c.bev_width,
                                     c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car, chs ? chs + b0 * 3 : nullptr, o,
                                     h->compat[BEVW_COMPAT_REMAP], yuv422_order(src.fmt));
-        else with_formats(src.nv12(), src.is_surf(), out_nv12, [&](auto in, auto on) {
+        else with_layout_out(frames_layout(src.fmt, src.is_surf()), out_nv12, [&](auto in, auto on) {
             auto launch = [&](auto bl, auto ba) {
-                hipLaunchKernelGGL((k_stitch_pp<bl, ba, decltype(in)::nv12, on, decltype(in)::surf>), grid, block, 0, h->stream, fr.packed, c.frame_width,
+                hipLaunchKernelGGL((k_stitch_pp<bl, ba, in, on>), grid, block, 0, h->stream, fr.packed, c.frame_width,
                                    c.frame_height, T, c.bev_width, c.bev_height, deltas ? deltas + b0 * 4 : nullptr, tab, d_car,
                                    chs ? chs + b0 * 3 : nullptr, o, h->compat[BEVW_COMPAT_REMAP], fr.surf, fr.pitch);
             };
@@ -1162,8 +1162,8 @@ static int vsum_launch(hipStream_t st, FrameSource src, int nframes, int fw, int
         if (src.yuv422())   // (k_vsum_yuv422: bevwarp_yuv422.hip; its 16-byte loads)
             yuv422_launch_vsum(st, dim3(bpf, nf), fr.packed, frame_bytes, (frame_bytes % 16 == 0 && (((uintptr_t)fr.packed) & 15u) == 0) ? 1 : 0,
                                d_vsums + (size_t)f0 * per_frame, part_stride, yuv422_order(src.fmt));
-        else with_input(src.nv12(), src.is_surf(), [&](auto in) {
-            hipLaunchKernelGGL((k_vsum<decltype(in)::nv12, decltype(in)::surf>), dim3(bpf, nf), dim3(256), 0, st, fr.packed, frame_bytes, vec_ok,
+        else with_layout(frames_layout(src.fmt, src.is_surf()), [&](auto in) {
+            hipLaunchKernelGGL((k_vsum<in>), dim3(bpf, nf), dim3(256), 0, st, fr.packed, frame_bytes, vec_ok,
                                d_vsums + (size_t)f0 * per_frame, part_stride, src.nv12() ? fw : 0, fr.surf, fr.pitch);
         });
     });

@@ -1,5 +1,5 @@
 // Host-only check of the group loads of the unit kernel's SURFACE instantiation (cameracalibration_amd/csrc/bevw_unit.h:
-// plan_unit_run<.., SURF>, unit_gsrc_surf) -- runs without a GPU.  The plan compiler (unit_compile) builds the units of real tables; their
+// plan_unit_run<.., kLayoutSurf>, unit_gsrc_surf) -- runs without a GPU.  The plan compiler (unit_compile) builds the units of real tables; their
 // group lists are translated for packed NV12 frame sets (unit_gsrc_nv12) and for surfaces with a row pitch (unit_gsrc_surf).  Random NV12
 // frames are laid out twice: packed, and as surfaces inside an arena whose gaps and padding columns hold other bytes.  For every unit,
 // round and lane the program walks the kernel's steps -- camera A / split / camera B of the wave's 64 lanes, one descriptor per plane

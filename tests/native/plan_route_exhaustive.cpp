@@ -46,7 +46,7 @@ static int check_route(const RouteIn &in)
     if (yuv422_units) { list = kLayoutYuv422; set_stride = (uint32_t)(frame_bytes_of(kFW, kFH, in.fmt) * kCams); }
     // the unit kernel's <NV12, SURF, P422> as plan_launch_units was handed them
     const bool k_nv12 = nv12_units, k_surf = surf && nv12_units, k_yuv422 = yuv422_units;
-    // the per-tap kernel: k_stitch_plan_yuv422, or with_formats(p.nv12(), surf, ..) -> with_input: surfaces first
+    // the per-tap kernel: k_stitch_plan_yuv422, or with_layout_out(rt.frames, ..) on the three other frame layouts
     const SrcLayout tap = yuv422 ? kLayoutYuv422 : surf ? kLayoutSurf : nv12 ? kLayoutNV12 : kLayoutBGR;
     const bool lum = in.balance || compact, tap_sums = in.balance || in.sums;
     // ---- plan_route against it ----

@@ -1,6 +1,6 @@
 """The format dispatch of the host code on the branches only an environment switch reaches:
 
-  BEVW_BAL_MODE=0     balance as the luminance round trip per tap: k_stitch_plan<BLEND, LUM, SUMS, NV12 | SURF>
+  BEVW_BAL_MODE=0     balance as the luminance round trip per tap: k_stitch_plan<BLEND, LUM, SUMS, kLayoutNV12 | kLayoutSurf, ..>
   BEVW_PLAN_UNITS=0   the plan's per-tap kernel over every tile, no unit kernel
   BEVW_REMAP_PLAN=0   remap_launch (k_remap_lut) on an aligned remapper that would otherwise run its plan; the per-pixel stitch is untouched
 

@@ -168,9 +168,10 @@ def test_surface_kernels_have_names_of_their_own(tmp_path):
     assert len({k for k in plan if "k_units_surf" in k}) == 2 and len({k for k in plan if "k_units_out_surf" in k}) == 2
     assert len({k for k in plan if "k_plan_units" in k}) == 4
     assert not {k for k in main if "k_units" in k}
-    # the last template argument (SURF) set: ...Lb1EEEv in the mangled name
-    assert {k for k in main if "k_stitch_pp" in k and "Lb1EEEv" in k}
-    assert {k for k in main if "k_remap_lut" in k and "Lb1EEEv" in k} and {k for k in main if "k_vsum" in k and "ILb1ELb1EE" in k}
+    # the layout argument is kLayoutSurf (SrcLayout 2): ...LNS_9SrcLayoutE2E... in the mangled name
+    surf = "LNS_9SrcLayoutE2E"
+    assert {k for k in main if "k_stitch_pp" in k and surf in k}
+    assert {k for k in main if "k_remap_lut" in k and surf in k} and {k for k in main if "k_vsum" in k and surf in k}
 
 
 @needs_hipcc
