@@ -105,7 +105,7 @@ class _Engine:
     """Owns one bevw_handle (4 cameras + masks on the device)."""
 
     def __init__(self, rig, blend, balance, device, schedule, output_pitch=0, input_format=_ffi.INPUT_BGR, output_format=_ffi.OUTPUT_BGR,
-                 input_pitch=0):
+                 input_pitch=0, channels=3):
         _ffi.require_device()
         self.cfg = _snapshot_config(blend, balance, device, schedule)
         h = C.c_void_p()
@@ -122,6 +122,8 @@ class _Engine:
                 check(lib().bevw_set_input_pitch(self.h, int(input_pitch)))
             if output_format != _ffi.OUTPUT_BGR:
                 check(lib().bevw_set_output_format(self.h, int(output_format)))
+            if channels != 3:
+                check(lib().bevw_set_channels(self.h, int(channels)))
             check(lib().bevw_build(self.h))
         except Exception:
             self.close()
@@ -299,7 +301,7 @@ class BevGenerator:
 
     def __init__(self, blend=args.BLEND_FLAG, balance=args.BALANCE_FLAG, *, rig=None, device=0,
                  schedule=_ffi.SCHED_AUTO, projection='lut', output_pitch='auto', input_format='bgr', output_format='bgr',
-                 input_pitch=None):
+                 input_pitch=None, channels=3):
         """blend / balance: as in the reference (surroundBEV.py:283).  Additive keywords: rig ({name: (K, D, H)} instead of the
         data directory), device, schedule, and projection -- 'lut' (default: the reference's table-driven path, bit-exact against
         the oracle) 'analytic' (inverse homography + fisheye model evaluated per frame and pixel in fp64, no tables; not the
@@ -322,10 +324,23 @@ class BevGenerator:
         BW and BH and the 'lut' projection; combines with either input_format; jpeg() / jpeg_stream() need BGR output.
         input_pitch -- with input_format='nv12': bytes between the rows of the decoder surfaces run_surfaces() / run_surface_table() read in
         place (None: FW; else a multiple of 4 >= FW; see bevw_set_input_pitch in include/bevwarp.h).  With a pitch other than FW the
-        packed entry points (__call__, batch, run_device) are refused."""
+        packed entry points (__call__, batch, run_device) are refused.
+        channels -- 3 (default) or 1: single-channel frames (mono, NIR, thermal cameras; a grey perception network).  With 1, __call__ takes
+        uint8 (FH, FW) frames and an optional (BH, BW) car and returns (BH, BW); batch takes [B, 4, FH, FW] and returns [B, BH, BW];
+        run_device reads and writes one byte per pixel (``in_set_bytes``, ``out_pitch``, ``out_image_bytes`` follow).  The result is what the
+        reference's __call__ gives when its cv2 calls are made on (H, W) arrays: every channel of the three-channel generator on the
+        replicated frames (see bevw_set_channels in include/bevwarp.h).  Needs balance=False, 'bgr' in and out, no input_pitch and the
+        'lut' projection; jpeg() / jpeg_stream() raise."""
         self.init_args()
         formats = _ffi.INPUT_FORMATS
         _ffi.input_format(input_format)   # (an unknown keyword is refused before any device call)
+        self.channels = _ffi.channels(channels)
+        if self.channels == 1:   # (what bevw_set_channels refuses, before any device call)
+            for bad, what in ((balance, "balance (the balance chain is HSV and three channel means)"), (input_format != 'bgr', "input_format=%r" % (input_format,)),
+                              (output_format != 'bgr', "output_format=%r" % (output_format,)), (input_pitch is not None, "an input_pitch"),
+                              (projection != 'lut', "projection=%r" % (projection,))):
+                if bad:
+                    raise Exception("channels=1 is not available with {}".format(what))
         in_pitch = _ffi.check_input_pitch(input_pitch, args.FRAME_WIDTH, input_format == 'nv12')
         if rig is None:
             self.cameras = [Camera('front'), Camera('back'), Camera('left'), Camera('right')]
@@ -348,11 +363,11 @@ class BevGenerator:
         rig_kdh = [(c.camera_mat, c.dist_coeff, c.homography) for c in self.cameras]
         fmts = (formats[input_format], out_formats[output_format])
         try:
-            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, pitch, *fmts, in_pitch)
+            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, pitch, *fmts, in_pitch, self.channels)
         except _ffi.BevwError:
             if not (auto and pitch != _ffi.PITCH_DENSE):
                 raise
-            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, _ffi.PITCH_DENSE, *fmts, in_pitch)   # a rig the tile plan cannot serve
+            self._engine = _Engine(rig_kdh, blend, balance, device, schedule, _ffi.PITCH_DENSE, *fmts, in_pitch, self.channels)   # a rig the tile plan cannot serve
         self.in_pitch = int(lib().bevw_input_pitch(self._engine.h))   # bytes between the rows of an NV12 surface (run_surfaces)
         self.out_pitch = int(lib().bevw_output_pitch(self._engine.h))   # pixels per row of run_device()'s output images
         modes = {'lut': _ffi.PROJ_LUT, 'analytic': _ffi.PROJ_ANALYTIC, 'analytic_f32': _ffi.PROJ_ANALYTIC_F32}
@@ -385,6 +400,8 @@ class BevGenerator:
     def _frame_shape(self):
         """Shape of one camera frame this generator takes: (FH, FW, 3) for 'bgr', (FH*3//2, FW) for 'nv12', (FH, FW, 2) for 'yuyv' / 'uyvy'."""
         c = self._engine.cfg
+        if self.channels == 1:
+            return (c.frame_height, c.frame_width)
         return _ffi.frame_shape(self.input_format, c.frame_height, c.frame_width)
 
     def _image_shape(self):
@@ -392,12 +409,28 @@ class BevGenerator:
         c = self._engine.cfg
         if self.output_format == 'nv12':
             return (c.bev_height * 3 // 2, c.bev_width)
+        if self.channels == 1:
+            return (c.bev_height, c.bev_width)
         return (c.bev_height, c.bev_width, 3)
+
+    def _as_car(self, car):
+        """The car sprite as the generator takes it: uint8 (BH, BW, 3), or (BH, BW) with channels=1."""
+        if self.channels == 1:
+            car = np.ascontiguousarray(car)
+            if car.dtype != np.uint8 or car.ndim != 2:
+                raise Exception("car must be uint8 [BH, BW] (channels=1), got {} {}".format(car.dtype, car.shape))
+            return car
+        return _ffi.as_u8_image(car, "car")
 
     # ---- reference call ------------------------------------------------------------------------------------
     def __call__(self, front, back, left, right, car=None):
         c = self._engine.cfg
-        if self.input_format == 'nv12':
+        if self.channels == 1:
+            images = [np.ascontiguousarray(i) for i in (front, back, left, right)]
+            for img in images:
+                if img.dtype != np.uint8 or img.ndim != 2:
+                    raise Exception("camera frame must be uint8 {} (FH, FW) with channels=1, got {} {}".format(self._frame_shape(), img.dtype, img.shape))
+        elif self.input_format == 'nv12':
             images = [np.ascontiguousarray(i) for i in (front, back, left, right)]
             for img in images:
                 if img.dtype != np.uint8 or img.shape != self._frame_shape():
@@ -417,7 +450,7 @@ class BevGenerator:
                                                                                c.frame_width, c.frame_height))
         car_p = None
         if car is not None:
-            car = _ffi.as_u8_image(car, "car")
+            car = self._as_car(car)
             if car.shape[:2] != (c.bev_height, c.bev_width):
                 raise Exception("car must be padded to the BEV size (padding())")
             car_p = ptr(car)
@@ -437,7 +470,7 @@ class BevGenerator:
             raise Exception("frames must be uint8 [B, {}]".format(", ".join(str(n) for n in want)))
         car_p = None
         if car is not None:
-            car = _ffi.as_u8_image(car, "car")
+            car = self._as_car(car)
             if car.shape[:2] != (c.bev_height, c.bev_width):
                 raise Exception("car must be padded to the BEV size (padding())")
             car_p = ptr(car)
@@ -521,6 +554,8 @@ class BevGenerator:
         return files
 
     def _jpeg_needs_bgr(self):
+        if self.channels != 3:
+            raise Exception("jpeg() / jpeg_stream() decode camera files to BGR and encode BGR images: use a BevGenerator with channels=3")
         if self.input_format != 'bgr':
             raise Exception("jpeg() / jpeg_stream() decode camera files to BGR: use a BevGenerator with input_format='bgr'")
         if self.output_format != 'bgr':
@@ -617,7 +652,7 @@ class BevGenerator:
         per pixel ('bgr') or a Y plane and a half-height U / V plane of ``out_pitch`` bytes per row ('nv12': out_pitch * BH * 3 // 2)."""
         if self.output_format == 'nv12':
             return self.out_pitch * self._engine.cfg.bev_height * 3 // 2
-        return self.out_pitch * self._engine.cfg.bev_height * 3
+        return self.out_pitch * self._engine.cfg.bev_height * (1 if self.channels == 1 else 3)
 
     @property
     def in_set_bytes(self) -> int:

@@ -95,6 +95,8 @@ SIGNATURES = {
     "bevw_run_surface_table_device": (_i, [_vp, _vp, _i, _vp, _vp]),
     "bevw_set_output_format": (_i, [_vp, _i]),
     "bevw_output_format": (_i, [_vp]),
+    "bevw_set_channels": (_i, [_vp, _i]),
+    "bevw_channels": (_i, [_vp]),
     "bevw_run_cameras": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bevw_camera_undistort": (_i, [_vp, _i, _vp, _i, _vp]),
     "bevw_camera_warp_homography": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),

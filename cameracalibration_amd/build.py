@@ -2,9 +2,10 @@
 
     python -m cameracalibration_amd.build [--force]
 
-Five translation units -- bevwarp.hip (handles, table builders, tools, the camera-per-GPU exchange), bevwarp_plan.hip (the tile plan
+Six translation units -- bevwarp.hip (handles, table builders, tools, the camera-per-GPU exchange), bevwarp_plan.hip (the tile plan
 and its per-frame kernels), bevwarp_jpeg.hip (the JPEG codec), bevwarp_yuv422.hip (every kernel that reads packed 4:2:2 camera frames:
-FORMAT_UNITS) and bevwarp_gray.hip (every kernel of the one-channel remapper: CHANNEL_UNITS) -- are compiled in parallel into objects under csrc/build/ and linked;
+FORMAT_UNITS), bevwarp_gray.hip (every kernel of the one-channel remapper: CHANNEL_UNITS) and bevwarp_gray_stitch.hip (every kernel of the
+one-channel stitch: STITCH_CHANNEL_UNITS) -- are compiled in parallel into objects under csrc/build/ and linked;
 a unit is recompiled when its source, ANY header under csrc/ or the flag set changed.  The shared object is written next to this file (in-tree: it travels
 to the GPU box with the repo snapshot and is git-ignored).  -ffp-contract=off is REQUIRED: the arithmetic being reproduced has no fused
 multiply-add.
@@ -28,7 +29,9 @@ UNITS = ["bevwarp.hip", "bevwarp_plan.hip", "bevwarp_jpeg.hip"]
 FORMAT_UNITS = ["bevwarp_yuv422.hip"]
 # units that hold the kernels of one channel count: the one-channel remapper (bevw_remapper_set_channels), every kernel named *gray*
 CHANNEL_UNITS = ["bevwarp_gray.hip"]
-ALL_UNITS = UNITS + FORMAT_UNITS + CHANNEL_UNITS
+# ... and the one-channel stitch of a handle (bevw_set_channels): the unit kernel over every class, the per-tap and the per-pixel kernel
+STITCH_CHANNEL_UNITS = ["bevwarp_gray_stitch.hip"]
+ALL_UNITS = UNITS + FORMAT_UNITS + CHANNEL_UNITS + STITCH_CHANNEL_UNITS
 
 
 def _headers():

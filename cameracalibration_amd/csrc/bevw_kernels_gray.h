@@ -1,6 +1,7 @@
 // bevw_kernels_gray.h -- every kernel that reads one-channel frames (bevw_remapper_set_channels: 8UC1 sources and destinations of a
-// remapper), under names of their own.  Included by bevwarp_gray.hip alone, behind bevw_plan.h with BEVW_PLAN_SHARED_ONLY (and by
-// tests/native/gray_emulate.cpp, which runs the __host__ __device__ functions below on a CPU).
+// remapper), under names of their own.  Included by bevwarp_gray.hip, behind bevw_plan.h with BEVW_PLAN_SHARED_ONLY (and by
+// tests/native/gray_emulate.cpp, which runs the __host__ __device__ functions below on a CPU); bevw_kernels_gray_stitch.h, the one-channel
+// stitch of a handle, includes it with BEVW_GRAY_SHARED_ONLY for the lane and device functions alone.
 //
 // The plan is the three-channel remapper's: the same unit partition, the same entries (pair index, two group slots, fx, fy), the same
 // launch order.  What differs is what a group slot holds.  A group is texels 4g .. 4g+4 of one source row; in one channel those are the
@@ -144,6 +145,9 @@ __device__ __forceinline__ void gray_unit_run(const PlanArgs &a, uint32_t chunk,
     }
 }
 
+// BEVW_GRAY_SHARED_ONLY (bevwarp_gray_stitch.hip): this header without its kernels -- the lane functions and device functions only.  A
+// non-template kernel is emitted by every unit that sees it.
+#ifndef BEVW_GRAY_SHARED_ONLY
 // every unit of every class in the partition's own order, one launch per step: plan_unit_any's block map and class switch over the
 // single-contributor classes
 __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_gray(PlanArgs a)
@@ -160,6 +164,7 @@ __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_
     }
 #undef BEVW_GRAY_CASE
 }
+#endif   // BEVW_GRAY_SHARED_ONLY
 
 // ---- the per-tap and per-pixel kernels ------------------------------------------------------------------------------------------------------
 // cv2.remap u8c1, INTER_LINEAR fixed point, BORDER_CONSTANT 0: remap_u8c3_px (bevw_device.h) for one channel, one path for interior and
@@ -178,6 +183,7 @@ __device__ __forceinline__ int remap_u8c1_px(const uint8_t *__restrict__ src, in
     return remap_round10(t[0] * (ax * ay) + t[1] * (fx * ay) + t[2] * (ax * fy) + t[3] * (fx * fy), ties_even);
 }
 
+#ifndef BEVW_GRAY_SHARED_ONLY
 // The per-tap tile kernel on one-channel frames: one wave per 32 x 8 base tile of the list (the tiles no unit owns: footprints on the frame
 // border), lane l owns the pixel quad (l % 8, l / 8), every tap read straight from the frame.  k_stitch_plan's block map and entries; an
 // entry without a contributor gives 0.  Rows of a.pitch == a.bw bytes, a.bw % 4 == 0: one dword store per lane.
@@ -226,5 +232,6 @@ __global__ void __launch_bounds__(256) k_remap_lut_gray(const uint8_t *__restric
     const uint8_t *s = src + (size_t)blockIdx.z * sw * sh;
     dst[(size_t)blockIdx.z * dw * dh + o] = (uint8_t)remap_u8c1_px(s, sw, sh, map1[o * 2], map1[o * 2 + 1], map2[o] & (kQTab2 - 1), ties_even);
 }
+#endif   // BEVW_GRAY_SHARED_ONLY
 
 }  // namespace bevw

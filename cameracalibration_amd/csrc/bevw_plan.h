@@ -27,6 +27,7 @@
 #include "bevw_planapi.h"
 #include "bevw_yuv422.h"
 #include "bevw_gray.h"
+#include "bevw_gray_stitch.h"
 
 namespace bevw {
 
@@ -458,8 +459,9 @@ static inline hipError_t plan_make_lists(Plan &p, SrcLayout lay)
         case kLayoutSurf:   // (a units' list with a unit of more than two cameras is not used: the per-tap kernel then serves every tile)
             return p.src_pitch > 0 && p.fh % 2 == 0 && unit_gsrc_surf(bgr, p.fw, p.fh, p.src_pitch, tr, units ? &p.un_ranges_host : nullptr);
         case kLayoutYuv422: unit_gsrc_yuv422(bgr, p.fw, p.fh, tr); return true;   // (the same list serves both byte orders)
-        case kLayoutGray:   // the units alone, and only single-contributor classes: k_units_gray has no blend (a one-camera plan has no other)
-            if (!units || p.n_un[4] + p.n_un[5] + p.n_un[6] != 0) return false;
+        case kLayoutGray:   // the units alone.  A remapper's plan (one camera): only single-contributor classes -- k_units_gray has no blend (a
+                            // one-camera plan has no other); a handle's: every class (k_stitch_units_gray)
+            if (!units || (p.ncams == 1 && p.n_un[4] + p.n_un[5] + p.n_un[6] != 0)) return false;
             unit_gsrc_gray(bgr, p.fw, p.fh, tr);
             return true;
         default:   // kLayoutCompact: the units alone, and only where the scratch stays below 2^31 bytes per frame set
@@ -643,6 +645,42 @@ static inline hipError_t plan_gray_step(const Plan &p, hipStream_t st, const Pla
     return hipGetLastError();
 }
 
+// One step of a handle's plan on one-channel frames (SrcFormat::GRAY with four cameras: bevw_set_channels): k_stitch_units_gray over every unit
+// of every class, k_stitch_tiles_gray over the base tiles no unit owns (bevwarp_gray_stitch.hip).  Images with rows of p.pitch bytes written in
+// place: whole quads per row (p.pitch % 4 == 0, the caller's own rows: one channel has no padded scratch) and 4-byte aligned `out` and `car`.
+// The sprite stays dense where its rows hold whole quads; else (a pitched handle with bw % 4 != 0) it is copied to the images' pitch.
+static inline hipError_t plan_gray_stitch_step(Plan &p, hipStream_t st, const PlanStep &s, const PlanTuning &tune, const Route &rt)
+{
+    if (!rt.use_units || rt.units != kLayoutGray || p.pitch % 4 != 0 || (p.pitch != p.bw && !p.out_pitched) ||
+        ((((uintptr_t)s.out) | ((uintptr_t)s.car)) & 3u) != 0 || s.balance || s.sums || s.scratch)
+        return hipErrorInvalidValue;   // (the caller runs the per-pixel kernel instead: plan_units_serve and its own checks)
+    hipError_t e;
+    const uint8_t *car = s.car;
+    int car_pitch = p.bw;
+    if (s.car && p.bw % 4 != 0) {
+        const size_t img = (size_t)p.pitch * p.bh;
+        if (!p.pad_car_gray) {
+            if ((e = hipMalloc(&p.pad_car_gray, img)) != hipSuccess) return e;
+            if ((e = hipMemsetAsync(p.pad_car_gray, 0, img, st)) != hipSuccess) return e;
+        }
+        if ((e = hipMemcpy2DAsync(p.pad_car_gray, (size_t)p.pitch, s.car, (size_t)p.bw, (size_t)p.bw, (size_t)p.bh, hipMemcpyDeviceToDevice, st)) != hipSuccess) return e;
+        car = static_cast<const uint8_t *>(p.pad_car_gray);
+        car_pitch = p.pitch;
+    }
+    PlanArgs a = plan_args(p, s.src, s.batch, car, s.out, tune);
+    a.plan = static_cast<const uint2 *>(p.entries); a.hdr = static_cast<const uint32_t *>(p.hdr);
+    a.tile_list = static_cast<const uint32_t *>(p.list_un_all); a.nlist = p.n_un_all; a.ngroups = p.n_un_all;
+    a.set_stride = rt.set_stride;
+    a.un_gsrc = static_cast<const uint32_t *>(p.units[kLayoutGray]);
+    gray_stitch_launch_units(a, car_pitch, s.blend, st);
+    e = hipGetLastError();
+    if (e != hipSuccess || p.n_slow == 0) return e;
+    a.tile_list = static_cast<const uint32_t *>(p.list_slow); a.nlist = p.n_slow; a.ngroups = (p.n_slow + 3) / 4;
+    a.set_stride = 0;
+    gray_stitch_launch_tiles(a, car_pitch, s.blend, st);
+    return hipGetLastError();
+}
+
 // One step of the tile plan on `st` (PlanStep, bevw_planapi.h).
 static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanStep &s, const PlanTuning &tune)
 {
@@ -656,7 +694,7 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
     a.deltas = s.deltas; a.tab = s.tab;
     const bool padded = p.pitch != p.bw, scratch = padded && !p.out_pitched;
     const Route rt = plan_route(plan_route_in(p, s, tune));
-    if (p.fmt == SrcFormat::GRAY) return plan_gray_step(p, st, s, tune, rt);
+    if (p.fmt == SrcFormat::GRAY) return p.ncams == 1 ? plan_gray_step(p, st, s, tune, rt) : plan_gray_stitch_step(p, st, s, tune, rt);   // (a remapper's; a handle's)
     const bool out_nv12 = rt.out_nv12, use_units = rt.use_units;
     if (out_nv12 && (scratch || p.pitch % 4 != 0)) return hipErrorInvalidValue;   // (the caller runs the per-pixel kernel instead)
     if (padded) {

@@ -41,8 +41,8 @@ struct FrameSource {
 // balance schedule -- exists once per layout of the memory it is read against: packed BGR, packed NV12, NV12 surfaces at Plan::src_pitch,
 // packed 4:2:2, the compact scratch (DESIGN.md section 8 has the table: what a slot holds, when a list is made, when it is missing).  A
 // missing list is nullptr, which sends the step to the per-tap kernel and is never an error.
-// kLayoutGray: the one-channel frames of a remapper (SrcFormat::GRAY), 1 byte per texel: the units' list alone, no sampled list (no balance
-// schedule), and routed by the format alone.
+// kLayoutGray: the one-channel frames of a remapper or a handle (SrcFormat::GRAY), 1 byte per texel: the units' list alone, no sampled list
+// (no balance schedule), and routed by the format alone.
 
 // a compiled tile plan: its device buffers and the geometry they were built for (plan_build / plan_build_wide)
 struct Plan {
@@ -57,6 +57,7 @@ struct Plan {
     int pitch = 0;
     bool out_pitched = false;    // the caller's output images have rows of `pitch` pixels themselves (bevw_set_output_pitch): no scratch, no compaction
     void *pad_out = nullptr, *pad_car = nullptr;
+    void *pad_car_gray = nullptr;   // one channel: the car sprite at the images' pitch (a pitched handle with bw % 4 != 0: plan_gray_stitch_step)
     size_t pad_cap = 0;
     int *d_max = nullptr;
     int fw = 0, fh = 0, bw = 0, bh = 0;

@@ -19,6 +19,7 @@
 #include "bevw_planapi.h"
 #include "bevw_yuv422.h"
 #include "bevw_gray.h"
+#include "bevw_gray_stitch.h"
 #include "bevw_comm.h"
 
 using namespace bevw;
@@ -356,7 +357,7 @@ struct EngineCore {
     int cams = 4;                        // frames per set
     int input_format = BEVW_INPUT_BGR, output_format = BEVW_OUTPUT_BGR;
     int in_pitch_request = 0;            // 0: the frame width
-    int channels = 3;                    // 1: 8UC1 frames and images (bevw_remapper_set_channels; BGR in and out, no pitch)
+    int channels = 3;                    // 1: 8UC1 frames and images (bevw_remapper_set_channels, bevw_set_channels; BGR in and out, no input pitch)
     SrcFormat fmt() const { return channels == 1 ? SrcFormat::GRAY : (SrcFormat)input_format; }
     bool nv12() const { return input_format == BEVW_INPUT_NV12; }
     bool yuv422() const { return src_is_yuv422(fmt()); }   // packed 4:2:2: YUYV / UYVY
@@ -969,7 +970,8 @@ struct bevw_handle : EngineCore {
     int compat[BEVW_COMPAT_KEYS] = {1, 1, 0, 0};   // bevw_set_compat values at bevw_build: a handle keeps the arithmetic it was built with
     int pitch_request = BEVW_PITCH_DENSE;   // bevw_set_output_pitch
     int pitch_px = 0;                 // pixels per row of the device-side BEV images (== bev_width unless a pitch was requested)
-    size_t out_image_bytes() const { return image_bytes_of(pitch_px, cfg.bev_height, out_nv12()); }   // one device-side BEV image
+    size_t out_image_bytes() const { return channels == 1 ? (size_t)pitch_px * cfg.bev_height : image_bytes_of(pitch_px, cfg.bev_height, out_nv12()); }   // one device-side BEV image
+    size_t bpp() const { return channels == 1 ? 1 : 3; }   // bytes per pixel of the car sprite and of a dense host-side BGR image
     DevBuf car_pitched;               // the car sprite with rows of pitch_px pixels (gain pass of a pitched handle)
     AnalyticRig arig;                 // filled by bevw_build
     Plan aplan;                       // analytic modes: the WIDE unit schedule compiled from the projection (analytic_units_build)
@@ -1327,6 +1329,30 @@ static int balance_plan_run(bevw_handle *h, const FrameSource &src, int batch, c
     return BEVW_OK;
 }
 
+// One step of a one-channel handle (bevw_set_channels: no balance, table projection, packed frames): the units and the per-tap kernel where
+// the tile plan is in use, has a one-channel unit list (FW % 4 == 0) and every row and buffer holds whole aligned quads; else the per-pixel
+// kernel, with the same bytes.
+static int run_device_gray(bevw_handle *h, const FrameSource &src, int batch, const uint8_t *d_car, uint8_t *d_out, bool aligned4)
+{
+    const bevw_config &c = h->cfg;
+    if (h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && h->pitch_px % 4 == 0) {
+        PlanStep step;
+        step.src = src; step.batch = batch; step.blend = c.blend != 0; step.car = d_car; step.out = d_out;
+        if (plan_units_serve(h->plan, step)) {
+            h->last_path = BEVW_PATH_UNITS;
+            return plan_stitch(h->plan, h->stream, step);
+        }
+    }
+    h->last_path = BEVW_PATH_PER_PIXEL;
+    const StitchTables T = stitch_tables(h);
+    for_each_chunk(batch, [&](int b0, int nb) {
+        gray_stitch_launch_pp(h->stream, dim3((c.bev_width + 255) / 256, c.bev_height, nb), c.blend != 0, src.from(b0, c.frame_width, c.frame_height).packed,
+                              c.frame_width, c.frame_height, T, c.bev_width, c.bev_height, d_car, d_out + (size_t)b0 * h->out_image_bytes(), h->pitch_px,
+                              h->compat[BEVW_COMPAT_REMAP]);
+    });
+    return launch_check("k_stitch_pp_gray");
+}
+
 static int run_device(bevw_handle *h, const FrameSource &src, int batch, const uint8_t *d_car, uint8_t *d_out)
 {
     const bevw_config &c = h->cfg;
@@ -1335,6 +1361,7 @@ static int run_device(bevw_handle *h, const FrameSource &src, int batch, const u
     const bool aligned4 = (((uintptr_t)d_out | (uintptr_t)d_car) & 3u) == 0 && src.aligned4();
     if (pitched && (h->projection != BEVW_PROJ_LUT || h->schedule_in_use != BEVW_SCHED_TILE_PLAN || !aligned4))
         return fail(BEVW_E_INVALID, "an output pitch needs the tile-plan schedule, the table projection and 4-byte aligned buffers");
+    if (h->channels == 1) return run_device_gray(h, src, batch, d_car, d_out, aligned4);
     if (h->projection == BEVW_PROJ_LUT && h->schedule_in_use == BEVW_SCHED_TILE_PLAN && aligned4 && c.balance && bal_mode() == 1 && h->plan.compact_stride != 0) {
         h->last_path = BEVW_PATH_UNITS;
         return balance_plan_run(h, src, batch, d_car, d_out);
@@ -1575,6 +1602,35 @@ static int need_built(bevw_handle *h)
     return use_device(h->cfg.device);
 }
 
+// what a one-channel handle (bevw_set_channels) does not take: refused by the setter or entry point that comes second
+static int handle_three_channels(const bevw_handle *h, const char *what)
+{
+    if (h->channels == 1) return fail(BEVW_E_INVALID, "%s: the handle has 1 channel (bevw_set_channels), which stitches dense BGR-order planes by the tables", what);
+    return BEVW_OK;
+}
+
+int bevw_set_channels(bevw_handle *h, int channels)
+{
+    if (!h) return fail(BEVW_E_INVALID, "null handle");
+    if (channels != 1 && channels != 3) return fail(BEVW_E_INVALID, "channel count must be 1 or 3, got %d", channels);
+    if (channels == 1) {
+        const char *why = h->cfg.balance ? "a handle created with balance = 1 (the balance chain is HSV and three channel means)"
+                          : h->input_format != BEVW_INPUT_BGR ? "an input format other than BGR"
+                          : h->out_nv12() ? "NV12 output"
+                          : h->in_pitch_request != 0 ? "an input pitch"
+                          : h->projection != BEVW_PROJ_LUT ? "the analytic projection"
+                          : h->shard_n ? "a camera-shard handle" : nullptr;
+        if (why) return fail(BEVW_E_INVALID, "channel count 1 is not available with %s", why);
+    }
+    return engine_set(*h, &EngineCore::channels, channels, h->built);
+}
+
+int bevw_channels(bevw_handle *h)
+{
+    if (!h) return fail(BEVW_E_INVALID, "null handle");
+    return h->channels;
+}
+
 int bevw_get_undistort_map(bevw_handle *h, int cam, int16_t *map1, uint16_t *map2)
 {
     BEVW_TRY(need_built(h));
@@ -1610,6 +1666,7 @@ int bevw_set_projection(bevw_handle *h, int mode)
     if (mode != BEVW_PROJ_LUT && (h->nv12() || h->yuv422()))
         return fail(BEVW_E_INVALID, "analytic projection is not available with %s input", input_format_name(h->input_format));
     if (mode != BEVW_PROJ_LUT && h->out_nv12()) return fail(BEVW_E_INVALID, "analytic projection is not available with NV12 output");
+    if (mode != BEVW_PROJ_LUT) BEVW_TRY(handle_three_channels(h, "analytic projection"));
     h->projection = mode;
     return BEVW_OK;
 }
@@ -1654,6 +1711,7 @@ int bevw_set_input_format(bevw_handle *h, int format)
 {
     if (!h) return fail(BEVW_E_INVALID, "null handle");
     BEVW_TRY(check_input_format(*h, format));
+    if (format != BEVW_INPUT_BGR) BEVW_TRY(handle_three_channels(h, "an input format other than BGR"));
     if (format != BEVW_INPUT_BGR) {
         const char *name = input_format_name(format);
         if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "%s input is not available with the analytic projection", name);
@@ -1665,6 +1723,7 @@ int bevw_set_input_format(bevw_handle *h, int format)
 int bevw_set_input_pitch(bevw_handle *h, int pitch_bytes)
 {
     if (!h) return fail(BEVW_E_INVALID, "null handle");
+    if (pitch_bytes != 0) BEVW_TRY(handle_three_channels(h, "an input pitch"));
     BEVW_TRY(check_input_pitch(pitch_bytes, h->fw, h->fh, h->nv12()));
     return engine_set(*h, &EngineCore::in_pitch_request, pitch_bytes, h->built);
 }
@@ -1686,6 +1745,7 @@ int bevw_set_output_format(bevw_handle *h, int format)
     if (!h) return fail(BEVW_E_INVALID, "null handle");
     if (format != BEVW_OUTPUT_BGR && format != BEVW_OUTPUT_NV12) return fail(BEVW_E_INVALID, "unknown output format %d", format);
     if (format == BEVW_OUTPUT_NV12) {
+        BEVW_TRY(handle_three_channels(h, "NV12 output"));
         const bevw_config &c = h->cfg;
         if (c.bev_width % 2 || c.bev_height % 2)
             return fail(BEVW_E_INVALID, "NV12 output needs an even BEV width and height, got %dx%d", c.bev_width, c.bev_height);
@@ -1711,7 +1771,7 @@ static int download_images(bevw_handle *h, uint8_t *out, const void *d_src, size
         else HIP_TRY(hipMemcpy2DAsync(out, row_bytes, d_src, src_pitch, row_bytes, nrows, hipMemcpyDeviceToHost, h->stream));
         return BEVW_OK;
     }
-    const size_t row_bytes = (size_t)h->cfg.bev_width * 3, src_pitch = (size_t)h->pitch_px * 3;
+    const size_t row_bytes = (size_t)h->cfg.bev_width * h->bpp(), src_pitch = (size_t)h->pitch_px * h->bpp();   // (one channel: one byte per pixel)
     if (src_pitch == row_bytes) HIP_TRY(hipMemcpyAsync(out, d_src, row_bytes * rows, hipMemcpyDeviceToHost, h->stream));
     else HIP_TRY(hipMemcpy2DAsync(out, row_bytes, d_src, src_pitch, row_bytes, rows, hipMemcpyDeviceToHost, h->stream));
     return BEVW_OK;
@@ -1736,6 +1796,7 @@ int bevw_run_device(bevw_handle *h, const void *d_frames, int batch, const void 
 static int need_surfaces(bevw_handle *h, const void *table, int batch, void *d_out)
 {
     BEVW_TRY(need_built(h));
+    BEVW_TRY(handle_three_channels(h, "NV12 surfaces"));
     if (h->shard_n) return fail(BEVW_E_INVALID, "NV12 surfaces are not available on camera-shard handles");
     BEVW_TRY(need_surface_input(*h));
     if (h->projection != BEVW_PROJ_LUT) return fail(BEVW_E_INVALID, "NV12 surfaces are not available with the analytic projection");
@@ -1769,7 +1830,7 @@ int bevw_run(bevw_handle *h, const uint8_t *frames, int batch, const uint8_t *ca
     if (batch == 0) return BEVW_OK;
     const bevw_config &c = h->cfg;
     const size_t nin = (size_t)batch * h->set_bytes();
-    const size_t bev = (size_t)c.bev_width * c.bev_height * 3, dbev = h->out_image_bytes();
+    const size_t bev = (size_t)c.bev_width * c.bev_height * h->bpp(), dbev = h->out_image_bytes();
     BEVW_TRY(h->in.reserve(nin));
     BEVW_TRY(h->out.reserve(dbev * batch));
     HIP_TRY(hipMemcpyAsync(h->in.p, frames, nin, hipMemcpyHostToDevice, h->stream));
@@ -1794,7 +1855,7 @@ int bevw_run_cameras(bevw_handle *h, const uint8_t *front, const uint8_t *back, 
     if (!front || !back || !left || !right || !out) return fail(BEVW_E_INVALID, "bad argument");
     BEVW_TRY(need_packed_frames(*h));
     const bevw_config &c = h->cfg;
-    const size_t frame = h->set_bytes() / 4, bev = (size_t)c.bev_width * c.bev_height * 3;
+    const size_t frame = h->set_bytes() / 4, bev = (size_t)c.bev_width * c.bev_height * h->bpp();
     BEVW_TRY(h->in.reserve(frame * 4));
     BEVW_TRY(h->out.reserve(h->out_image_bytes()));
     const uint8_t *src[4] = {front, back, left, right};
@@ -1868,6 +1929,7 @@ int bevw_set_camera_shard(bevw_handle *h, const int32_t *cams, int ncams)
     }
     if (h->input_format != BEVW_INPUT_BGR) return fail(BEVW_E_INVALID, "camera-shard handles take BGR frames only (%s input is set)", input_format_name(h->input_format));
     if (h->out_nv12()) return fail(BEVW_E_INVALID, "camera-shard handles write BGR images only (NV12 output is set)");
+    BEVW_TRY(handle_three_channels(h, "a camera shard"));
     h->shard_n = ncams; h->cams = ncams;
     for (int k = 0; k < 4; ++k) h->shard_cams[k] = k < ncams ? cams[k] : cams[0];
     h->built = false;
@@ -2091,6 +2153,7 @@ int bevw_combine_device(bevw_handle *h, const void *const *d_parts, const int32_
     if (!d_parts || !boxes || !d_out || batch < 0) return fail(BEVW_E_INVALID, "bad argument");
     if (nparts < 1 || nparts > 8) return fail(BEVW_E_INVALID, "1..8 parts");
     if (h->out_nv12()) return fail(BEVW_E_INVALID, "bevw_combine_device writes BGR images (the handle's output format is NV12)");
+    BEVW_TRY(handle_three_channels(h, "bevw_combine_device writes three-channel images"));
     const bevw_config &c = h->cfg;
     const int bw = c.bev_width, bh = c.bev_height;
     CombineParts parts;

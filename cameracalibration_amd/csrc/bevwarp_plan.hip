@@ -7,7 +7,7 @@ namespace bevw {
 
 void plan_release(Plan &p)
 {
-    void *ptrs[] = {p.un_desc, p.un_entries, p.list_un_all, p.entries, p.hdr, p.psums, p.pad_out, p.pad_car, p.d_max, p.list_slow};
+    void *ptrs[] = {p.un_desc, p.un_entries, p.list_un_all, p.entries, p.hdr, p.psums, p.pad_out, p.pad_car, p.pad_car_gray, p.d_max, p.list_slow};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (int l = 0; l < kPlanLayouts; ++l)

@@ -266,6 +266,25 @@ int bevw_run_surface_table_device(bevw_handle *h, const void *d_surfaces, int ba
 #define BEVW_OUTPUT_NV12 1
 int bevw_set_output_format(bevw_handle *h, int format);
 int bevw_output_format(bevw_handle *h);   /* BEVW_OUTPUT_BGR or BEVW_OUTPUT_NV12 */
+/* Single-channel frames (mono, NIR, thermal cameras; the Y plane of a grey perception network): what the reference's __call__ gives when its
+ * cv2 calls are made on (H, W) arrays.  channels = 3 (the default) or 1.  With 1, bevw_run, bevw_run_device and bevw_run_cameras take frames
+ * as uint8 [batch][4][FH][FW] (or four [FH][FW] arrays), the car as [BH][BW] or NULL, and write device images [batch][BH][bevw_output_pitch()]
+ * of one byte per pixel (host images [batch][BH][BW], dense): cv2.remap per camera (INTER_LINEAR, BORDER_CONSTANT 0, ties half up), the
+ * direct masks or the blend weights trunc(f32(v) * f32(m / 255.0)), saturating adds in camera order, then the car; a pixel no camera
+ * covers is 0, or the car.  Byte for byte this is every channel of the three-channel handle on the replicated frames and car.  The plan,
+ * the unit partition and the entries are the three-channel handle's; call before or after bevw_build (after: the handle's queued steps are
+ * waited for).  The output pitch keeps its meaning -- pixels per row, here bytes; BEVW_PITCH_ALIGNED is BEV_WIDTH rounded up to 64 -- the
+ * bytes of the padding columns are unspecified, and d_car stays dense.  A step runs the units and the per-tap kernel (BEVW_PATH_UNITS) when
+ * the tile plan is in use, FRAME_WIDTH % 4 == 0, d_frames, d_car and d_out are 4-byte aligned and bevw_output_pitch() % 4 == 0; every other
+ * step runs the per-pixel kernel (BEVW_PATH_PER_PIXEL) with the same bytes -- except that a handle with an output pitch refuses a
+ * misaligned buffer before anything is written, as with three channels.
+ * Refused with BEVW_E_INVALID, whichever setter comes second, bevw_last_error() naming the channel count: a handle created with
+ * balance = 1 (the balance chain is HSV and three channel means); any input format but BGR; BEVW_OUTPUT_NV12; an input pitch and the
+ * surface entry points; BEVW_PROJ_ANALYTIC / BEVW_PROJ_ANALYTIC_F32; camera-shard handles; bevw_combine_device.
+ * The per-camera tools (bevw_camera_undistort, _warp_homography, _raw2bev, bevw_apply_mask) and the JPEG entry points keep taking BGR
+ * whatever the channel count.  Not provided: balance on grey frames, grey NV12 / surface sources, 4 channels, 16-bit images. */
+int bevw_set_channels(bevw_handle *h, int channels);
+int bevw_channels(bevw_handle *h);   /* 1 or 3 */
 /* The reference's own call shape, bev(front, back, left, right, car) (surroundBEV.py:312, main.py:84): four separate
  * [FH][FW][3] host arrays (no packing copy on the host), one frame set, out [BH][BW][3]. */
 int bevw_run_cameras(bevw_handle *h, const uint8_t *front, const uint8_t *back, const uint8_t *left, const uint8_t *right,
