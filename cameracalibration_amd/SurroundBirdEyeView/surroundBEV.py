@@ -478,6 +478,49 @@ class BevGenerator:
         check(lib().bevw_run(self._engine.h, ptr(frames), frames.shape[0], car_p, ptr(out)))
         return out
 
+    # ---- additive: a homography per frame set (moving extrinsics) ---------------------------------------------
+    def _need_moving(self, what: str) -> None:
+        """What bevw_run_homographies_device refuses, before any device call."""
+        c = self._engine.cfg
+        for bad, why in ((self.balance, "balance (the natural next step: the V means do not depend on H)"),
+                         (self.channels != 3, "channels=%r" % (self.channels,)), (self.input_format != 'bgr', "input_format=%r" % (self.input_format,)),
+                         (self.in_pitch != c.frame_width, "an input_pitch"), (self.output_format != 'bgr', "output_format=%r" % (self.output_format,)),
+                         (self.projection != 'lut', "projection=%r" % (self.projection,))):
+            if bad:
+                raise Exception("{} is not available with {}".format(what, why))
+
+    def batch_homographies(self, frames, homographies, car=None):
+        """batch() with a homography per frame set and camera: frames uint8 [B, 4, FH, FW, 3], homographies float64 [B, 4, 3, 3] (H as the
+        rig holds it, undistorted grid -> BEV; front, back, left, right) -> uint8 [B, BH, BW, 3].  Image b is, byte for byte, what
+        BevGenerator(rig with homographies[b]) returns for frames[b]; the undistort maps, masks and blend weights of this generator are
+        reused and nothing of it changes (bevw_run_homographies in include/bevwarp.h).  Needs balance=False, 'bgr' in and out, channels=3, no
+        input_pitch and the 'lut' projection."""
+        self._need_moving("batch_homographies()")
+        c = self._engine.cfg
+        frames = np.ascontiguousarray(frames)
+        want = (4, c.frame_height, c.frame_width, 3)
+        if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[1:] != want:
+            raise Exception("frames must be uint8 [B, {}]".format(", ".join(str(n) for n in want)))
+        hs = _ffi.homography_table(homographies, frames.shape[0])
+        car_p = None
+        if car is not None:
+            car = self._as_car(car)
+            if car.shape[:2] != (c.bev_height, c.bev_width):
+                raise Exception("car must be padded to the BEV size (padding())")
+            car_p = ptr(car)
+        out = np.empty((frames.shape[0], c.bev_height, c.bev_width, 3), np.uint8)
+        check(lib().bevw_run_homographies(self._engine.h, ptr(frames), ptr(hs), frames.shape[0], car_p, ptr(out)))
+        return out
+
+    def run_homographies_device(self, d_frames: int, homographies, batch: int, d_car, d_out: int, out_bytes: int = None) -> None:
+        """run_device() with a homography per frame set and camera: ``homographies`` is float64 [batch, 4, 3, 3] on the HOST, copied before
+        the call returns; d_frames, d_car, d_out and out_bytes as for run_device().  last_path() reports PATH_PER_PIXEL afterwards, and the
+        next run_device() is back on the tile plan."""
+        self._need_moving("run_homographies_device()")
+        hs = _ffi.homography_table(homographies, batch)
+        self._check_out_bytes(batch, out_bytes)
+        check(lib().bevw_run_homographies_device(self._engine.h, d_frames, ptr(hs), int(batch), d_car, d_out))
+
     # ---- additive: compressed in, compressed out (row f4) ----------------------------------------------------
     def _imgcodecs(self):
         try:

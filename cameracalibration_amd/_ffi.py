@@ -97,6 +97,8 @@ SIGNATURES = {
     "bevw_output_format": (_i, [_vp]),
     "bevw_set_channels": (_i, [_vp, _i]),
     "bevw_channels": (_i, [_vp]),
+    "bevw_run_homographies_device": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "bevw_run_homographies": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "bevw_run_cameras": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bevw_camera_undistort": (_i, [_vp, _i, _vp, _i, _vp]),
     "bevw_camera_warp_homography": (_i, [_vp, _i, _vp, _i, _i, _i, _vp]),
@@ -241,6 +243,19 @@ def surface_table(table, per_set: int, what: str = "table") -> np.ndarray:
     ok = a.dtype == np.uint64 and a.shape[-1:] == (2,) and (a.ndim == 3 and a.shape[1] == per_set if per_set > 1 else a.ndim == 2)
     if not ok:
         raise Exception("{} must be uint64 {} (device addresses of the Y and U/V planes), got {} {}".format(what, want, a.dtype, list(a.shape)))
+    return np.ascontiguousarray(a)
+
+
+def homography_table(table, batch=None) -> np.ndarray:
+    """The homographies of a moving step as the library reads them (bevw_run_homographies_device): a C-contiguous float64 array
+    [B, 4, 3, 3] on the host, H per frame set and camera (front, back, left, right) as set_camera takes it.  Raises with the expected shape
+    otherwise; non-finite entries are refused here as the library refuses them."""
+    a = np.asarray(table)
+    if a.dtype != np.float64 or a.ndim != 4 or a.shape[1:] != (4, 3, 3) or (batch is not None and a.shape[0] != int(batch)):
+        raise Exception("homographies must be float64 [{}, 4, 3, 3], got {} {}".format("B" if batch is None else int(batch), a.dtype, list(a.shape)))
+    bad = np.argwhere(~np.isfinite(a))
+    if len(bad):
+        raise Exception("homographies: frame set {}, camera {} has an entry that is not finite".format(int(bad[0][0]), int(bad[0][1])))
     return np.ascontiguousarray(a)
 
 

@@ -20,6 +20,7 @@
 #include "bevw_yuv422.h"
 #include "bevw_gray.h"
 #include "bevw_gray_stitch.h"
+#include "bevw_moving.h"
 #include "bevw_comm.h"
 
 using namespace bevw;
@@ -280,11 +281,18 @@ struct SurfStage {
             if ((((uintptr_t)tab[i].y) | ((uintptr_t)tab[i].uv)) & 3u)
                 return fail(BEVW_E_INVALID, "surface %zu of the table has a plane pointer that is not 4-byte aligned", i);
         }
+        const void *d = nullptr;
+        BEVW_TRY(stage_bytes(st, tab, n * sizeof(Nv12Surface), d, slot));
+        d_tab = static_cast<const Nv12Surface *>(d);
+        return BEVW_OK;
+    }
+    // any host table of `bytes` bytes (the inverse homographies of bevw_run_homographies_device), checked by its caller
+    int stage_bytes(hipStream_t st, const void *tab, size_t bytes, const void *&d_tab, int &slot)
+    {
         slot = next;
         next = (next + 1) % kSlots;
         if (used[slot]) HIP_TRY(hipEventSynchronize(ev[slot]));
         used[slot] = false;
-        const size_t bytes = n * sizeof(Nv12Surface);
         if (bytes > cap[slot]) {
             if (host[slot]) (void)hipHostFree(host[slot]);
             if (dev[slot]) (void)hipFree(dev[slot]);
@@ -296,7 +304,7 @@ struct SurfStage {
         if (!ev[slot]) HIP_TRY(hipEventCreateWithFlags(&ev[slot], hipEventDisableTiming));
         memcpy(host[slot], tab, bytes);
         HIP_TRY(hipMemcpyAsync(dev[slot], host[slot], bytes, hipMemcpyHostToDevice, st));
-        d_tab = static_cast<const Nv12Surface *>(dev[slot]);
+        d_tab = dev[slot];
         return BEVW_OK;
     }
     int done(hipStream_t st, int slot)
@@ -982,6 +990,7 @@ struct bevw_handle : EngineCore {
     int shard_box[4] = {0, 0, 0, 0};   // x0, y0, x1, y1: bounding box of the owned masks
     DevBuf sdeltas;
     DevBuf xchg;          // RCCL staging (rank-major V sums)
+    SurfStage minv_stage; // the inverse homographies of the moving steps on their way to the device (bevw_run_homographies_device)
     bool owns(int cam) const
     {
         if (shard_n == 0) return true;
@@ -1589,6 +1598,7 @@ void bevw_destroy(bevw_handle *h)
         h->hsv.release(); h->vsums.release(); h->deltas.release(); h->chsums.release(); h->sdeltas.release();
         h->car.release(); h->tmp.release(); h->pre.release(); h->car_pitched.release(); h->xchg.release();
         plan_release(h->aplan);
+        h->minv_stage.release();
         for (hipEvent_t e : {h->ev_fork, h->ev_skew, h->ev_join}) if (e) (void)hipEventDestroy(e);
         h->close();
     }
@@ -1841,6 +1851,102 @@ int bevw_run(bevw_handle *h, const uint8_t *frames, int batch, const uint8_t *ca
         d_car = h->car.as<uint8_t>();
     }
     BEVW_TRY(run_device(h, h->source(h->in.as<uint8_t>(), nullptr), batch, d_car, h->out.as<uint8_t>()));
+    BEVW_TRY(download_images(h, out, h->out.p, (size_t)batch * c.bev_height));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return BEVW_OK;
+}
+
+// ---- a homography per frame set (moving extrinsics) -------------------------------------------------------------------------------------
+// what a moving step does not take, by the entry point's name: refused whichever of the setters, bevw_build and the step comes last
+static int need_moving(bevw_handle *h, const char *entry)
+{
+    if (!h) return fail(BEVW_E_INVALID, "%s: null handle", entry);
+    const char *why = h->shard_n ? "a camera-shard handle"
+                      : h->cfg.balance ? "a handle created with balance = 1 (its V means do not depend on H: the natural next step, not built)"
+                      : h->channels != 3 ? "a handle with 1 channel (bevw_set_channels)"
+                      : h->input_format != BEVW_INPUT_BGR ? "an input format other than BGR"
+                      : h->in_pitch_request != 0 ? "an input pitch (NV12 surfaces)"
+                      : h->out_nv12() ? "BEVW_OUTPUT_NV12"
+                      : h->projection != BEVW_PROJ_LUT ? "the analytic projection" : nullptr;
+    if (why) return fail(BEVW_E_INVALID, "%s is not available with %s", entry, why);
+    if (!h->built) return fail(BEVW_E_INVALID, "%s: bevw_build has not been called", entry);
+    return use_device(h->cfg.device);
+}
+
+// The inverse of every matrix on the HOST, with the invert3x3 of bevw_build (a singular matrix: zeros), refused where an entry of a matrix or
+// of its inverse is not finite; then the kernel over the batch's chunks.  Nothing of the handle's own tables, plan or calibration is touched.
+static int run_homographies_device(bevw_handle *h, const char *entry, const uint8_t *d_frames, const double *homographies, int batch, const uint8_t *d_car,
+                                   uint8_t *d_out)
+{
+    const bevw_config &c = h->cfg;
+    std::vector<double> inv((size_t)batch * 36);
+    for (int b = 0; b < batch; ++b)
+        for (int cam = 0; cam < 4; ++cam) {
+            const double *H = homographies + ((size_t)b * 4 + cam) * 9;
+            double *t = inv.data() + ((size_t)b * 4 + cam) * 9;
+            invert3x3(H, t);
+            for (int k = 0; k < 9; ++k)
+                if (!std::isfinite(H[k]) || !std::isfinite(t[k]))
+                    return fail(BEVW_E_INVALID, "%s: frame set %d, camera %d: entry %d of the %s is not finite", entry, b, cam, k,
+                                std::isfinite(H[k]) ? "inverse homography" : "homography");
+        }
+    const bool pitched = h->pitch_px != c.bev_width;
+    if (pitched && ((((uintptr_t)d_frames | (uintptr_t)d_out | (uintptr_t)d_car) & 3u) != 0 || h->schedule_in_use != BEVW_SCHED_TILE_PLAN))
+        return fail(BEVW_E_INVALID, "%s: an output pitch needs the tile-plan schedule, the table projection and 4-byte aligned buffers", entry);
+    const void *d_inv = nullptr;
+    int slot = 0;
+    BEVW_TRY(h->minv_stage.stage_bytes(h->stream, inv.data(), inv.size() * sizeof(double), d_inv, slot));
+    MovingArgs a;
+    for (int cam = 0; cam < 4; ++cam) {
+        a.und1[cam] = h->und1[cam].as<int16_t>(); a.und2[cam] = h->und2[cam].as<uint16_t>(); a.mask[cam] = h->mask[cam].as<uint8_t>();
+    }
+    a.car = d_car;
+    a.fw = c.frame_width; a.fh = c.frame_height; a.uw = h->uw; a.uh = h->uh; a.bw = c.bev_width; a.bh = c.bev_height;
+    a.bw0 = persp_block_width(c.bev_width, c.bev_height);
+    a.pitch = h->pitch_px;
+    a.warp_mode = h->compat[BEVW_COMPAT_WARP]; a.ties_even = h->compat[BEVW_COMPAT_REMAP];
+    const long long tiles = (long long)((c.bev_width + kMovingTileW - 1) / kMovingTileW) * ((c.bev_height + kMovingTileH - 1) / kMovingTileH);
+    const size_t set_bytes = (size_t)c.frame_width * c.frame_height * 3 * 4, img_bytes = (size_t)h->pitch_px * c.bev_height * 3;
+    for_each_chunk(batch, [&](int b0, int nb) {
+        a.frames = d_frames + (size_t)b0 * set_bytes;
+        a.minv = static_cast<const double *>(d_inv) + (size_t)b0 * 36;
+        a.out = d_out + (size_t)b0 * img_bytes;
+        a.batch = nb; a.nb = moving_nb(nb, tiles);
+        moving_launch_stitch(h->stream, a, c.blend != 0);
+    });
+    const int s = launch_check("k_stitch_moving");
+    BEVW_TRY(h->minv_stage.done(h->stream, slot));   // (behind whatever was enqueued: the slot's table stays until then)
+    if (s == BEVW_OK) h->last_path = BEVW_PATH_PER_PIXEL;
+    return s;
+}
+
+int bevw_run_homographies_device(bevw_handle *h, const void *d_frames, const double *homographies, int batch, const void *d_car, void *d_out)
+{
+    static const char *const entry = "bevw_run_homographies_device";
+    BEVW_TRY(need_moving(h, entry));
+    if (!d_frames || !homographies || !d_out || batch < 0) return fail(BEVW_E_INVALID, "%s: bad argument", entry);
+    if (batch == 0) return BEVW_OK;
+    return run_homographies_device(h, entry, (const uint8_t *)d_frames, homographies, batch, (const uint8_t *)d_car, (uint8_t *)d_out);
+}
+
+int bevw_run_homographies(bevw_handle *h, const uint8_t *frames, const double *homographies, int batch, const uint8_t *car, uint8_t *out)
+{
+    static const char *const entry = "bevw_run_homographies";
+    BEVW_TRY(need_moving(h, entry));
+    if (!frames || !homographies || !out || batch < 0) return fail(BEVW_E_INVALID, "%s: bad argument", entry);
+    if (batch == 0) return BEVW_OK;
+    const bevw_config &c = h->cfg;
+    const size_t nin = (size_t)batch * h->set_bytes(), bev = (size_t)c.bev_width * c.bev_height * 3;
+    BEVW_TRY(h->in.reserve(nin));
+    BEVW_TRY(h->out.reserve(h->out_image_bytes() * batch));
+    HIP_TRY(hipMemcpyAsync(h->in.p, frames, nin, hipMemcpyHostToDevice, h->stream));
+    const uint8_t *d_car = nullptr;
+    if (car) {
+        BEVW_TRY(h->car.reserve(bev));
+        HIP_TRY(hipMemcpyAsync(h->car.p, car, bev, hipMemcpyHostToDevice, h->stream));
+        d_car = h->car.as<uint8_t>();
+    }
+    BEVW_TRY(run_homographies_device(h, entry, h->in.as<uint8_t>(), homographies, batch, d_car, h->out.as<uint8_t>()));
     BEVW_TRY(download_images(h, out, h->out.p, (size_t)batch * c.bev_height));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return BEVW_OK;

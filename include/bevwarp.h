@@ -285,6 +285,34 @@ int bevw_output_format(bevw_handle *h);   /* BEVW_OUTPUT_BGR or BEVW_OUTPUT_NV12
  * whatever the channel count.  Not provided: balance on grey frames, grey NV12 / surface sources, 4 channels, 16-bit images. */
 int bevw_set_channels(bevw_handle *h, int channels);
 int bevw_channels(bevw_handle *h);   /* 1 or 3 */
+/* A homography per frame set (moving extrinsics).  K and D of a camera are fixed, H is not: braking, load, suspension travel and a trailer
+ * tilt the ground plane frame by frame, and a replayed log carries a pose per frame.  Frame set b of such a step is stitched, byte for
+ * byte, as a handle would stitch it after bevw_set_camera(cam, K, D, homographies[b][cam]) for the four cameras and bevw_build in table
+ * mode (BEVW_PROJ_LUT): Camera.get_bev_maps is cv2.warpPerspective(undistort maps, H), and the undistort maps depend on K, D and the
+ * sizes only, so they stay resident from bevw_build and the step is "warp the maps with H_b, then remap the frame", fused per pixel --
+ * the same inverse, the same column blocks of warpPerspective, the handle's BEVW_COMPAT_WARP and BEVW_COMPAT_REMAP, saturation to int16 /
+ * uint16, the masks (direct) or the blend weights, saturating adds in camera order, then the car.  No table is written and no plan is
+ * compiled.  A BEV pixel whose position falls outside the undistorted grid reads map value 0 and samples the frame at (0, 0), as in the
+ * reference; this is not "fixed".  Masks, blend weights and the car do not depend on H.
+ *   homographies   a HOST array [batch][4][9] of H as bevw_set_camera takes it (undistorted grid -> BEV), cameras front, back, left, right.
+ *                  Every matrix is inverted on the host with the 3x3 inverse bevw_build uses (a singular matrix gives the zero matrix,
+ *                  as cv::invert does).  The inverses are staged in pinned slots as the tables of bevw_run_surfaces_device are: the
+ *                  array is free when the call returns, and consecutive calls need no host synchronisation (a fifth queued call waits
+ *                  for the first).  A non-finite entry of a matrix or of its inverse is refused with BEVW_E_INVALID before any device
+ *                  work; bevw_last_error() names frame set and camera.
+ *   buffers        d_frames, d_car, d_out, the rows of bevw_output_pitch() pixels and the chunks of 65535 frame sets are those of
+ *                  bevw_run_device.  Any byte alignment is served; a handle with an output pitch refuses a misaligned buffer before
+ *                  anything is written, as bevw_run_device does.  bevw_run_homographies takes host buffers and returns dense images, as
+ *                  bevw_run does.
+ *   handle state   bevw_last_path reports BEVW_PATH_PER_PIXEL after such a step.  The handle's tables, plan and calibration are untouched:
+ *                  the next bevw_run_device is back on the units with the bytes it gave before.
+ * Refused with BEVW_E_INVALID, bevw_last_error() naming the entry point, whichever of the setter, bevw_build and the step comes last: a
+ * handle created with balance = 1; any input format but BGR; BEVW_OUTPUT_NV12; 1 channel; an input pitch (surfaces); BEVW_PROJ_ANALYTIC /
+ * BEVW_PROJ_ANALYTIC_F32; camera-shard handles; a handle that is not built.
+ * Not provided: a device-resident table of H (a device-side inversion would have to match the host's to the last bit); balance (the V
+ * means do not depend on H: the natural next step); any source format but BGR; NV12 images; grey frames. */
+int bevw_run_homographies_device(bevw_handle *h, const void *d_frames, const double *homographies, int batch, const void *d_car, void *d_out);
+int bevw_run_homographies(bevw_handle *h, const uint8_t *frames, const double *homographies, int batch, const uint8_t *car, uint8_t *out);
 /* The reference's own call shape, bev(front, back, left, right, car) (surroundBEV.py:312, main.py:84): four separate
  * [FH][FW][3] host arrays (no packing copy on the host), one frame set, out [BH][BW][3]. */
 int bevw_run_cameras(bevw_handle *h, const uint8_t *front, const uint8_t *back, const uint8_t *left, const uint8_t *right,
