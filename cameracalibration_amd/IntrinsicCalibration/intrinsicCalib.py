@@ -53,6 +53,7 @@ class Fisheye:
         self.data.type = "FISHEYE"
         self._remapper = None
         self._remapper_gray = None   # the same maps in one channel (InCalibrator.undistort on a [FH, FW] image), made on first use
+        self._remapper_gray16 = None   # ... and in one channel of 16 bits (a uint16 [FH, FW] image)
         self._device = 0
 
     def _get_camera_mat_dst(self, camera_mat):
@@ -65,6 +66,9 @@ class Fisheye:
         return camera_mat_dst
 
     def _release(self):
+        if self._remapper_gray16:
+            lib().bevw_remapper_destroy(self._remapper_gray16)
+            self._remapper_gray16 = None
         if self._remapper_gray:
             lib().bevw_remapper_destroy(self._remapper_gray)
             self._remapper_gray = None
@@ -72,20 +76,24 @@ class Fisheye:
             lib().bevw_remapper_destroy(self._remapper)
             self._remapper = None
 
-    def _gray_remapper(self):
-        """A one-channel remapper over the camera's own maps (bevw_remapper_from_maps + bevw_remapper_set_channels)."""
-        if self._remapper_gray is None:
+    def _gray_remapper(self, depth=8):
+        """A one-channel remapper over the camera's own maps (bevw_remapper_from_maps + bevw_remapper_set_channels); depth=16: one of its
+        own for uint16 planes (bevw_remapper_set_depth)."""
+        slot = "_remapper_gray16" if depth == 16 else "_remapper_gray"
+        if getattr(self, slot) is None:
             d = self.data
             r = C.c_void_p()
             check(lib().bevw_remapper_from_maps(self._device, int(args.FRAME_WIDTH), int(args.FRAME_HEIGHT), ptr(d.map1), ptr(d.map2),
                                                 int(d.map2.shape[1]), int(d.map2.shape[0]), C.byref(r)))
             try:
                 check(lib().bevw_remapper_set_channels(r, 1))
+                if depth == 16:
+                    check(lib().bevw_remapper_set_depth(r, 16))
             except Exception:
                 lib().bevw_remapper_destroy(r)
                 raise
-            self._remapper_gray = r
-        return self._remapper_gray
+            setattr(self, slot, r)
+        return getattr(self, slot)
 
     def _get_undistort_maps(self):
         """intrinsicCalib.py:98-103 -- maps are built by k_fisheye_map and stay on the device."""
@@ -164,12 +172,16 @@ class InCalibrator:
 
     def undistort(self, img):
         """intrinsicCalib.py:193-195: cv2.remap(img, data.map1, data.map2, cv2.INTER_LINEAR).  A uint8 [FH, FW] image gives [h, w], as
-        cv2.remap does for a single plane."""
+        cv2.remap does for a single plane; a uint16 [FH, FW] image (a depth map, a thermal plane) gives uint16 [h, w]."""
         cam = self.camera
         if cam._remapper is None:
             raise Exception("no calibration: call set_calibration(K, D) first")
         if np.ndim(img) == 2:
             img = np.ascontiguousarray(img)
+            if img.dtype == np.uint16 and img.shape == (args.FRAME_HEIGHT, args.FRAME_WIDTH):
+                out = np.empty(cam.data.map2.shape, np.uint16)
+                check(lib().bevw_remap(cam._gray_remapper(16), ptr(img), 1, ptr(out)))
+                return out
             if img.dtype != np.uint8 or img.shape != (args.FRAME_HEIGHT, args.FRAME_WIDTH):
                 raise Exception("image is {} {}x{}, FRAME is uint8 {}x{}".format(img.dtype, img.shape[1], img.shape[0], args.FRAME_WIDTH,
                                                                               args.FRAME_HEIGHT))

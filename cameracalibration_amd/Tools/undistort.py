@@ -49,7 +49,7 @@ class Undistorter:
     """The map set of one (K, D, size, scales, offsets) on the device."""
 
     def __init__(self, K, D, width, height, focalscale=1.0, sizescale=1.0, offset_h=0.0, offset_v=0.0, device=0, input_format='bgr',
-                 output_format='bgr', input_pitch=None, channels=3):
+                 output_format='bgr', input_pitch=None, channels=3, depth=8):
         """input_format: 'bgr' (images [height, width, 3]) or 'nv12' ([height*3//2, width]: Y plane, then the interleaved U / V plane; the
         result is what cv2.remap gives for cv2.cvtColor(img, cv2.COLOR_YUV2BGR_NV12) -- bevw_remapper_set_input_format in include/bevwarp.h),
         'yuyv' / 'uyvy' ([height, width, 2]: packed 4:2:2 as a live camera delivers it; cv2.COLOR_YUV2BGR_YUY2 / _UYVY; an even width).
@@ -58,9 +58,14 @@ class Undistorter:
         input_pitch: with input_format='nv12', bytes between the rows of the decoder surfaces run_surfaces() reads in place (None: width;
         else a multiple of 4 >= width -- bevw_remapper_set_input_pitch); with a pitch other than width __call__ is refused.
         channels: 3, or 1 for single uint8 planes (images [height, width], results [out_h, out_w]: what cv2.remap gives for a 2-D array --
-        bevw_remapper_set_channels); one channel is 'bgr' in and out without a pitch."""
+        bevw_remapper_set_channels); one channel is 'bgr' in and out without a pitch.
+        depth: 8, or 16 with channels=1 for single uint16 planes (depth maps, thermal and NIR planes, HDR luma, label maps: images uint16
+        [height, width], results uint16 [out_h, out_w]: what cv2.remap gives for a 2-D uint16 array -- bevw_remapper_set_depth)."""
         self._r = None
         self.channels = _ffi.channels(channels)
+        self.depth = _ffi.depth(depth)
+        if self.depth == 16 and self.channels != 1:
+            raise Exception("depth=16 needs channels=1")
         formats = _ffi.INPUT_FORMATS
         _ffi.input_format(input_format)
         out_formats = {'bgr': _ffi.OUTPUT_BGR, 'nv12': _ffi.OUTPUT_NV12}
@@ -87,6 +92,8 @@ class Undistorter:
                 check(lib().bevw_remapper_set_output_format(r, out_formats[output_format]))
             if self.channels == 1:
                 check(lib().bevw_remapper_set_channels(r, 1))
+            if self.depth == 16:
+                check(lib().bevw_remapper_set_depth(r, 16))
         except Exception:
             self.close()
             raise
@@ -99,7 +106,7 @@ class Undistorter:
     def out_image_bytes(self) -> int:
         """Bytes of one dense device image as run_surfaces() writes it."""
         if self.channels == 1:
-            return self.out_w * self.out_h
+            return self.out_w * self.out_h * (self.depth // 8)
         return self.out_w * self.out_h * 3 // 2 if self.output_format == 'nv12' else self.out_w * self.out_h * 3
 
     def last_path(self) -> int:
@@ -140,8 +147,17 @@ class Undistorter:
     def __call__(self, images):
         """uint8 [B, height, width, 3] (or one [height, width, 3]) -> undistorted images of the map size.  'nv12': [B, height*3//2, width]
         (or one [height*3//2, width]); 'yuyv' / 'uyvy': [B, height, width, 2] (or one [height, width, 2]).  output_format 'nv12': [B, out_h*3//2, out_w] (or one [out_h*3//2, out_w]).
-        channels=1: [B, height, width] (or one [height, width]) -> [B, out_h, out_w] (or one [out_h, out_w])."""
+        channels=1: [B, height, width] (or one [height, width]) -> [B, out_h, out_w] (or one [out_h, out_w]); depth=16: the same in uint16."""
         imgs = np.ascontiguousarray(images)
+        if self.depth == 16:
+            single = imgs.ndim == 2
+            if single:
+                imgs = imgs[np.newaxis]
+            if imgs.dtype != np.uint16 or imgs.ndim != 3 or imgs.shape[1:] != (self.height, self.width):
+                raise Exception("images must be uint16 [B, height, width] = [B, {}, {}] (depth=16)".format(self.height, self.width))
+            out = np.empty((imgs.shape[0], self.out_h, self.out_w), np.uint16)
+            check(lib().bevw_remap(self._r, ptr(imgs), imgs.shape[0], ptr(out)))
+            return out[0] if single else out
         frame = (self.height, self.width) if self.channels == 1 else _ffi.frame_shape(self.input_format, self.height, self.width)
         single = imgs.ndim == len(frame)
         if single:

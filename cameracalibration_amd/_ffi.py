@@ -36,6 +36,13 @@ def channels(n) -> int:
     return int(n)
 
 
+def depth(bits) -> int:
+    """The bit depth of a one-channel remapper's images (bevw_remapper_set_depth): 8, or 16 for uint16 [H, W] planes."""
+    if isinstance(bits, bool) or bits not in (8, 16):
+        raise Exception("depth should be 8/16")
+    return int(bits)
+
+
 def frame_shape(name, height: int, width: int):
     """Shape of one camera frame of a format: (H, W, 3) 'bgr', (H*3//2, W) 'nv12', (H, W, 2) 'yuyv' / 'uyvy'."""
     if name == 'nv12':
@@ -137,6 +144,8 @@ SIGNATURES = {
     "bevw_remapper_set_input_pitch": (_i, [_vp, _i]),
     "bevw_remapper_set_channels": (_i, [_vp, _i]),
     "bevw_remapper_channels": (_i, [_vp]),
+    "bevw_remapper_set_depth": (_i, [_vp, _i]),
+    "bevw_remapper_depth": (_i, [_vp]),
     "bevw_remapper_last_path": (_i, [_vp]),
     "bevw_remap_surfaces_device": (_i, [_vp, _vp, _i, _vp]),
     "bevw_remap_surface_table_device": (_i, [_vp, _vp, _i, _vp]),

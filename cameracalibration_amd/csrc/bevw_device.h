@@ -302,11 +302,14 @@ __host__ __device__ __forceinline__ size_t frame_bytes_of(int fw, int fh, bool n
 // The arithmetic is NV12's (nv12_bgr): cv2.cvtColor(COLOR_YUV2BGR_YUY2 / COLOR_YUV2BGR_UYVY).
 // The format of the camera frames of a step; the values are the BEVW_INPUT_* constants of include/bevwarp.h.
 // GRAY is internal: the one-channel frames of a remapper (bevw_remapper_set_channels), a channel count and no BEVW_INPUT_* value.
-enum class SrcFormat : int { BGR = 0, NV12 = 1, YUYV = 4, UYVY = 5, GRAY = 0x100 };
+// GRAY16: the same with 16 bits per texel (bevw_remapper_set_depth: little-endian uint16); a remapper's only, and host-side only.
+enum class SrcFormat : int { BGR = 0, NV12 = 1, YUYV = 4, UYVY = 5, GRAY = 0x100, GRAY16 = 0x101 };
 __host__ __device__ __forceinline__ bool src_is_yuv422(SrcFormat f) { return f == SrcFormat::YUYV || f == SrcFormat::UYVY; }
-// bytes of one frame: BGR 3 per texel, NV12 1.5, packed 4:2:2 2, one channel 1
+__host__ __device__ __forceinline__ bool src_is_gray(SrcFormat f) { return f == SrcFormat::GRAY || f == SrcFormat::GRAY16; }   // one channel, 8 or 16 bits
+// bytes of one frame: BGR 3 per texel, NV12 1.5, packed 4:2:2 2, one channel 1 or 2
 __host__ __device__ __forceinline__ size_t frame_bytes_of(int fw, int fh, SrcFormat f)
 {
+    if (f == SrcFormat::GRAY16) return (size_t)fw * fh * 2;
     if (f == SrcFormat::GRAY) return (size_t)fw * fh;
     return src_is_yuv422(f) ? (size_t)fw * fh * 2 : frame_bytes_of(fw, fh, f == SrcFormat::NV12);
 }

@@ -27,6 +27,7 @@
 #include "bevw_planapi.h"
 #include "bevw_yuv422.h"
 #include "bevw_gray.h"
+#include "bevw_gray16.h"
 #include "bevw_gray_stitch.h"
 
 namespace bevw {
@@ -627,6 +628,8 @@ static inline RouteIn plan_route_in(const Plan &p, const PlanStep &s, const Plan
 
 // One step of a one-channel plan (SrcFormat::GRAY: bevw_remapper_set_channels): k_units_gray over every unit, k_stitch_plan_gray over the
 // base tiles no unit owns (bevwarp_gray.hip).  Images of bw x bh bytes: bw % 4 == 0 and a 4-byte aligned `out` (a quad is one dword store).
+// SrcFormat::GRAY16 (bevw_remapper_set_depth): the same route, lists and conditions on k_units_gray16 and k_stitch_plan_gray16
+// (bevwarp_gray16.hip) -- images of bw x bh uint16, a quad is one 8-byte store at a multiple of 8 bytes from `out`.
 static inline hipError_t plan_gray_step(const Plan &p, hipStream_t st, const PlanStep &s, const PlanTuning &tune, const Route &rt)
 {
     if (!rt.use_units || rt.units != kLayoutGray || p.pitch != p.bw || p.bw % 4 != 0 || (((uintptr_t)s.out) & 3u) != 0 || s.car || s.blend)
@@ -636,12 +639,15 @@ static inline hipError_t plan_gray_step(const Plan &p, hipStream_t st, const Pla
     a.tile_list = static_cast<const uint32_t *>(p.list_un_all); a.nlist = p.n_un_all; a.ngroups = p.n_un_all;
     a.set_stride = rt.set_stride;
     a.un_gsrc = static_cast<const uint32_t *>(p.units[kLayoutGray]);
-    gray_launch_units(a, st);
+    const bool deep = p.fmt == SrcFormat::GRAY16;
+    if (deep) gray16_launch_units(a, st);
+    else gray_launch_units(a, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || p.n_slow == 0) return e;
     a.tile_list = static_cast<const uint32_t *>(p.list_slow); a.nlist = p.n_slow; a.ngroups = (p.n_slow + 3) / 4;
     a.set_stride = 0;
-    gray_launch_stitch_plan(a, st);
+    if (deep) gray16_launch_stitch_plan(a, st);
+    else gray_launch_stitch_plan(a, st);
     return hipGetLastError();
 }
 
@@ -694,7 +700,7 @@ static inline hipError_t plan_stitch_impl(Plan &p, hipStream_t st, const PlanSte
     a.deltas = s.deltas; a.tab = s.tab;
     const bool padded = p.pitch != p.bw, scratch = padded && !p.out_pitched;
     const Route rt = plan_route(plan_route_in(p, s, tune));
-    if (p.fmt == SrcFormat::GRAY) return p.ncams == 1 ? plan_gray_step(p, st, s, tune, rt) : plan_gray_stitch_step(p, st, s, tune, rt);   // (a remapper's; a handle's)
+    if (src_is_gray(p.fmt)) return p.ncams == 1 ? plan_gray_step(p, st, s, tune, rt) : plan_gray_stitch_step(p, st, s, tune, rt);   // (a remapper's; a handle's)
     const bool out_nv12 = rt.out_nv12, use_units = rt.use_units;
     if (out_nv12 && (scratch || p.pitch % 4 != 0)) return hipErrorInvalidValue;   // (the caller runs the per-pixel kernel instead)
     if (padded) {

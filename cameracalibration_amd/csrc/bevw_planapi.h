@@ -42,7 +42,8 @@ struct FrameSource {
 // packed 4:2:2, the compact scratch (DESIGN.md section 8 has the table: what a slot holds, when a list is made, when it is missing).  A
 // missing list is nullptr, which sends the step to the per-tap kernel and is never an error.
 // kLayoutGray: the one-channel frames of a remapper or a handle (SrcFormat::GRAY), 1 byte per texel: the units' list alone, no sampled list
-// (no balance schedule), and routed by the format alone.
+// (no balance schedule), and routed by the format alone.  SrcFormat::GRAY16 (bevw_remapper_set_depth) reads the same list: a group's offset
+// in 2 bytes per texel is twice its offset in 1.
 
 // a compiled tile plan: its device buffers and the geometry they were built for (plan_build / plan_build_wide)
 struct Plan {
@@ -115,7 +116,7 @@ struct Route {
 };
 inline SrcLayout frames_layout(SrcFormat fmt, bool surf)
 {
-    return fmt == SrcFormat::GRAY ? kLayoutGray : src_is_yuv422(fmt) ? kLayoutYuv422 : surf ? kLayoutSurf : fmt == SrcFormat::NV12 ? kLayoutNV12 : kLayoutBGR;
+    return src_is_gray(fmt) ? kLayoutGray : src_is_yuv422(fmt) ? kLayoutYuv422 : surf ? kLayoutSurf : fmt == SrcFormat::NV12 ? kLayoutNV12 : kLayoutBGR;
 }
 inline Route plan_route(const RouteIn &in)
 {
@@ -131,7 +132,7 @@ inline Route plan_route(const RouteIn &in)
                   (r.units != kLayoutCompact || in.scratch_aligned) && (bgr_units || !in.sums);
     // one channel: the units on the frames themselves or nothing -- no balance chain, no shard scratch, no NV12 image exists in one channel,
     // and a step without units leaves the plan (the caller runs the per-pixel kernel: plan_units_serve)
-    const bool gray = in.fmt == SrcFormat::GRAY;
+    const bool gray = src_is_gray(in.fmt);   // (16 bits: the same list and the same rules -- k_units_gray16 doubles the list's offsets)
     if (gray) r.use_units = r.use_units && r.units == kLayoutGray && !in.out_nv12;
     r.out_nv12 = in.out_nv12 && !in.balance && !in.sums && !in.scratch && !gray;
     r.set_stride = !r.use_units || r.units == kLayoutBGR ? 0u : r.units == kLayoutCompact ? in.compact_stride : in.set_bytes;

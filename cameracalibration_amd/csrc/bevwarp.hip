@@ -19,6 +19,7 @@
 #include "bevw_planapi.h"
 #include "bevw_yuv422.h"
 #include "bevw_gray.h"
+#include "bevw_gray16.h"
 #include "bevw_gray_stitch.h"
 #include "bevw_moving.h"
 #include "bevw_comm.h"
@@ -366,7 +367,8 @@ struct EngineCore {
     int input_format = BEVW_INPUT_BGR, output_format = BEVW_OUTPUT_BGR;
     int in_pitch_request = 0;            // 0: the frame width
     int channels = 3;                    // 1: 8UC1 frames and images (bevw_remapper_set_channels, bevw_set_channels; BGR in and out, no input pitch)
-    SrcFormat fmt() const { return channels == 1 ? SrcFormat::GRAY : (SrcFormat)input_format; }
+    int depth = 8;                       // 16: 16UC1 frames and images of a remapper (bevw_remapper_set_depth; needs channels == 1)
+    SrcFormat fmt() const { return channels == 1 ? (depth == 16 ? SrcFormat::GRAY16 : SrcFormat::GRAY) : (SrcFormat)input_format; }
     bool nv12() const { return input_format == BEVW_INPUT_NV12; }
     bool yuv422() const { return src_is_yuv422(fmt()); }   // packed 4:2:2: YUYV / UYVY
     bool out_nv12() const { return output_format == BEVW_OUTPUT_NV12; }
@@ -498,7 +500,7 @@ static const EngineNouns kRemapperNouns = {"remapper", "the source width", "sour
 struct bevw_remapper : EngineCore {
     int dw = 0, dh = 0;   // (the source size: EngineCore::fw, fh)
     int last_path = BEVW_PATH_NONE;   // which kernels served the last step (bevw_remapper_last_path)
-    size_t image_bytes() const { return channels == 1 ? (size_t)dw * dh : image_bytes_of(dw, dh, out_nv12()); }   // one destination image
+    size_t image_bytes() const { return channels == 1 ? (size_t)dw * dh * (size_t)(depth / 8) : image_bytes_of(dw, dh, out_nv12()); }   // one destination image
     DevBuf map1, map2, ones;
     // the plan: a single-image contributor plan (same kernels as the BEV stitch, one frame per set)
     bool plan_ready = false;
@@ -510,7 +512,8 @@ static int remapper_build_plan(bevw_remapper *r)
 {
     static const int use_plan = env_int("BEVW_REMAP_PLAN", 1);
     r->plan_ready = false;
-    if (!use_plan || r->ties_even) return BEVW_OK;
+    // (a 16-bit remapper has one tie rule, its float arithmetic's, and takes the plan in both modes: bevw_remapper_set_depth builds it then)
+    if (!use_plan || (r->ties_even && r->depth != 16)) return BEVW_OK;
     const size_t npx = (size_t)r->dw * r->dh;
     BEVW_TRY(r->ones.reserve(npx));
     HIP_TRY(hipMemsetAsync(r->ones.p, 0xff, npx, r->stream));
@@ -557,7 +560,10 @@ static int remap_launch(hipStream_t st, const FrameSource &src, int sw, int sh, 
 {
     for_each_chunk(batch, [&](int b0, int nb) {
         const FrameSource fr = src.from(b0, sw, sh);
-        if (src.fmt == SrcFormat::GRAY)   // (k_remap_lut_gray: bevwarp_gray.hip)
+        if (src.fmt == SrcFormat::GRAY16)   // (k_remap_lut_gray16: bevwarp_gray16.hip; no tie rule to choose)
+            gray16_launch_remap_lut(st, dim3((dw + 255) / 256, dh, nb), reinterpret_cast<const uint16_t *>(fr.packed), sw, sh, m1, m2, dw, dh,
+                                    reinterpret_cast<uint16_t *>(d_dst + (size_t)b0 * dw * dh * 2));
+        else if (src.fmt == SrcFormat::GRAY)   // (k_remap_lut_gray: bevwarp_gray.hip)
             gray_launch_remap_lut(st, dim3((dw + 255) / 256, dh, nb), fr.packed, sw, sh, m1, m2, dw, dh, d_dst + (size_t)b0 * dw * dh, ties_even);
         else if (src.yuv422())   // (k_remap_lut_yuv422: bevwarp_yuv422.hip)
             yuv422_launch_remap_lut(st, dim3((dw + 255) / 256, dh, nb), out_nv12, fr.packed, sw, sh, m1, m2, dw, dh,
@@ -753,7 +759,30 @@ int bevw_remapper_set_channels(bevw_remapper *r, int channels)
     if (channels == 1 && (r->input_format != BEVW_INPUT_BGR || r->out_nv12() || r->in_pitch_request != 0))
         return fail(BEVW_E_INVALID, "one channel needs BGR input, BGR output and no input pitch: the remapper's are %s, %s, %d",
                     input_format_name(r->input_format), r->out_nv12() ? "NV12" : "BGR", r->in_pitch_request);
+    if (channels != 1 && r->depth == 16)
+        return fail(BEVW_E_INVALID, "%d channels: the remapper's depth is 16 bits (bevw_remapper_set_depth), which is one channel", channels);
     return engine_set(*r, &EngineCore::channels, channels, r->plan_ready);
+}
+
+int bevw_remapper_set_depth(bevw_remapper *r, int bits)
+{
+    if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    if (bits != 8 && bits != 16) return fail(BEVW_E_INVALID, "depth must be 8 or 16 bits, got %d", bits);
+    if (bits == 16 && r->channels != 1)
+        return fail(BEVW_E_INVALID, "depth 16 needs one channel (bevw_remapper_set_channels): the remapper has %d", r->channels);
+    BEVW_TRY(engine_set(*r, &EngineCore::depth, bits, r->plan_ready));
+    // a remapper made under BEVW_COMPAT_REMAP has no plan (half-to-even ties are the per-pixel kernel's in 8 bits); its 16-bit steps take one
+    if (bits == 16 && !r->plan_ready && r->ties_even) {
+        BEVW_TRY(remapper_build_plan(r));
+        if (r->plan_ready) BEVW_TRY(r->apply_format());
+    }
+    return BEVW_OK;
+}
+
+int bevw_remapper_depth(bevw_remapper *r)
+{
+    if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    return r->depth;
 }
 
 int bevw_remapper_channels(bevw_remapper *r)
@@ -781,8 +810,11 @@ int bevw_remapper_set_input_pitch(bevw_remapper *r, int pitch_bytes)
 // a step its units do not serve (no list, BEVW_PLAN_UNITS=0) runs the per-pixel kernel.
 static int remap_step(bevw_remapper *r, const FrameSource &src, int batch, void *d_dst)
 {
-    const bool gray = r->channels == 1;
-    if (r->plan_ready && (!src.is_surf() || r->plan.src_pitch == src.pitch) && src.aligned4() && (((uintptr_t)d_dst) & 3u) == 0 &&
+    const bool gray = r->channels == 1, deep = gray && r->depth == 16;
+    if (deep && ((((uintptr_t)src.packed) | ((uintptr_t)d_dst)) & 1u))
+        return fail(BEVW_E_INVALID, "depth 16: the source and destination hold uint16 and must be 2-byte aligned");
+    // (the plan of a remapper made under BEVW_COMPAT_REMAP exists for its 16-bit steps alone)
+    if (r->plan_ready && (deep || !r->ties_even) && (!src.is_surf() || r->plan.src_pitch == src.pitch) && src.aligned4() && (((uintptr_t)d_dst) & 3u) == 0 &&
         (!(r->out_nv12() || gray) || r->dw % 4 == 0)) {
         PlanStep step;
         step.src = src; step.batch = batch; step.out = (uint8_t *)d_dst;

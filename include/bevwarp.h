@@ -447,6 +447,19 @@ int bevw_remapper_set_output_format(bevw_remapper *r, int format);
  * BEVW_OUTPUT_NV12, an input pitch and the surface entry points are refused; bevw_last_error() names the channel count each time. */
 int bevw_remapper_set_channels(bevw_remapper *r, int channels);
 int bevw_remapper_channels(bevw_remapper *r);   /* 1 or 3 */
+/* 16-bit single-channel images (depth maps, thermal and NIR planes, HDR luma, label maps): what cv2.remap does with an (H, W) uint16
+ * array.  bits = 8 (the default) or 16; 16 needs channels == 1.  With 16, bevw_remap and bevw_remap_device read src as
+ * [batch][src_h][src_w] little-endian uint16 and write dst as [batch][dst_h][dst_w] uint16, dense rows: INTER_LINEAR, BORDER_CONSTANT 0,
+ * byte for byte cv2.remap on the uint16 array.  cv2.remap interpolates CV_16U with float32 weights, a float32 sum from left to right,
+ * cvRound and saturation, not in the fixed point of CV_8U: BEVW_COMPAT_REMAP, which selects the tie rule of the fixed-point path, has no
+ * effect, and the result rounds to nearest even in both modes.  Any remapper takes a depth (fisheye, pinhole, from maps).  The step runs
+ * the unit kernel where src_w % 4 == 0, dst_w % 4 == 0 and both device pointers are 4-byte aligned, and the per-pixel kernel otherwise
+ * (bevw_remapper_last_path tells); d_src or d_dst at an odd address is refused (BEVW_E_INVALID) with nothing written.  The setter waits
+ * for every queued step of the remapper.  Refused (BEVW_E_INVALID, bevw_last_error() names the depth): any other bit count,
+ * bevw_remapper_set_depth(r, 16) on a three-channel remapper, bevw_remapper_set_channels(r, 3) on a 16-bit one; what a one-channel
+ * remapper refuses stays refused. */
+int bevw_remapper_set_depth(bevw_remapper *r, int bits);
+int bevw_remapper_depth(bevw_remapper *r);      /* 8 or 16 */
 /* Which kernels served the remapper's last step, whatever its channel count (a diagnostic: tests assert it instead of assuming it). */
 #define BEVW_PATH_NONE 0        /* no step yet */
 #define BEVW_PATH_UNITS 1       /* the unit kernel (+ the per-tap kernel for the base tiles whose footprints touch the frame border) */
