@@ -54,6 +54,7 @@ class Fisheye:
         self._remapper = None
         self._remapper_gray = None   # the same maps in one channel (InCalibrator.undistort on a [FH, FW] image), made on first use
         self._remapper_gray16 = None   # ... and in one channel of 16 bits (a uint16 [FH, FW] image)
+        self._remapper_nearest = {}    # ... and in nearest-neighbour mode, per depth (undistort(mask, interpolation='nearest'))
         self._device = 0
 
     def _get_camera_mat_dst(self, camera_mat):
@@ -66,6 +67,8 @@ class Fisheye:
         return camera_mat_dst
 
     def _release(self):
+        for depth in list(self._remapper_nearest):
+            lib().bevw_remapper_destroy(self._remapper_nearest.pop(depth))
         if self._remapper_gray16:
             lib().bevw_remapper_destroy(self._remapper_gray16)
             self._remapper_gray16 = None
@@ -76,11 +79,14 @@ class Fisheye:
             lib().bevw_remapper_destroy(self._remapper)
             self._remapper = None
 
-    def _gray_remapper(self, depth=8):
+    def _gray_remapper(self, depth=8, nearest=False):
         """A one-channel remapper over the camera's own maps (bevw_remapper_from_maps + bevw_remapper_set_channels); depth=16: one of its
-        own for uint16 planes (bevw_remapper_set_depth)."""
+        own for uint16 planes (bevw_remapper_set_depth); nearest: one of its own per depth that picks the nearest texel
+        (bevw_remapper_set_interpolation)."""
         slot = "_remapper_gray16" if depth == 16 else "_remapper_gray"
-        if getattr(self, slot) is None:
+        if nearest and depth in self._remapper_nearest:
+            return self._remapper_nearest[depth]
+        if nearest or getattr(self, slot) is None:
             d = self.data
             r = C.c_void_p()
             check(lib().bevw_remapper_from_maps(self._device, int(args.FRAME_WIDTH), int(args.FRAME_HEIGHT), ptr(d.map1), ptr(d.map2),
@@ -89,9 +95,14 @@ class Fisheye:
                 check(lib().bevw_remapper_set_channels(r, 1))
                 if depth == 16:
                     check(lib().bevw_remapper_set_depth(r, 16))
+                if nearest:
+                    check(lib().bevw_remapper_set_interpolation(r, _ffi.INTER_NEAREST))
             except Exception:
                 lib().bevw_remapper_destroy(r)
                 raise
+            if nearest:
+                self._remapper_nearest[depth] = r
+                return r
             setattr(self, slot, r)
         return getattr(self, slot)
 
@@ -170,23 +181,27 @@ class InCalibrator:
         self.camera._get_undistort_maps()
         return d
 
-    def undistort(self, img):
+    def undistort(self, img, interpolation='linear'):
         """intrinsicCalib.py:193-195: cv2.remap(img, data.map1, data.map2, cv2.INTER_LINEAR).  A uint8 [FH, FW] image gives [h, w], as
-        cv2.remap does for a single plane; a uint16 [FH, FW] image (a depth map, a thermal plane) gives uint16 [h, w]."""
+        cv2.remap does for a single plane; a uint16 [FH, FW] image (a depth map, a thermal plane) gives uint16 [h, w].
+        interpolation='nearest' on such a plane (a class-ID map, an instance-ID map, a mask): cv2.remap(..., cv2.INTER_NEAREST)."""
         cam = self.camera
+        nearest = _ffi.interpolation(interpolation) == _ffi.INTER_NEAREST
         if cam._remapper is None:
             raise Exception("no calibration: call set_calibration(K, D) first")
+        if nearest and np.ndim(img) != 2:
+            raise Exception("interpolation='nearest' takes a uint8 or uint16 [FH, FW] plane")
         if np.ndim(img) == 2:
             img = np.ascontiguousarray(img)
             if img.dtype == np.uint16 and img.shape == (args.FRAME_HEIGHT, args.FRAME_WIDTH):
                 out = np.empty(cam.data.map2.shape, np.uint16)
-                check(lib().bevw_remap(cam._gray_remapper(16), ptr(img), 1, ptr(out)))
+                check(lib().bevw_remap(cam._gray_remapper(16, nearest), ptr(img), 1, ptr(out)))
                 return out
             if img.dtype != np.uint8 or img.shape != (args.FRAME_HEIGHT, args.FRAME_WIDTH):
                 raise Exception("image is {} {}x{}, FRAME is uint8 {}x{}".format(img.dtype, img.shape[1], img.shape[0], args.FRAME_WIDTH,
                                                                               args.FRAME_HEIGHT))
             out = np.empty(cam.data.map2.shape, np.uint8)
-            check(lib().bevw_remap(cam._gray_remapper(), ptr(img), 1, ptr(out)))
+            check(lib().bevw_remap(cam._gray_remapper(8, nearest), ptr(img), 1, ptr(out)))
             return out
         img = _ffi.as_u8_image(img)
         if img.shape[:2] != (args.FRAME_HEIGHT, args.FRAME_WIDTH):

@@ -49,7 +49,7 @@ class Undistorter:
     """The map set of one (K, D, size, scales, offsets) on the device."""
 
     def __init__(self, K, D, width, height, focalscale=1.0, sizescale=1.0, offset_h=0.0, offset_v=0.0, device=0, input_format='bgr',
-                 output_format='bgr', input_pitch=None, channels=3, depth=8):
+                 output_format='bgr', input_pitch=None, channels=3, depth=8, interpolation='linear'):
         """input_format: 'bgr' (images [height, width, 3]) or 'nv12' ([height*3//2, width]: Y plane, then the interleaved U / V plane; the
         result is what cv2.remap gives for cv2.cvtColor(img, cv2.COLOR_YUV2BGR_NV12) -- bevw_remapper_set_input_format in include/bevwarp.h),
         'yuyv' / 'uyvy' ([height, width, 2]: packed 4:2:2 as a live camera delivers it; cv2.COLOR_YUV2BGR_YUY2 / _UYVY; an even width).
@@ -60,12 +60,18 @@ class Undistorter:
         channels: 3, or 1 for single uint8 planes (images [height, width], results [out_h, out_w]: what cv2.remap gives for a 2-D array --
         bevw_remapper_set_channels); one channel is 'bgr' in and out without a pitch.
         depth: 8, or 16 with channels=1 for single uint16 planes (depth maps, thermal and NIR planes, HDR luma, label maps: images uint16
-        [height, width], results uint16 [out_h, out_w]: what cv2.remap gives for a 2-D uint16 array -- bevw_remapper_set_depth)."""
+        [height, width], results uint16 [out_h, out_w]: what cv2.remap gives for a 2-D uint16 array -- bevw_remapper_set_depth).
+        interpolation: 'linear', or 'nearest' with channels=1 for class-ID maps, instance-ID maps and masks, at either depth: what
+        cv2.remap(..., cv2.INTER_NEAREST) gives with the same fixed-point maps, every result value one of the image's own or 0
+        (bevw_remapper_set_interpolation); cv2's values 1 / 0 are taken too."""
         self._r = None
         self.channels = _ffi.channels(channels)
         self.depth = _ffi.depth(depth)
         if self.depth == 16 and self.channels != 1:
             raise Exception("depth=16 needs channels=1")
+        self.interpolation = 'nearest' if _ffi.interpolation(interpolation) == _ffi.INTER_NEAREST else 'linear'
+        if self.interpolation == 'nearest' and self.channels != 1:
+            raise Exception("interpolation='nearest' needs channels=1")
         formats = _ffi.INPUT_FORMATS
         _ffi.input_format(input_format)
         out_formats = {'bgr': _ffi.OUTPUT_BGR, 'nv12': _ffi.OUTPUT_NV12}
@@ -94,6 +100,8 @@ class Undistorter:
                 check(lib().bevw_remapper_set_channels(r, 1))
             if self.depth == 16:
                 check(lib().bevw_remapper_set_depth(r, 16))
+            if self.interpolation == 'nearest':
+                check(lib().bevw_remapper_set_interpolation(r, _ffi.INTER_NEAREST))
         except Exception:
             self.close()
             raise

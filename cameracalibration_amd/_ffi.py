@@ -43,13 +43,21 @@ def depth(bits) -> int:
     return int(bits)
 
 
+def interpolation(v) -> int:
+    """The interpolation of a one-channel remapper (bevw_remapper_set_interpolation): 'linear' / 'nearest', or cv2's own values 1 / 0."""
+    if isinstance(v, bool) or not isinstance(v, (str, int)) or v not in ('linear', 'nearest', 0, 1):
+        raise Exception("interpolation should be linear/nearest")
+    return {'nearest': INTER_NEAREST, 'linear': INTER_LINEAR}.get(v, v)
+
+
 def frame_shape(name, height: int, width: int):
     """Shape of one camera frame of a format: (H, W, 3) 'bgr', (H*3//2, W) 'nv12', (H, W, 2) 'yuyv' / 'uyvy'."""
     if name == 'nv12':
         return (height * 3 // 2, width)
     return (height, width, 2 if name in ('yuyv', 'uyvy') else 3)
 PATH_NONE, PATH_UNITS, PATH_PER_PIXEL = 0, 1, 2      # bevw_last_path, bevw_remapper_last_path
-OUTPUT_BGR, OUTPUT_NV12 = 0, 1                       # bevw_set_output_format, bevw_remapper_set_output_format
+INTER_NEAREST, INTER_LINEAR = 0, 1                   # bevw_remapper_set_interpolation (cv2's own values)
+OUTPUT_BGR, OUTPUT_NV12 = 0, 1                     # bevw_set_output_format, bevw_remapper_set_output_format
 COMPAT_FILLPOLY, COMPAT_ADDWEIGHTED, COMPAT_WARP, COMPAT_REMAP = 0, 1, 2, 3   # bevw_set_compat keys (include/bevwarp.h)
 
 
@@ -146,6 +154,8 @@ SIGNATURES = {
     "bevw_remapper_channels": (_i, [_vp]),
     "bevw_remapper_set_depth": (_i, [_vp, _i]),
     "bevw_remapper_depth": (_i, [_vp]),
+    "bevw_remapper_set_interpolation": (_i, [_vp, _i]),
+    "bevw_remapper_interpolation": (_i, [_vp]),
     "bevw_remapper_last_path": (_i, [_vp]),
     "bevw_remap_surfaces_device": (_i, [_vp, _vp, _i, _vp]),
     "bevw_remap_surface_table_device": (_i, [_vp, _vp, _i, _vp]),

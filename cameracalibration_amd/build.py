@@ -2,11 +2,12 @@
 
     python -m cameracalibration_amd.build [--force]
 
-Eight translation units -- bevwarp.hip (handles, table builders, tools, the camera-per-GPU exchange), bevwarp_plan.hip (the tile plan
+Nine translation units -- bevwarp.hip (handles, table builders, tools, the camera-per-GPU exchange), bevwarp_plan.hip (the tile plan
 and its per-frame kernels), bevwarp_jpeg.hip (the JPEG codec), bevwarp_yuv422.hip (every kernel that reads packed 4:2:2 camera frames:
 FORMAT_UNITS), bevwarp_gray.hip (every kernel of the one-channel remapper: CHANNEL_UNITS) and bevwarp_gray_stitch.hip (every kernel of the
 one-channel stitch: STITCH_CHANNEL_UNITS) and bevwarp_moving.hip (the stitch with a homography per frame set: MOVING_UNITS) and bevwarp_gray16.hip (every kernel of the 16-bit
-one-channel remapper: DEPTH_UNITS) -- are compiled in parallel into objects under csrc/build/ and linked;
+one-channel remapper: DEPTH_UNITS) and bevwarp_nearest.hip (every kernel of the
+nearest-neighbour one-channel remapper: INTERP_UNITS) -- are compiled in parallel into objects under csrc/build/ and linked;
 a unit is recompiled when its source, ANY header under csrc/ or the flag set changed.  The shared object is written next to this file (in-tree: it travels
 to the GPU box with the repo snapshot and is git-ignored).  -ffp-contract=off is REQUIRED: the arithmetic being reproduced has no fused
 multiply-add.
@@ -40,7 +41,11 @@ BUILD_UNITS = ALL_UNITS + MOVING_UNITS
 # ... and the 16-bit one-channel remapper (bevw_remapper_set_depth): every kernel named *gray16*.  A list of its own again: the seven units
 # above compile to the code objects they were before this one existed
 DEPTH_UNITS = ["bevwarp_gray16.hip"]
-LINK_UNITS = BUILD_UNITS + DEPTH_UNITS   # what is compiled and linked
+LINK_UNITS = BUILD_UNITS + DEPTH_UNITS
+# ... and the nearest-neighbour one-channel remapper (bevw_remapper_set_interpolation): every kernel named *nn8* / *nn16*.  A list of its own
+# once more: the eight units above compile to the code objects they were before this one existed
+INTERP_UNITS = ["bevwarp_nearest.hip"]
+LINKED = LINK_UNITS + INTERP_UNITS   # what is compiled and linked
 
 
 def _headers():
@@ -77,12 +82,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
         force = True
     jobs = []
     hdrs = _headers()
-    for src in LINK_UNITS:
+    for src in LINKED:
         obj = os.path.join(OBJ, src.replace(".hip", ".o"))
         deps = [os.path.join(CSRC, src)] + hdrs + [me]
         if force or _newer(obj, deps):
             jobs.append([hipcc] + CFLAGS + EXTRA + ["-c", os.path.join(CSRC, src), "-o", obj])
-    objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in LINK_UNITS]
+    objs = [os.path.join(OBJ, s.replace(".hip", ".o")) for s in LINKED]
     if not jobs and not _newer(LIB, objs):
         return LIB
 
@@ -91,7 +96,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)
 
-    with ThreadPoolExecutor(max_workers=len(LINK_UNITS)) as pool:
+    with ThreadPoolExecutor(max_workers=len(LINKED)) as pool:
         list(pool.map(run, jobs))
     with open(stamp, "w") as f:
         f.write(flags)

@@ -28,6 +28,7 @@
 #include "bevw_yuv422.h"
 #include "bevw_gray.h"
 #include "bevw_gray16.h"
+#include "bevw_nearest.h"
 #include "bevw_gray_stitch.h"
 
 namespace bevw {
@@ -630,6 +631,8 @@ static inline RouteIn plan_route_in(const Plan &p, const PlanStep &s, const Plan
 // base tiles no unit owns (bevwarp_gray.hip).  Images of bw x bh bytes: bw % 4 == 0 and a 4-byte aligned `out` (a quad is one dword store).
 // SrcFormat::GRAY16 (bevw_remapper_set_depth): the same route, lists and conditions on k_units_gray16 and k_stitch_plan_gray16
 // (bevwarp_gray16.hip) -- images of bw x bh uint16, a quad is one 8-byte store at a multiple of 8 bytes from `out`.
+// A nearest step (PlanStep::nearest: bevw_remapper_set_interpolation): the same again on k_units_nn8 / nn16 and k_tiles_nn8 / nn16
+// (bevwarp_nearest.hip).
 static inline hipError_t plan_gray_step(const Plan &p, hipStream_t st, const PlanStep &s, const PlanTuning &tune, const Route &rt)
 {
     if (!rt.use_units || rt.units != kLayoutGray || p.pitch != p.bw || p.bw % 4 != 0 || (((uintptr_t)s.out) & 3u) != 0 || s.car || s.blend)
@@ -640,13 +643,15 @@ static inline hipError_t plan_gray_step(const Plan &p, hipStream_t st, const Pla
     a.set_stride = rt.set_stride;
     a.un_gsrc = static_cast<const uint32_t *>(p.units[kLayoutGray]);
     const bool deep = p.fmt == SrcFormat::GRAY16;
-    if (deep) gray16_launch_units(a, st);
+    if (s.nearest) nearest_launch_units(a, st, deep);
+    else if (deep) gray16_launch_units(a, st);
     else gray_launch_units(a, st);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || p.n_slow == 0) return e;
     a.tile_list = static_cast<const uint32_t *>(p.list_slow); a.nlist = p.n_slow; a.ngroups = (p.n_slow + 3) / 4;
     a.set_stride = 0;
-    if (deep) gray16_launch_stitch_plan(a, st);
+    if (s.nearest) nearest_launch_tiles(a, st, deep);
+    else if (deep) gray16_launch_stitch_plan(a, st);
     else gray_launch_stitch_plan(a, st);
     return hipGetLastError();
 }

@@ -166,6 +166,9 @@ struct PlanStep {
     // set, group lists p.units[kLayoutCompact]), the per-tap kernel serves what no unit owns from the RAW frames with the luminance round trip per
     // tap (deltas, tab); everything on the per-tap kernel when the units cannot run
     const uint8_t *scratch = nullptr;
+    // a one-channel remapper's step in nearest-neighbour mode (bevw_remapper_set_interpolation): the same route and lists on the kernels of
+    // bevwarp_nearest.hip, at the plan's depth
+    bool nearest = false;
 };
 int plan_stitch(Plan &p, hipStream_t st, const PlanStep &step);
 // whether the unit kernel serves that step (plan_route on the plan's lists and the step's pointers): what a remapper records as the path of

@@ -20,6 +20,7 @@
 #include "bevw_yuv422.h"
 #include "bevw_gray.h"
 #include "bevw_gray16.h"
+#include "bevw_nearest.h"
 #include "bevw_gray_stitch.h"
 #include "bevw_moving.h"
 #include "bevw_comm.h"
@@ -368,6 +369,7 @@ struct EngineCore {
     int in_pitch_request = 0;            // 0: the frame width
     int channels = 3;                    // 1: 8UC1 frames and images (bevw_remapper_set_channels, bevw_set_channels; BGR in and out, no input pitch)
     int depth = 8;                       // 16: 16UC1 frames and images of a remapper (bevw_remapper_set_depth; needs channels == 1)
+    int interpolation = BEVW_INTER_LINEAR;   // BEVW_INTER_NEAREST: a remapper picks cv2's nearest texel (bevw_remapper_set_interpolation; needs channels == 1)
     SrcFormat fmt() const { return channels == 1 ? (depth == 16 ? SrcFormat::GRAY16 : SrcFormat::GRAY) : (SrcFormat)input_format; }
     bool nv12() const { return input_format == BEVW_INPUT_NV12; }
     bool yuv422() const { return src_is_yuv422(fmt()); }   // packed 4:2:2: YUYV / UYVY
@@ -505,6 +507,7 @@ struct bevw_remapper : EngineCore {
     // the plan: a single-image contributor plan (same kernels as the BEV stitch, one frame per set)
     bool plan_ready = false;
     int ties_even = 0;    // BEVW_COMPAT_REMAP at creation: half-to-even ties -> the per-pixel kernel (the plan's arithmetic rounds half up)
+    bool nearest() const { return interpolation == BEVW_INTER_NEAREST; }
 };
 
 // cv2.remap as a 1-camera stitch: every destination pixel has exactly one contributor with mask 255.
@@ -512,8 +515,9 @@ static int remapper_build_plan(bevw_remapper *r)
 {
     static const int use_plan = env_int("BEVW_REMAP_PLAN", 1);
     r->plan_ready = false;
-    // (a 16-bit remapper has one tie rule, its float arithmetic's, and takes the plan in both modes: bevw_remapper_set_depth builds it then)
-    if (!use_plan || (r->ties_even && r->depth != 16)) return BEVW_OK;
+    // (a 16-bit remapper has one tie rule, its float arithmetic's, and takes the plan in both modes: bevw_remapper_set_depth builds it then;
+    // a nearest one has no tie at all: bevw_remapper_set_interpolation)
+    if (!use_plan || (r->ties_even && r->depth != 16 && !r->nearest())) return BEVW_OK;
     const size_t npx = (size_t)r->dw * r->dh;
     BEVW_TRY(r->ones.reserve(npx));
     HIP_TRY(hipMemsetAsync(r->ones.p, 0xff, npx, r->stream));
@@ -556,11 +560,14 @@ static int remapper_finish(bevw_remapper *r, int s, bevw_remapper **out)
 
 // k_remap_lut over `batch` images of `src` (one frame per set); out_nv12: the destinations are dense NV12 images (bevw_remapper_set_output_format)
 static int remap_launch(hipStream_t st, const FrameSource &src, int sw, int sh, const int16_t *m1, const uint16_t *m2,
-                        int dw, int dh, int batch, uint8_t *d_dst, int ties_even, bool out_nv12)
+                        int dw, int dh, int batch, uint8_t *d_dst, int ties_even, bool out_nv12, bool nearest = false)
 {
     for_each_chunk(batch, [&](int b0, int nb) {
         const FrameSource fr = src.from(b0, sw, sh);
-        if (src.fmt == SrcFormat::GRAY16)   // (k_remap_lut_gray16: bevwarp_gray16.hip; no tie rule to choose)
+        if (nearest) {   // (k_remap_nn8 / k_remap_nn16: bevwarp_nearest.hip; one channel, no tie rule to choose)
+            const bool deep = src.fmt == SrcFormat::GRAY16;
+            nearest_launch_remap(st, dim3((dw + 255) / 256, dh, nb), deep, fr.packed, sw, sh, m1, m2, dw, dh, d_dst + (size_t)b0 * dw * dh * (deep ? 2 : 1));
+        } else if (src.fmt == SrcFormat::GRAY16)   // (k_remap_lut_gray16: bevwarp_gray16.hip; no tie rule to choose)
             gray16_launch_remap_lut(st, dim3((dw + 255) / 256, dh, nb), reinterpret_cast<const uint16_t *>(fr.packed), sw, sh, m1, m2, dw, dh,
                                     reinterpret_cast<uint16_t *>(d_dst + (size_t)b0 * dw * dh * 2));
         else if (src.fmt == SrcFormat::GRAY)   // (k_remap_lut_gray: bevwarp_gray.hip)
@@ -761,6 +768,8 @@ int bevw_remapper_set_channels(bevw_remapper *r, int channels)
                     input_format_name(r->input_format), r->out_nv12() ? "NV12" : "BGR", r->in_pitch_request);
     if (channels != 1 && r->depth == 16)
         return fail(BEVW_E_INVALID, "%d channels: the remapper's depth is 16 bits (bevw_remapper_set_depth), which is one channel", channels);
+    if (channels != 1 && r->nearest())
+        return fail(BEVW_E_INVALID, "%d channels: the remapper's interpolation is nearest (bevw_remapper_set_interpolation), which is one channel", channels);
     return engine_set(*r, &EngineCore::channels, channels, r->plan_ready);
 }
 
@@ -783,6 +792,28 @@ int bevw_remapper_depth(bevw_remapper *r)
 {
     if (!r) return fail(BEVW_E_INVALID, "null remapper");
     return r->depth;
+}
+
+int bevw_remapper_set_interpolation(bevw_remapper *r, int interpolation)
+{
+    if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    if (interpolation != BEVW_INTER_NEAREST && interpolation != BEVW_INTER_LINEAR)
+        return fail(BEVW_E_INVALID, "interpolation must be BEVW_INTER_NEAREST (0) or BEVW_INTER_LINEAR (1), got %d", interpolation);
+    if (interpolation == BEVW_INTER_NEAREST && r->channels != 1)
+        return fail(BEVW_E_INVALID, "nearest interpolation needs one channel (bevw_remapper_set_channels): the remapper has %d", r->channels);
+    BEVW_TRY(engine_set(*r, &EngineCore::interpolation, interpolation, r->plan_ready));
+    // a remapper made under BEVW_COMPAT_REMAP has no plan (half-to-even ties are the per-pixel kernel's in 8 bits); its nearest steps take one
+    if (r->nearest() && !r->plan_ready && r->ties_even) {
+        BEVW_TRY(remapper_build_plan(r));
+        if (r->plan_ready) BEVW_TRY(r->apply_format());
+    }
+    return BEVW_OK;
+}
+
+int bevw_remapper_interpolation(bevw_remapper *r)
+{
+    if (!r) return fail(BEVW_E_INVALID, "null remapper");
+    return r->interpolation;
 }
 
 int bevw_remapper_channels(bevw_remapper *r)
@@ -810,14 +841,16 @@ int bevw_remapper_set_input_pitch(bevw_remapper *r, int pitch_bytes)
 // a step its units do not serve (no list, BEVW_PLAN_UNITS=0) runs the per-pixel kernel.
 static int remap_step(bevw_remapper *r, const FrameSource &src, int batch, void *d_dst)
 {
-    const bool gray = r->channels == 1, deep = gray && r->depth == 16;
+    const bool gray = r->channels == 1, deep = gray && r->depth == 16, nearest = gray && r->nearest();
     if (deep && ((((uintptr_t)src.packed) | ((uintptr_t)d_dst)) & 1u))
         return fail(BEVW_E_INVALID, "depth 16: the source and destination hold uint16 and must be 2-byte aligned");
-    // (the plan of a remapper made under BEVW_COMPAT_REMAP exists for its 16-bit steps alone)
-    if (r->plan_ready && (deep || !r->ties_even) && (!src.is_surf() || r->plan.src_pitch == src.pitch) && src.aligned4() && (((uintptr_t)d_dst) & 3u) == 0 &&
+    // (the plan of a remapper made under BEVW_COMPAT_REMAP exists for its 16-bit and its nearest steps alone; the plan's entries do not carry
+    // the wrap of cv2's short, which a nearest step on a source beyond 32768 texels can show: the per-pixel kernel serves those)
+    const bool wraps = nearest && (r->fw > 32768 || r->fh > 32768);
+    if (r->plan_ready && (deep || nearest || !r->ties_even) && !wraps && (!src.is_surf() || r->plan.src_pitch == src.pitch) && src.aligned4() && (((uintptr_t)d_dst) & 3u) == 0 &&
         (!(r->out_nv12() || gray) || r->dw % 4 == 0)) {
         PlanStep step;
-        step.src = src; step.batch = batch; step.out = (uint8_t *)d_dst;
+        step.src = src; step.batch = batch; step.out = (uint8_t *)d_dst; step.nearest = nearest;
         const bool units = plan_units_serve(r->plan, step);
         if (units || !gray) {
             r->last_path = units ? BEVW_PATH_UNITS : BEVW_PATH_PER_PIXEL;
@@ -826,7 +859,7 @@ static int remap_step(bevw_remapper *r, const FrameSource &src, int batch, void 
     }
     r->last_path = BEVW_PATH_PER_PIXEL;
     return remap_launch(r->stream, src, r->fw, r->fh, r->map1.as<int16_t>(), r->map2.as<uint16_t>(), r->dw, r->dh, batch, (uint8_t *)d_dst,
-                        r->ties_even, r->out_nv12());
+                        r->ties_even, r->out_nv12(), nearest);
 }
 
 int bevw_remap_surface_table_device(bevw_remapper *r, const void *d_surfaces, int batch, void *d_dst)

@@ -460,6 +460,26 @@ int bevw_remapper_channels(bevw_remapper *r);   /* 1 or 3 */
  * remapper refuses stays refused. */
 int bevw_remapper_set_depth(bevw_remapper *r, int bits);
 int bevw_remapper_depth(bevw_remapper *r);      /* 8 or 16 */
+/* Nearest-neighbour remapping of single-channel images (class-ID maps, instance-ID maps, validity masks: planes whose values must not be
+ * blended): what cv2.remap(src, map1, map2, cv2.INTER_NEAREST) does with an (H, W) uint8 or uint16 array and fixed-point maps (map1
+ * CV_16SC2, a non-empty map2 CV_16UC1), BORDER_CONSTANT 0.  With a = map2 & 1023, fx = a & 31, fy = a >> 5:
+ *     x = (int16)(map1.x + (fx >= 16)),  y = (int16)(map1.y + (fy >= 16)),  dst = inside the frame ? src[y][x] : 0
+ * -- the sum is stored into a short and wraps (32767 + 1 -> -32768), which only a source beyond 32768 texels can show.  There is no
+ * rounding, no tie rule and no depth-dependent arithmetic: BEVW_COMPAT_REMAP has no effect, and the 16-bit result is the same pick in
+ * uint16.  A pixel whose bilinear footprint straddles the frame border is its nearest texel where that lies inside, not 0.  The values are
+ * cv2's own; BEVW_INTER_LINEAR is the default.  Nearest needs channels == 1; any remapper takes it (fisheye, pinhole, from maps), at depth 8
+ * or 16, in either order with bevw_remapper_set_depth.  bevw_remap and bevw_remap_device keep their layouts: dense rows, one uint8 or
+ * uint16 per pixel.  The step runs the unit kernel where src_w % 4 == 0, dst_w % 4 == 0, both device pointers are 4-byte aligned and
+ * src_w, src_h <= 32768, in both BEVW_COMPAT_REMAP modes, and the per-pixel kernel otherwise (bevw_remapper_last_path tells): at 8 bits any
+ * byte alignment is served, at 16 bits an odd d_src or d_dst stays refused with nothing written.  Going back to BEVW_INTER_LINEAR restores
+ * the linear dispatch exactly.  The setter waits for every queued step of the remapper.  Refused (BEVW_E_INVALID, bevw_last_error() names
+ * the interpolation): any other value, BEVW_INTER_NEAREST on a three-channel remapper, bevw_remapper_set_channels(r, 3) on a nearest one;
+ * what a one-channel remapper refuses stays refused.  The rule restates OpenCV's RemapInvoker for fixed-point maps and is not pinned
+ * against a real cv2 build here (tests/golden/make_nearest_goldens_with_cv2.py writes the vectors that would). */
+#define BEVW_INTER_NEAREST 0   /* cv2's own values */
+#define BEVW_INTER_LINEAR  1   /* the default */
+int bevw_remapper_set_interpolation(bevw_remapper *r, int interpolation);
+int bevw_remapper_interpolation(bevw_remapper *r);   /* BEVW_INTER_NEAREST or BEVW_INTER_LINEAR */
 /* Which kernels served the remapper's last step, whatever its channel count (a diagnostic: tests assert it instead of assuming it). */
 #define BEVW_PATH_NONE 0        /* no step yet */
 #define BEVW_PATH_UNITS 1       /* the unit kernel (+ the per-tap kernel for the base tiles whose footprints touch the frame border) */
