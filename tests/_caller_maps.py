@@ -35,7 +35,11 @@ to read outside a frame.
   extremes     the identity (x, y) with 400 entries (drawn with replacement) replaced, both coordinates, by draws from
                {-32768, 32767, -1, -2, sw - 1, sw, sh - 1, sh}
   strip_w, strip_h, strip_w4   strip-shaped sources at the int16 limit (STRIPS has their sizes).  Per axis of size s, half of the
-               entries (drawn per pixel) come from {-2, -1, 0, 1, s - 2, s - 1, s, 32767, -32768}, the rest are uniform in [0, s); s = 32768 wraps to -32768."""
+               entries (drawn per pixel) come from {-2, -1, 0, 1, s - 2, s - 1, s, 32767, -32768}, the rest are uniform in [0, s); s = 32768 wraps to -32768.
+
+One more family stands outside FAMILIES (BATCH_LOOP_FAMILIES: the catalogue's per-family cases do not run it), for the batch-loop tests
+(tests/_batch_loops.py), which need whole units without any contributor AND base tiles on the frame border under one map:
+  swirl_wide   swirl at the scales ax = 1.6 sw / dw, ay = 1.6 sh / dh: the outer ring of the destination leaves the frame as a whole"""
 import numpy as np
 
 SMALL = (256, 192, 160, 120)          # sw, sh, dw, dh
@@ -45,6 +49,7 @@ LARGE_FAMILIES = ("rot45", "swirl", "jitter40", "minify8")
 FAMILIES = ("scatter", "transpose", "mirror", "rot180", "quadswap", "constant", "stripes", "rowshuffle", "colshuffle", "minify8", "magnify16",
             "rot45", "swirl", "jitter40", "corner", "extremes", "strip_w", "strip_h", "strip_w4")
 GENERAL = tuple(n for n in FAMILIES if n not in STRIPS)   # the families that take any size
+BATCH_LOOP_FAMILIES = ("swirl_wide",)                     # seeded behind FAMILIES; no case list above enumerates them
 SEED = 20
 
 
@@ -56,7 +61,7 @@ def sizes(name):
 
 
 def family(name, sw, sh, dw, dh, seed=SEED):
-    rng = np.random.default_rng([int(seed), FAMILIES.index(name)])
+    rng = np.random.default_rng([int(seed), (FAMILIES + BATCH_LOOP_FAMILIES).index(name)])
     map2 = rng.integers(0, 65536, (dh, dw)).astype(np.uint16)
     y, x = np.mgrid[0:dh, 0:dw]
     if name == "scatter":
@@ -86,10 +91,11 @@ def family(name, sw, sh, dw, dh, seed=SEED):
     elif name == "rot45":
         u, v, c = x - dw / 2, y - dh / 2, np.sqrt(0.5)
         sx, sy = np.floor(sw / 2 + c * (u - v)), np.floor(sh / 2 + c * (u + v))
-    elif name == "swirl":
+    elif name in ("swirl", "swirl_wide"):
         u, v = x - dw / 2, y - dh / 2
         t = 3.5 * (1 - np.hypot(u, v) / (np.hypot(dw, dh) / 2)) ** 2
-        ax, ay = 0.97 * sw / dw, 0.97 * sh / dh
+        scale = 0.97 if name == "swirl" else 1.6
+        ax, ay = scale * sw / dw, scale * sh / dh
         sx, sy = np.floor(sw / 2 + ax * (u * np.cos(t) - v * np.sin(t))), np.floor(sh / 2 + ay * (u * np.sin(t) + v * np.cos(t)))
     elif name == "jitter40":
         hit = rng.random((dh, dw)) < 0.4

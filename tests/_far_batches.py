@@ -34,7 +34,17 @@ REMAP_SIZE = (64, 48, 248, 250)                                # sw, sh, dw, dh 
 REMAP_FAMILY = "swirl"                                         # of tests/_caller_maps.py: smooth inside, leaves the frame at the corners
 COUNT_SIZE, COUNT_BATCH, COUNT_FAMILY = (8, 8, 8, 8), 65540, "scatter"   # remap_launch's cut: one grid of 65535 images and five more
 
-Case = collections.namedtuple("Case", "name kind geometry inp out schedule mode env")
+# One-channel cases (tests/test_batch_loops_gpu.py covers their batch loops below 4 GiB): 62,000 bytes per image of the grey stitch on T,
+# 124,000 per 16-bit image of the far remapper; depth / nearest describe a one-channel remapper.
+# The moving stitch (bevw_run_homographies_device) runs 65,540 frame sets, five more than one grid: the cut of its launcher, whose second
+# span starts at `minv + b0 * 36`.  MOVING_CFG is the smallest rung of a ladder of geometries tried on an MI355X (16 x 12 -> 32 x 32 and
+# 64 x 64, 32 x 24 -> 64 x 64 and 124 x 126, 64 x 48 -> 124 x 126, each with a car and the rig scaled to it): every rung builds and its moving
+# step equals the oracle, so the smallest one serves -- 2,304 bytes per frame set, 3,072 per dense image, 352 MB on the device in all.
+MOVING_CFG = dict(FRAME_WIDTH=16, FRAME_HEIGHT=12, BEV_WIDTH=32, BEV_HEIGHT=32, CAR_WIDTH=8, CAR_HEIGHT=12, FOCAL_SCALE=1.0, SIZE_SCALE=2.0)
+MOVING_BATCH = 65540
+MOVING_RIGS = 7                                                # frame set b on rig b % 7 of tests/_batch_loops.moving_rigs
+
+Case = collections.namedtuple("Case", "name kind geometry inp out schedule mode env depth nearest", defaults=(8, False))
 
 
 def cases():
@@ -48,6 +58,13 @@ def cases():
     c.append(Case("T bgr->nv12 plan direct", "stitch", "T", "bgr", "nv12", "plan", "direct", {}))
     c.append(Case("remap far output", "remap", None, "bgr", "bgr", None, None, {}))
     c.append(Case("remap 65540 images", "remap_count", None, "bgr", "bgr", None, None, {"BEVW_REMAP_PLAN": "0"}))
+    for schedule in ("plan", "per_pixel"):
+        c.append(Case("T gray->gray %s" % schedule, "stitch_gray", "T", "gray", "gray", schedule, "direct", {}))
+    c.append(Case("remap gray16 far output", "plane", None, "gray", "gray", None, None, {}, 16, False))
+    c.append(Case("remap nn16 far output", "plane", None, "gray", "gray", None, None, {}, 16, True))
+    c.append(Case("remap gray16 65540 images", "plane_count", None, "gray", "gray", None, None, {"BEVW_REMAP_PLAN": "0"}, 16, False))
+    c.append(Case("remap nn8 65540 images", "plane_count", None, "gray", "gray", None, None, {"BEVW_REMAP_PLAN": "0"}, 8, True))
+    c.append(Case("moving 65540 sets", "moving", None, "bgr", "bgr", None, "direct", {}))
     return c
 
 
@@ -139,3 +156,14 @@ def pool(cfg, inp):
 
 def remap_pool(size):
     return np.random.default_rng([SEED, size[0], size[1]]).integers(0, 256, (POOL, size[1], size[0], 3), dtype=np.uint8)
+
+
+def plane_pool(size, depth):
+    """POOL distinct one-channel frames of uniform random texels over the full range of the depth."""
+    return np.random.default_rng([SEED, size[0], size[1], depth]).integers(0, 1 << depth, (POOL, size[1], size[0]), dtype=np.uint8 if depth == 8 else np.uint16)
+
+
+def gray_pool(cfg):
+    """(POOL grey frame sets [POOL, 4, FH, FW]: channel 0 of the graded BGR pool, the grey car sprite)"""
+    bgr, _, car = pool(cfg, "bgr")
+    return np.ascontiguousarray(bgr[..., 0]), np.ascontiguousarray(car[..., 0])

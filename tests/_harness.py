@@ -327,8 +327,11 @@ def balance_slices(batch):
 
 
 def where(batch, b, balance=False, nb_env=0):
-    """'batch B, frame b: chunk c of n frames, last of its chunk or not' -- with the table's nb (nb_env: an explicit BEVW_PLAN_NB)."""
-    slices = [(n, nb) for n, nb, _, _ in SLICES[batch]] if balance else [(batch, PLAIN[batch][0])]
+    """'batch B, frame b: chunk c of n frames, last of its chunk or not' -- with the table's nb (nb_env: an explicit BEVW_PLAN_NB, or
+    {batch: nb} of a kernel that cuts its batches by a rule of its own: moving_nb)."""
+    if isinstance(nb_env, dict):
+        nb_env = nb_env[batch]
+    slices = [(n, nb) for n, nb, _, _ in SLICES[batch]] if balance else [(batch, PLAIN[batch][0] if batch in PLAIN else nb_env)]
     b0 = 0
     for k, (n, nb) in enumerate(slices):
         nb = min(nb_env, n) if nb_env else nb
@@ -397,9 +400,28 @@ def image_of(raw, nv12, bw, bh, pitch):
     return raw.reshape(bh * 3 // 2, pitch)[:, :bw] if nv12 else raw.reshape(bh, pitch, 3)[:, :bw]
 
 
-def run_batches(ffi, launch, sync, image_bytes, nv12, bw, bh, pitch, batches, want, what, balance=False, nb_env=0, black=False):
+def plane_of(raw, dtype, bw, bh, pitch):
+    """One device image of one channel (flat bytes, rows of `pitch` pixels of `dtype`) -> dense [bh, bw] of that type."""
+    return raw.view(dtype).reshape(bh, pitch)[:, :bw]
+
+
+def check_plane(got, want, fixed, what, under=0):
+    """One one-channel image [BH, BW] (uint8 or uint16) against the yardstick's at tolerance 0.  fixed: the pixels whose value no frame
+    decides (a remapper's footprints outside the frame, a stitch's pixels no camera covers), asserted on their own first: `under` there
+    -- 0, or an image [BH, BW] (the car sprite)."""
+    assert got.shape == want.shape and got.dtype == want.dtype, "%s: %s %s, want %s %s" % (what, got.shape, got.dtype, want.shape, want.dtype)
+    bad = got[fixed] != (under[fixed] if isinstance(under, np.ndarray) else under)
+    assert not bad.any(), "%s: %d pixels that no frame reaches are not %s (first at %s: %d)" % (
+        what, int(bad.sum()), "the car" if isinstance(under, np.ndarray) else "0", np.argwhere(fixed)[np.argmax(bad)].tolist(), int(got[fixed][bad][0]))
+    if not np.array_equal(got, want):
+        raise AssertionError("%s: %d of %d pixels differ; %s" % (what, int((got != want).sum()), got.size, first_difference(got, want)))
+
+
+def run_batches(ffi, launch, sync, image_bytes, nv12, bw, bh, pitch, batches, want, what, balance=False, nb_env=0, black=False, plane=None,
+                under=0):
     """launch(B, d_out) enqueues a step over the first B frame sets into d_out; every image of every batch against want = (bgr, nv12, none),
-    the sentinel fill before and the guard image after each run."""
+    the sentinel fill before and the guard image after each run.  plane: np.uint8 / np.uint16 -- the images are one-channel planes of that
+    type, want = (images [n, bh, bw], None, the pixels no frame reaches) and every image goes through check_plane(..., under)."""
     want_bgr, want_nv12, none = want
     d_out = ffi.DeviceBuffer((max(batches) + 1) * image_bytes)
     try:
@@ -411,6 +433,9 @@ def run_batches(ffi, launch, sync, image_bytes, nv12, bw, bh, pitch, batches, wa
             assert (raw[B] == FILL).all(), "%s, batch %d: %d bytes of the guard image behind image %d were written (first at byte %d)" % (
                 what, B, int((raw[B] != FILL).sum()), B - 1, int(np.argmax(raw[B] != FILL)))
             for b in range(B):
+                if plane is not None:
+                    check_plane(plane_of(raw[b], plane, bw, bh, pitch), want_bgr[b], none, "%s, %s" % (what, where(B, b, balance, nb_env)), under)
+                    continue
                 check_image(image_of(raw[b], nv12, bw, bh, pitch), want_bgr[b], none, "%s, %s" % (what, where(B, b, balance, nb_env)),
                             "nv12" if nv12 else "bgr", black, want_nv12=want_nv12[b] if nv12 else None)
     finally:

@@ -14,8 +14,12 @@ IN_UNIT = {("F", "bgr"): 4 * 320 * 256 * 3, ("F", "nv12"): 4 * 320 * 256 * 3 // 
 OUT_UNIT = {"bgr": 248 * 250 * 3, "nv12": 248 * 250 * 3 // 2}
 
 
+# ... and of the one-channel cases: a grey frame set and image of geometry T, a 16-bit frame and image of the far remapper
+PLANE_UNIT = {"gray set": 4 * 64 * 48, "gray image": 248 * 250, "gray16 frame": 64 * 48 * 2, "gray16 image": 248 * 250 * 2}
+
+
 def units():
-    return sorted(set(IN_UNIT.values()) | set(OUT_UNIT.values()) | {64 * 48 * 3})
+    return sorted(set(IN_UNIT.values()) | set(OUT_UNIT.values()) | {64 * 48 * 3} | set(PLANE_UNIT.values()))
 
 
 @pytest.mark.parametrize("boundary", FB.BOUNDARIES)
@@ -45,6 +49,34 @@ def test_the_literals_of_the_two_geometries():
     assert FB.COUNT_BATCH == 65540 > FB.GRID_MAX
 
 
+def test_the_literals_of_the_one_channel_and_moving_cases():
+    assert PLANE_UNIT == {"gray set": 12288, "gray image": 62000, "gray16 frame": 6144, "gray16 image": 124000}
+    assert FB.far_batch(62000) == 69276 > FB.GRID_MAX and [FB.straddler(62000, x) for x in FB.BOUNDARIES] == [34636, 69273]
+    assert FB.far_batch(124000) == 34639 and [FB.straddler(124000, x) for x in FB.BOUNDARIES] == [17318, 34636]
+    assert 69276 * 12288 < 1 << 31 and 34639 * 6144 < 1 << 31, "the inputs of these cases stay below 2^31: the far side is the output"
+    cfg = FB.MOVING_CFG
+    in_unit, out_unit = 4 * cfg["FRAME_WIDTH"] * cfg["FRAME_HEIGHT"] * 3, cfg["BEV_WIDTH"] * cfg["BEV_HEIGHT"] * 3
+    assert (in_unit, out_unit) == (2304, 3072) and FB.MOVING_BATCH == 65540 > FB.GRID_MAX and FB.MOVING_RIGS == FB.POOL == 7
+    assert FB.MOVING_BATCH * in_unit + (FB.MOVING_BATCH + 1) * out_unit + out_unit < 16 << 30, "the child's device allocations"
+    for unit in (in_unit, out_unit):
+        assert all(x % unit for x in FB.BOUNDARIES)
+
+
+@pytest.mark.parametrize("batch,in_unit,out_unit", [(69276, 12288, 62000), (65540, 128, 128), (65540, 64, 64), (FB.MOVING_BATCH, 2304, 3072)],
+                         ids=["T gray", "gray16 count", "nn8 count", "moving"])
+def test_the_sampled_set_contains_the_cut_of_a_grid_of_images(batch, in_unit, out_unit):
+    """images 65534 .. 65536 around the first image of the second span (for_each_chunk cuts at 65535), with the ends and every straddler"""
+    stride = FB.stride_for(batch)
+    why = FB.checked(batch, in_unit, out_unit, stride, range(FB.GRID_MAX - 2, FB.GRID_MAX + 3))
+    assert {FB.GRID_MAX - 1, FB.GRID_MAX, FB.GRID_MAX + 1, 0, 1, batch - 2, batch - 1} <= set(why) and "cut of a grid" in why[FB.GRID_MAX]
+    for unit in (in_unit, out_unit):
+        for boundary in FB.BOUNDARIES:
+            s = FB.straddler(unit, boundary)
+            if s is not None and s + 1 < batch:
+                assert {s - 1, s, s + 1} <= set(why)
+    assert math.gcd(stride, 7) == 1 and math.gcd(stride, 16) == 1 and len(why) <= 2300
+
+
 def test_strides_are_coprime_to_7_and_16():
     for unit in units():
         batch = FB.far_batch(unit)
@@ -54,13 +86,22 @@ def test_strides_are_coprime_to_7_and_16():
 
 def test_case_list():
     cs = FB.cases()
-    assert len({c.name for c in cs}) == len(cs) == 10
+    assert len({c.name for c in cs}) == len(cs) == 17
+    assert [c.name for c in cs[:10]] == ["F bgr->bgr plan direct", "F bgr->bgr plan balance", "F nv12->bgr plan direct", "T bgr->bgr plan direct",
+                                         "T bgr->bgr plan balance", "T bgr->bgr per_pixel direct", "T bgr->bgr per_pixel balance", "T bgr->nv12 plan direct",
+                                         "remap far output", "remap 65540 images"], "the first catalogue is still there, whole"
+    assert {(c.name, c.kind, c.schedule, c.depth, c.nearest, bool(c.env)) for c in cs[10:]} == {
+        ("T gray->gray plan", "stitch_gray", "plan", 8, False, False), ("T gray->gray per_pixel", "stitch_gray", "per_pixel", 8, False, False),
+        ("remap gray16 far output", "plane", None, 16, False, False), ("remap nn16 far output", "plane", None, 16, True, False),
+        ("remap gray16 65540 images", "plane_count", None, 16, False, True), ("remap nn8 65540 images", "plane_count", None, 8, True, True),
+        ("moving 65540 sets", "moving", None, 8, False, False)}
+    assert all(c.env == {"BEVW_REMAP_PLAN": "0"} for c in cs if c.kind == "plane_count")
     got = {(c.geometry, c.inp, c.out, c.schedule, c.mode) for c in cs if c.kind == "stitch"}
     assert got == {("F", "bgr", "bgr", "plan", "direct"), ("F", "bgr", "bgr", "plan", "balance"), ("F", "nv12", "bgr", "plan", "direct"),
                    ("T", "bgr", "bgr", "plan", "direct"), ("T", "bgr", "bgr", "plan", "balance"), ("T", "bgr", "bgr", "per_pixel", "direct"),
                    ("T", "bgr", "bgr", "per_pixel", "balance"), ("T", "bgr", "nv12", "plan", "direct")}
     assert FB.MODES == {"direct": (False, False), "balance": (True, True)} and FB.POOL == 7
-    assert [c.env for c in cs if c.kind == "remap_count"] == [{"BEVW_REMAP_PLAN": "0"}] and all(not c.env for c in cs if c.kind != "remap_count")
+    assert [c.env for c in cs if c.kind == "remap_count"] == [{"BEVW_REMAP_PLAN": "0"}] and all(not c.env for c in cs if c.kind not in ("remap_count", "plane_count"))
     assert FB.GEOMETRIES["F"][1] == "in" and FB.GEOMETRIES["T"][1] == "out"
 
 
