@@ -13,6 +13,7 @@
 // bytes: one dword store per quad slot.
 #pragma once
 #include "bevw_plan.h"
+#include "bevw_mono_unit.h"
 
 namespace bevw {
 
@@ -44,106 +45,47 @@ __host__ __device__ __forceinline__ uint32_t gray_pack(const uint32_t acc[4])
 }
 
 // ---- the unit kernel ------------------------------------------------------------------------------------------------------------------
-// plan_unit_run (bevw_unit.h) for one channel: one block of 4 waves owns a unit for the frames of its batch chunk.  Per frame every lane
-// fetches up to GR group slots -- ONE 8-byte load each at the slot's 4-byte aligned offset (unit_gsrc_gray) through the frame set's
-// range-checked descriptor, as the NV12 unit kernel fetches its Y bytes.  Only the last group of the set's last row would reach a dword
-// past the set (it would read as zero and touch nothing), and the plan never hands that group to a unit: unit_compile drops every base
-// tile whose 16-byte BGR window would overrun the frame set, which is that group's (tests/test_gray_host.py holds it on a map that ends
-// in the frame's last texel).  Texel 4g+4 of a row's last group is never sampled either (its footprint would cross the frame border: a
-// base tile of the per-tap kernel).  A lane without a group is out of the descriptor's range as a whole.  The 8 bytes go to the
-// patch half of their frame as they are.  The groups of the next two frames are in flight in registers; frame b+1 lands in the other
-// half while frame b is interpolated: one barrier per frame for every class (GR x 2 KB per half).
-// Single-contributor classes only (a one-camera plan has no other: plan_make_lists refuses the list otherwise): no blend, no channel
-// sums, no car sprite, no wide fractions.
+// mono_unit_run (bevw_mono_unit.h) has the loop, the frame ring and the end-of-set argument; here is what 1-byte texels give it.
+//
+// The group slots of 1-byte texels, shared with the one-channel stitch (bevw_kernels_gray_stitch.h): the patch, the fetch and the landing --
+// ONE 8-byte load per group slot, landed in the patch half of its frame as fetched
+template <int GR>
+struct GraySlots {
+    static constexpr int kGR = GR, kTexelBytes = 1, kPatch = GR * kUnitThreads * kGraySlotBytes, kMaxPatch = kGrayPatch;
+    typedef pair_u32x2 Fetch;
+    static __device__ __forceinline__ uint32_t group_offset(uint32_t g) { return g; }
+    static __device__ __forceinline__ Fetch fetch(__amdgpu_buffer_rsrc_t rs, int off) { return __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, kPairLoadAux); }
+    static __device__ __forceinline__ void land(uint8_t *half, int idx, Fetch f) { reinterpret_cast<uint2 *>(half)[idx] = make_uint2(f.x, f.y); }
+};
+// The lane of the one-channel remapper, fixed-point bilinear weights: per frame a pixel reads the 8 bytes of its two slots and interpolates
+// (gray_pixel), and a lane's 4 pixels are one dword.  Single-contributor classes only (a one-camera plan has no other: plan_make_lists
+// refuses the list otherwise): no blend, no channel sums, no car sprite, no wide fractions.
 template <int NQ, int GR>
-__device__ __forceinline__ void gray_unit_run(const PlanArgs &a, uint32_t chunk, uint32_t unit, uint8_t *lds)
-{
-    static_assert(NQ >= 1 && NQ <= kUnitMaxNQ && GR >= 1 && GR <= kUnitMaxGR, "unit class");
-    constexpr int kPatch = GR * kUnitThreads * kGraySlotBytes;
-    static_assert(2 * kPatch <= 2 * kGrayPatch, "both halves of the frame ring fit the block's LDS");
-    const uint32_t *dp = reinterpret_cast<const uint32_t *>(a.un_desc + unit);
-    const uint32_t pos = __builtin_amdgcn_readfirstlane(dp[0]), shape = __builtin_amdgcn_readfirstlane(dp[1]);
-    const uint32_t ent_off = __builtin_amdgcn_readfirstlane(dp[2]), gs_off = __builtin_amdgcn_readfirstlane(dp[3]);
-    const uint32_t lq = __builtin_amdgcn_readfirstlane(dp[4]);
-    const uint32_t ngroups = __builtin_amdgcn_readfirstlane(dp[6]);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ux = (int)(int16_t)(pos & 0xffffu), uy = (int)(pos >> 16), uw = (int)(shape & 0xffffu), uh = (int)(shape >> 16);
-    const size_t set_bytes = a.set_stride ? (size_t)a.set_stride : (size_t)a.fw * a.fh * a.ncams, img_bytes = (size_t)a.pitch * a.bh;
-    const bool streaming = (uint32_t)a.pitch % 64u == 0u;   // rows of whole sectors (unit_store_quad's rule)
+struct GrayLane : GraySlots<GR> {
+    static constexpr int kNQ = NQ, kPart = 1;
+    typedef uint32_t Quad;
+    uint32_t a0[NQ][4], a1[NQ][4], pk[NQ][4], wx[NQ][4], wy[NQ][4];
 
-    uint32_t a0[NQ][4], a1[NQ][4], pk[NQ][4], wx[NQ][4], wy[NQ][4], gs[GR], ooff[NQ];
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) {
-        const int sidx = unit_slot(wave, j);
-        int qx, row;
-        unit_quad(lq, sidx, lane, qx, row);
-        const int x = ux + 4 * qx + unit_skew((uint32_t)a.un_skew, uy + row);
-        const uint4 e4 = unit_plan_load(a.un_entries + ((size_t)ent_off + sidx) * 64 + lane);   // the lane's 4 pixels of this slot
+    __device__ __forceinline__ uint32_t load(int j, const uint4 *ent)
+    {
+        const uint4 e4 = unit_plan_load(ent);
         const uint32_t e[4] = {e4.x, e4.y, e4.z, e4.w};
 #pragma unroll
         for (int p = 0; p < 4; ++p) gray_decode(e[p], a0[j][p], a1[j][p], pk[j][p], wx[j][p], wy[j][p]);
-        const bool store = 4 * qx < uw && row < uh && x >= 0 && x < a.pitch && !(unit_no_contributor(e[0]) && (e[0] & kUnitSkip));
-        // out of range of the image's buffer descriptor: not written
-        ooff[j] = store ? (uint32_t)(uy + row) * (uint32_t)a.pitch + (uint32_t)x : kPairNoGroup;
+        return e[0];
     }
-    const int b_begin = (int)chunk * a.nb, b_end = min(a.batch, b_begin + a.nb);
-    auto frame_of = [&](int b) { return min(b, b_end - 1); };   // past the chunk: the last frame once more
-    auto image = [&](int b) { return __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)frame_of(b) * img_bytes, 0, (uint32_t)img_bytes, kBufferWord3); };
-
-    if (ngroups == 0) {
-        // no contributor anywhere (the map leaves the frame): zeros, in whole row runs
-#pragma unroll 1
-        for (int b = b_begin; b < b_end; ++b) {
-            const __amdgpu_buffer_rsrc_t ro = image(b);
+    __device__ __forceinline__ void place(int, bool, int, int) {}
+    __device__ __forceinline__ void ready() {}
+    __device__ __forceinline__ Quad empty(int) const { return 0u; }   // the map leaves the frame: zeros
+    __device__ __forceinline__ Quad quad(int j, const uint8_t *pw) const
+    {
+        uint32_t acc[4];
 #pragma unroll
-            for (int j = 0; j < NQ; ++j) unit_store_dword(0u, ro, (int)ooff[j], streaming);
-        }
-        return;
+        for (int p = 0; p < 4; ++p)
+            acc[p] = gray_pixel(*reinterpret_cast<const uint2 *>(pw + a0[j][p]), *reinterpret_cast<const uint2 *>(pw + a1[j][p]), pk[j][p], wx[j][p], wy[j][p]);
+        return gray_pack(acc);
     }
-#pragma unroll
-    for (int r = 0; r < GR; ++r) gs[r] = once_load<BEVW_PLAN_NT>(a.un_gsrc + ((size_t)gs_off + r) * kUnitThreads + threadIdx.x);
-
-    pair_u32x2 pf[2][GR];
-    auto issue = [&](int b, int ring) {
-        const uint8_t *src = a.frames + (size_t)frame_of(b) * set_bytes;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), 0, (uint32_t)set_bytes, kBufferWord3);
-#pragma unroll
-        for (int r = 0; r < GR; ++r) pf[ring][r] = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)gs[r], 0, kPairLoadAux);
-    };
-    auto land = [&](int ring) {   // the groups of ring slot `ring` -> the patch half of that frame: 8 bytes per group slot, as fetched
-#pragma unroll
-        for (int r = 0; r < GR; ++r)
-            reinterpret_cast<uint2 *>(lds + ring * kPatch)[r * kUnitThreads + (int)threadIdx.x] = make_uint2(pf[ring][r].x, pf[ring][r].y);
-    };
-    auto frame = [&](int b, int ring) {
-        const uint8_t *const pw = lds + ring * kPatch;
-        issue(b + 2, ring);        // the ring slot of frame b has landed
-        uint32_t d[NQ];
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-            uint32_t acc[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-                acc[p] = gray_pixel(*reinterpret_cast<const uint2 *>(pw + a0[j][p]), *reinterpret_cast<const uint2 *>(pw + a1[j][p]), pk[j][p], wx[j][p], wy[j][p]);
-            d[j] = gray_pack(acc);
-        }
-        land(ring ^ 1);            // frame b+1 into the other half: nobody reads it before the barrier
-        const __amdgpu_buffer_rsrc_t ro = image(b);   // past the chunk: re-writes the last frame with the same bytes
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) unit_store_dword(d[j], ro, (int)ooff[j], streaming);
-        block_lds_barrier();       // half[ring ^ 1] complete for everybody, half[ring] free for frame b+2
-    };
-    issue(b_begin, 0);
-    issue(b_begin + 1, 1);
-    land(0);
-    block_lds_barrier();
-#pragma unroll 1
-    for (int b = b_begin; b < b_end; b += 2) {
-        frame(b, 0);
-        frame(b + 1, 1);
-    }
-}
+};
 
 // BEVW_GRAY_SHARED_ONLY (bevwarp_gray_stitch.hip): this header without its kernels -- the lane functions and device functions only.  A
 // non-template kernel is emitted by every unit that sees it.
@@ -157,7 +99,7 @@ __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_
     if (!plan_block_map(a, blockIdx.x, chunk, group)) return;
     if ((int)group >= a.nlist) return;
     const uint32_t e = __builtin_amdgcn_readfirstlane(a.tile_list[group]), unit = e & 0x0fffffffu;
-#define BEVW_GRAY_CASE(C) case C: static_assert(kUnitClassCON[C] == 1, "one contributor per pixel"); gray_unit_run<kUnitClassNQ[C], kUnitClassGR[C]>(a, chunk, unit, patch); break;
+#define BEVW_GRAY_CASE(C) case C: { static_assert(kUnitClassCON[C] == 1, "one contributor per pixel"); GrayLane<kUnitClassNQ[C], kUnitClassGR[C]> ln; mono_unit_run(a, ln, chunk, unit, patch); } break;
     switch (e >> 28) {
         BEVW_GRAY_CASE(0) BEVW_GRAY_CASE(1) BEVW_GRAY_CASE(2) BEVW_GRAY_CASE(3) BEVW_GRAY_CASE(7)
         default: break;   // (two-contributor classes: the host makes no one-channel list for a plan that has such units)
@@ -187,6 +129,8 @@ __device__ __forceinline__ int remap_u8c1_px(const uint8_t *__restrict__ src, in
 // The per-tap tile kernel on one-channel frames: one wave per 32 x 8 base tile of the list (the tiles no unit owns: footprints on the frame
 // border), lane l owns the pixel quad (l % 8, l / 8), every tap read straight from the frame.  k_stitch_plan's block map and entries; an
 // entry without a contributor gives 0.  Rows of a.pitch == a.bw bytes, a.bw % 4 == 0: one dword store per lane.
+// (mono_tiles of bevw_mono_unit.h is this walk for the nearest kernels.  This kernel and k_stitch_plan_gray16 keep their own text: they
+// take the kernel's arguments directly, and already passing them to a shared body by reference changes their machine code.)
 __global__ void __launch_bounds__(256) k_stitch_plan_gray(PlanArgs a)
 {
     uint32_t chunk, group;
@@ -217,20 +161,17 @@ __global__ void __launch_bounds__(256) k_stitch_plan_gray(PlanArgs a)
             d |= (uint32_t)remap_u8c1_px(fb + (size_t)cam * a.fw * a.fh, a.fw, a.fh, sx, sy, e[j].meta & 1023u, 0) << (8 * j);
         }
         const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)b * img_bytes, 0, (uint32_t)img_bytes, kBufferWord3);
-        unit_store_dword(d, ro, (int)((uint32_t)y * (uint32_t)a.pitch + (uint32_t)x0), false);
+        mono_store(d, ro, (int)((uint32_t)y * (uint32_t)a.pitch + (uint32_t)x0), false);
     }
 }
 
-// k_remap_lut on one-channel sources: one thread per destination pixel, both tie rules; grid = (ceil(dw / 256), dh, images)
+// k_remap_lut on one-channel sources (mono_remap), both tie rules
 __global__ void __launch_bounds__(256) k_remap_lut_gray(const uint8_t *__restrict__ src, int sw, int sh, const int16_t *__restrict__ map1,
                                                        const uint16_t *__restrict__ map2, int dw, int dh, uint8_t *__restrict__ dst, int ties_even)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= dw) return;
-    const size_t o = (size_t)y * dw + x;
-    const uint8_t *s = src + (size_t)blockIdx.z * sw * sh;
-    dst[(size_t)blockIdx.z * dw * dh + o] = (uint8_t)remap_u8c1_px(s, sw, sh, map1[o * 2], map1[o * 2 + 1], map2[o] & (kQTab2 - 1), ties_even);
+    mono_remap<uint8_t>(src, sw, sh, map1, map2, dw, dh, dst, [ties_even](const uint8_t *s, int w, int h, int sx, int sy, unsigned code) {
+        return remap_u8c1_px(s, w, h, sx, sy, code, ties_even);
+    });
 }
 #endif   // BEVW_GRAY_SHARED_ONLY
 

@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "bevw_plan.h"
+#include "bevw_mono_unit.h"
 
 namespace bevw {
 
@@ -89,55 +90,33 @@ __host__ __device__ __forceinline__ uint32_t gray16_pixel(uint2 q0, uint2 q1, ui
 __host__ __device__ __forceinline__ uint2 gray16_pack(const uint32_t v[4]) { return make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16)); }
 
 // ---- the unit kernel ------------------------------------------------------------------------------------------------------------------
-// gray_unit_run (bevw_kernels_gray.h) for 2-byte texels: one block of 4 waves owns a unit for the frames of its batch chunk.  Per frame every
-// lane fetches up to GR group slots -- ONE 12-byte load each at the slot's offset 8g (4-byte aligned: frame sets are, and 8g is) through the
+// The lane of mono_unit_run (bevw_mono_unit.h has the loop and the frame ring) for 2-byte texels and float weights.  Per frame every lane
+// fetches up to GR group slots -- ONE 12-byte load each at the slot's offset 8g (4-byte aligned: frame sets are, and 8g is) through the
 // frame set's range-checked descriptor (num_records = the set's bytes).
 // The end of the set.  The 12 bytes of group g are texels 4g .. 4g+5.  Rows are whole groups (fw % 4 == 0), so for every group but a row's
 // last all 12 bytes lie in the group's own row; a row's last group reads 4 bytes of the next row (texels 4g+4, 4g+5: never sampled -- a
 // footprint on texel 4g+4 of a row's last group crosses the frame border, which is a base tile of the per-tap kernel), and only the last
 // group of the set's last row reaches past the set: its third dword starts exactly at the set's end (the set is a multiple of 8 bytes), so it
 // is out of range as a whole, reads as zero and touches nothing -- no dword ever straddles the end.  The plan never hands that group to a
-// unit either: unit_compile drops every base tile whose 16-byte BGR window would overrun the frame set, which is that group's
-// (tests/native/gray16_emulate.cpp checks every byte of every load against the set's size and counts the dwords past it: 0, also on a map
-// that ends in the frame's last texel).  A lane without a group is out of the descriptor's range as a whole.
-// The groups of the next two frames are in flight in registers (2 x GR x 3 dwords); frame b+1 lands in the other half of the ring while
-// frame b is interpolated: one barrier per frame for every class.  The four weights of a pixel stay in registers across the frames as two
-// binary16 pairs (exact: gray16_weights_pack) -- 16 pixels x 3 registers for the four-quad classes.  As four floats (16 x 5) the kernel
-// spilled 57 registers to scratch at the 168 of three waves per SIMD; rebuilding them from fx, fy would cost 8 more vector instructions
-// per pixel and frame against the 4 conversions, in a kernel whose float arithmetic is its longest chain already.
+// unit either (tests/native/gray16_emulate.cpp checks every byte of every load against the set's size and counts the dwords past it: 0,
+// also on a map that ends in the frame's last texel).
+// Registers.  The groups of the next two frames are in flight (2 x GR x 3 dwords).  The four weights of a pixel stay in registers across the
+// frames as two binary16 pairs (exact: gray16_weights_pack) -- 16 pixels x 3 registers for the four-quad classes.  As four floats (16 x 5)
+// the kernel spilled 57 registers to scratch at the 168 of three waves per SIMD; rebuilding them from fx, fy would cost 8 more vector
+// instructions per pixel and frame against the 4 conversions, in a kernel whose float arithmetic is its longest chain already.
 // Single-contributor classes only, as k_units_gray.  A lane's quad is 8 bytes: one dwordx2 store per quad slot.
-__device__ __forceinline__ void gray16_store_quad(uint2 v, __amdgpu_buffer_rsrc_t ro, int off, bool streaming)
-{
-    const pair_u32x2 d = {v.x, v.y};
-    if (streaming) __builtin_amdgcn_raw_buffer_store_b64(d, ro, off, 0, kPairStreamAux);
-    else __builtin_amdgcn_raw_buffer_store_b64(d, ro, off, 0, kPairStoreAux);
-}
-
 template <int NQ, int GR>
-__device__ __forceinline__ void gray16_unit_run(const PlanArgs &a, uint32_t chunk, uint32_t unit, uint8_t *lds)
-{
-    static_assert(NQ >= 1 && NQ <= kUnitMaxNQ && GR >= 1 && GR <= kUnitMaxGR, "unit class");
-    constexpr int kPlane = GR * kUnitThreads * kGray16HalfBytes, kPatch = 2 * kPlane;
-    static_assert(2 * kPatch <= 2 * kGray16Patch && kPatch <= 65536, "both halves of the frame ring fit the block's LDS; 16-bit patch offsets");
-    const uint32_t *dp = reinterpret_cast<const uint32_t *>(a.un_desc + unit);
-    const uint32_t pos = __builtin_amdgcn_readfirstlane(dp[0]), shape = __builtin_amdgcn_readfirstlane(dp[1]);
-    const uint32_t ent_off = __builtin_amdgcn_readfirstlane(dp[2]), gs_off = __builtin_amdgcn_readfirstlane(dp[3]);
-    const uint32_t lq = __builtin_amdgcn_readfirstlane(dp[4]);
-    const uint32_t ngroups = __builtin_amdgcn_readfirstlane(dp[6]);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ux = (int)(int16_t)(pos & 0xffffu), uy = (int)(pos >> 16), uw = (int)(shape & 0xffffu), uh = (int)(shape >> 16);
-    const size_t set_bytes = a.set_stride ? (size_t)a.set_stride : (size_t)a.fw * a.fh * a.ncams * 2, img_bytes = (size_t)a.pitch * a.bh * 2;
-    const bool streaming = ((uint32_t)a.pitch * 2u) % 64u == 0u;   // rows of whole sectors (unit_store_quad's rule on bytes)
+struct Gray16Lane {
+    static constexpr int kNQ = NQ, kGR = GR, kTexelBytes = 2, kPart = 1;
+    static constexpr int kPlane = GR * kUnitThreads * kGray16HalfBytes, kPatch = 2 * kPlane, kMaxPatch = kGray16Patch;
+    static_assert(kPatch <= 65536, "16-bit patch offsets");
+    typedef uint2 Quad;
+    typedef pair_u32x3 Fetch;
+    uint32_t aw[NQ][4], w01[NQ][4], w23[NQ][4];
 
-    uint32_t aw[NQ][4], w01[NQ][4], w23[NQ][4], gs[GR], ooff[NQ];
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) {
-        const int sidx = unit_slot(wave, j);
-        int qx, row;
-        unit_quad(lq, sidx, lane, qx, row);
-        const int x = ux + 4 * qx + unit_skew((uint32_t)a.un_skew, uy + row);
-        const uint4 e4 = unit_plan_load(a.un_entries + ((size_t)ent_off + sidx) * 64 + lane);   // the lane's 4 pixels of this slot
+    __device__ __forceinline__ uint32_t load(int j, const uint4 *ent)
+    {
+        const uint4 e4 = unit_plan_load(ent);
         const uint32_t e[4] = {e4.x, e4.y, e4.z, e4.w};
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
@@ -145,77 +124,35 @@ __device__ __forceinline__ void gray16_unit_run(const PlanArgs &a, uint32_t chun
             gray16_decode(e[p], (uint32_t)kPlane, aw[j][p], w);
             gray16_weights_pack(w, w01[j][p], w23[j][p]);
         }
-        const bool store = 4 * qx < uw && row < uh && x >= 0 && x < a.pitch && !(unit_no_contributor(e[0]) && (e[0] & kUnitSkip));
-        // out of range of the image's buffer descriptor: not written
-        ooff[j] = store ? ((uint32_t)(uy + row) * (uint32_t)a.pitch + (uint32_t)x) * 2u : kPairNoGroup;
+        return e[0];
     }
-    const int b_begin = (int)chunk * a.nb, b_end = min(a.batch, b_begin + a.nb);
-    auto frame_of = [&](int b) { return min(b, b_end - 1); };   // past the chunk: the last frame once more
-    auto image = [&](int b) { return __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)frame_of(b) * img_bytes, 0, (uint32_t)img_bytes, kBufferWord3); };
-
-    if (ngroups == 0) {
-        // no contributor anywhere (the map leaves the frame): zeros, in whole row runs
-#pragma unroll 1
-        for (int b = b_begin; b < b_end; ++b) {
-            const __amdgpu_buffer_rsrc_t ro = image(b);
-#pragma unroll
-            for (int j = 0; j < NQ; ++j) gray16_store_quad(make_uint2(0u, 0u), ro, (int)ooff[j], streaming);
-        }
-        return;
+    __device__ __forceinline__ void place(int, bool, int, int) {}
+    __device__ __forceinline__ void ready() {}
+    __device__ __forceinline__ Quad empty(int) const { return make_uint2(0u, 0u); }   // the map leaves the frame: zeros
+    static __device__ __forceinline__ uint32_t group_offset(uint32_t g) { return gray16_group_offset(g); }
+    static __device__ __forceinline__ Fetch fetch(__amdgpu_buffer_rsrc_t rs, int off) { return __builtin_amdgcn_raw_buffer_load_b96(rs, off, 0, kPairLoadAux); }
+    static __device__ __forceinline__ void land(uint8_t *half, int idx, Fetch f)   // {d0, d1} to plane 0, {d1, d2} to plane 1
+    {
+        uint2 *const q = reinterpret_cast<uint2 *>(half) + idx;
+        q[0] = make_uint2(f.x, f.y);
+        q[kPlane / kGray16HalfBytes] = make_uint2(f.y, f.z);
     }
+    __device__ __forceinline__ Quad quad(int j, const uint8_t *pw)
+    {
+        uint32_t v[4];
 #pragma unroll
-    for (int r = 0; r < GR; ++r) gs[r] = gray16_group_offset(once_load<BEVW_PLAN_NT>(a.un_gsrc + ((size_t)gs_off + r) * kUnitThreads + threadIdx.x));
-
-    pair_u32x3 pf[2][GR];
-    auto issue = [&](int b, int ring) {
-        const uint8_t *src = a.frames + (size_t)frame_of(b) * set_bytes;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), 0, (uint32_t)set_bytes, kBufferWord3);
-#pragma unroll
-        for (int r = 0; r < GR; ++r) pf[ring][r] = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)gs[r], 0, kPairLoadAux);
-    };
-    auto land = [&](int ring) {   // the groups of ring slot `ring` -> the patch half of that frame: {d0, d1} to plane 0, {d1, d2} to plane 1
-#pragma unroll
-        for (int r = 0; r < GR; ++r) {
-            uint2 *const q = reinterpret_cast<uint2 *>(lds + ring * kPatch) + r * kUnitThreads + (int)threadIdx.x;
-            q[0] = make_uint2(pf[ring][r].x, pf[ring][r].y);
-            q[kPlane / kGray16HalfBytes] = make_uint2(pf[ring][r].y, pf[ring][r].z);
+        for (int p = 0; p < 4; ++p) {
+            float w[4];
+            // (the packed pairs are opaque to the optimiser here: it would hoist the conversions out of the frame loop otherwise, and
+            // keep the four floats of every pixel after all -- 57 registers in scratch)
+            asm volatile("" : "+v"(w01[j][p]), "+v"(w23[j][p]));
+            gray16_weights_unpack(w01[j][p], w23[j][p], w);
+            v[p] = gray16_pixel(*reinterpret_cast<const uint2 *>(pw + gray16_addr0(aw[j][p])), *reinterpret_cast<const uint2 *>(pw + gray16_addr1(aw[j][p])),
+                                aw[j][p], w);
         }
-    };
-    auto frame = [&](int b, int ring) {
-        const uint8_t *const pw = lds + ring * kPatch;
-        issue(b + 2, ring);        // the ring slot of frame b has landed
-        uint2 d[NQ];
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-            uint32_t v[4];
-#pragma unroll
-            for (int p = 0; p < 4; ++p) {
-                float w[4];
-                // (the packed pairs are opaque to the optimiser here: it would hoist the conversions out of the frame loop otherwise, and
-                // keep the four floats of every pixel after all -- 57 registers in scratch)
-                asm volatile("" : "+v"(w01[j][p]), "+v"(w23[j][p]));
-                gray16_weights_unpack(w01[j][p], w23[j][p], w);
-                v[p] = gray16_pixel(*reinterpret_cast<const uint2 *>(pw + gray16_addr0(aw[j][p])), *reinterpret_cast<const uint2 *>(pw + gray16_addr1(aw[j][p])),
-                                    aw[j][p], w);
-            }
-            d[j] = gray16_pack(v);
-        }
-        land(ring ^ 1);            // frame b+1 into the other half: nobody reads it before the barrier
-        const __amdgpu_buffer_rsrc_t ro = image(b);   // past the chunk: re-writes the last frame with the same bytes
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) gray16_store_quad(d[j], ro, (int)ooff[j], streaming);
-        block_lds_barrier();       // half[ring ^ 1] complete for everybody, half[ring] free for frame b+2
-    };
-    issue(b_begin, 0);
-    issue(b_begin + 1, 1);
-    land(0);
-    block_lds_barrier();
-#pragma unroll 1
-    for (int b = b_begin; b < b_end; b += 2) {
-        frame(b, 0);
-        frame(b + 1, 1);
+        return gray16_pack(v);
     }
-}
+};
 
 // every unit of every class in the partition's own order, one launch per step: k_units_gray's block map and class switch
 __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_eu(BEVW_PLAN_ALL_WAVES, BEVW_PLAN_ALL_WAVES))) k_units_gray16(PlanArgs a)
@@ -225,7 +162,7 @@ __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_
     if (!plan_block_map(a, blockIdx.x, chunk, group)) return;
     if ((int)group >= a.nlist) return;
     const uint32_t e = __builtin_amdgcn_readfirstlane(a.tile_list[group]), unit = e & 0x0fffffffu;
-#define BEVW_GRAY16_CASE(C) case C: static_assert(kUnitClassCON[C] == 1, "one contributor per pixel"); gray16_unit_run<kUnitClassNQ[C], kUnitClassGR[C]>(a, chunk, unit, patch); break;
+#define BEVW_GRAY16_CASE(C) case C: { static_assert(kUnitClassCON[C] == 1, "one contributor per pixel"); Gray16Lane<kUnitClassNQ[C], kUnitClassGR[C]> ln; mono_unit_run(a, ln, chunk, unit, patch); } break;
     switch (e >> 28) {
         BEVW_GRAY16_CASE(0) BEVW_GRAY16_CASE(1) BEVW_GRAY16_CASE(2) BEVW_GRAY16_CASE(3) BEVW_GRAY16_CASE(7)
         default: break;   // (two-contributor classes: the host makes no one-channel list for a plan that has such units)
@@ -245,7 +182,7 @@ __device__ __forceinline__ uint32_t remap_u16c1_px(const uint16_t *__restrict__ 
 
 // The per-tap tile kernel on 16-bit one-channel frames: k_stitch_plan_gray's block map, entries and lane layout (one wave per 32 x 8 base
 // tile of the list, lane l owns the pixel quad (l % 8, l / 8)), every tap read straight from the frame.  Rows of a.pitch == a.bw pixels,
-// a.bw % 4 == 0, a.out 4-byte aligned: one dwordx2 store per lane.
+// a.bw % 4 == 0, a.out 4-byte aligned: one dwordx2 store per lane.  (Its own text, as k_stitch_plan_gray's and for the same reason.)
 __global__ void __launch_bounds__(256) k_stitch_plan_gray16(PlanArgs a)
 {
     uint32_t chunk, group;
@@ -276,21 +213,16 @@ __global__ void __launch_bounds__(256) k_stitch_plan_gray16(PlanArgs a)
             v[j] = remap_u16c1_px(fb + (size_t)cam * a.fw * a.fh, a.fw, a.fh, sx, sy, e[j].meta & 1023u);
         }
         const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)b * img_bytes, 0, (uint32_t)img_bytes, kBufferWord3);
-        gray16_store_quad(gray16_pack(v), ro, (int)(((uint32_t)y * (uint32_t)a.pitch + (uint32_t)x0) * 2u), false);
+        mono_store(gray16_pack(v), ro, (int)(((uint32_t)y * (uint32_t)a.pitch + (uint32_t)x0) * 2u), false);
     }
 }
 
-// k_remap_lut on 16-bit one-channel sources: one thread per destination pixel; grid = (ceil(dw / 256), dh, images).  `src` and `dst` are
-// 2-byte aligned and nothing more
+// k_remap_lut on 16-bit one-channel sources (mono_remap).  `src` and `dst` are 2-byte aligned and nothing more
 __global__ void __launch_bounds__(256) k_remap_lut_gray16(const uint16_t *__restrict__ src, int sw, int sh, const int16_t *__restrict__ map1,
                                                          const uint16_t *__restrict__ map2, int dw, int dh, uint16_t *__restrict__ dst)
 {
-    const int x = blockIdx.x * blockDim.x + threadIdx.x;
-    const int y = blockIdx.y;
-    if (x >= dw) return;
-    const size_t o = (size_t)y * dw + x;
-    const uint16_t *s = src + (size_t)blockIdx.z * sw * sh;
-    dst[(size_t)blockIdx.z * dw * dh + o] = (uint16_t)remap_u16c1_px(s, sw, sh, map1[o * 2], map1[o * 2 + 1], map2[o] & (kQTab2 - 1));
+    mono_remap<uint16_t>(src, sw, sh, map1, map2, dw, dh, dst,
+                         [](const uint16_t *s, int w, int h, int sx, int sy, unsigned code) { return remap_u16c1_px(s, w, h, sx, sy, code); });
 }
 
 }  // namespace bevw

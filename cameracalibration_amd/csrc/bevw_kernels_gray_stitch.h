@@ -49,51 +49,37 @@ __host__ __device__ __forceinline__ uint32_t gray_stitch_quad(const uint32_t acc
 }
 
 // ---- the unit kernel ------------------------------------------------------------------------------------------------------------------
-// plan_unit_run (bevw_unit.h) on one channel, every class: one block of 4 waves owns a unit for the frames of its batch chunk.  The fetch,
-// the landing and the frame ring are gray_unit_run's (bevw_kernels_gray.h): ONE 8-byte load per group slot through the frame set's
-// range-checked descriptor (4 * FW * FH bytes; the plan hands no unit the one group whose load would reach past it, and a lane without a
-// group is out of range as a whole), landed as fetched; both halves of the ring fit for every class, two-contributor ones included
-// (GR <= 4: 8 KB per half), so there is one barrier per frame.
+// The lane of mono_unit_run (bevw_mono_unit.h has the loop and the frame ring) for every class of the stitch.  The fetch and the landing
+// are GrayLane's (bevw_kernels_gray.h): ONE 8-byte load per group slot through the frame set's range-checked descriptor (4 * FW * FH bytes;
+// the plan hands no unit the one group whose load would reach past it), landed as fetched; both halves of the ring fit for every class,
+// two-contributor ones included (GR <= 4: 8 KB per half).
 // NCON == 2 (classes 4, 5, 6): the plan holds three uint4 per lane and quad slot -- the entries of contributor 0, of contributor 1, and the
 // two u8 blend weights of every pixel (w0 | w1 << 8) -- read as plan_unit_run reads them.
 // The car sprite: a quad's four bytes are one dword through a range-checked descriptor of its own (num_records 0 without a sprite: zeros, no
 // memory touched), read ONCE per unit before the frame loop, kept in one register per quad slot and added with saturation per byte; a wave
 // whose quads see only zeros skips the add.  A unit without groups (under the car) stores the sprite or zeros in whole row runs.
 template <bool BLEND, int NQ, int GR, int NCON>
-__device__ __forceinline__ void gray_stitch_unit_run(const GrayStitchArgs &g, uint32_t chunk, uint32_t unit, uint8_t *lds)
-{
-    static_assert(NQ >= 1 && NQ <= kUnitMaxNQ && GR >= 1 && GR <= kUnitMaxGR && (NCON == 1 || NCON == 2), "unit class");
-    const PlanArgs &a = g.p;
-    constexpr int kFPart = NCON == 2 ? 3 : 1;          // uint4 per lane and quad slot in the plan (plan_unit_run's narrow part)
-    constexpr bool kWeights = BLEND && NCON == 2;
-    constexpr int kPatch = GR * kUnitThreads * kGraySlotBytes;
-    static_assert(2 * kPatch <= 2 * kGrayPatch, "both halves of the frame ring fit the block's LDS");
-    const uint32_t *dp = reinterpret_cast<const uint32_t *>(a.un_desc + unit);
-    const uint32_t pos = __builtin_amdgcn_readfirstlane(dp[0]), shape = __builtin_amdgcn_readfirstlane(dp[1]);
-    const uint32_t ent_off = __builtin_amdgcn_readfirstlane(dp[2]), gs_off = __builtin_amdgcn_readfirstlane(dp[3]);
-    const uint32_t lq = __builtin_amdgcn_readfirstlane(dp[4]);
-    const uint32_t ngroups = __builtin_amdgcn_readfirstlane(dp[6]);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ux = (int)(int16_t)(pos & 0xffffu), uy = (int)(pos >> 16), uw = (int)(shape & 0xffffu), uh = (int)(shape >> 16);
-    const size_t set_bytes = a.set_stride ? (size_t)a.set_stride : (size_t)a.fw * a.fh * a.ncams, img_bytes = (size_t)a.pitch * a.bh;
-    const bool streaming = (uint32_t)a.pitch % 64u == 0u;   // rows of whole sectors (unit_store_quad's rule)
-    const bool with_car = a.car != nullptr;
-    const __amdgpu_buffer_rsrc_t rcar = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(with_car ? a.car : a.out), 0,
-                                                                          with_car ? (uint32_t)g.car_pitch * (uint32_t)a.bh : 0u, kBufferWord3);
-
-    uint32_t a0[NQ][NCON][4], a1[NQ][NCON][4], pk[NQ][NCON][4], wx[NQ][NCON][4], wy[NQ][NCON][4], wq[NQ][NCON][4], gs[GR], ooff[NQ], car[NQ];
+struct GrayStitchLane : GraySlots<GR> {
+    static_assert(NCON == 1 || NCON == 2, "unit class");
+    static constexpr int kNQ = NQ, kPart = NCON == 2 ? 3 : 1;   // (plan_unit_run's narrow part)
+    static constexpr bool kWeights = BLEND && NCON == 2;
+    typedef uint32_t Quad;
+    const int car_pitch;                  // bytes per row of the sprite
+    const __amdgpu_buffer_rsrc_t rcar;    // the sprite; num_records 0 without one
+    uint32_t a0[NQ][NCON][4], a1[NQ][NCON][4], pk[NQ][NCON][4], wx[NQ][NCON][4], wy[NQ][NCON][4], wq[NQ][NCON][4], car[NQ];
     uint32_t car_or = 0;
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) {
-        const int sidx = unit_slot(wave, j);
-        int qx, row;
-        unit_quad(lq, sidx, lane, qx, row);
-        const int x = ux + 4 * qx + unit_skew((uint32_t)a.un_skew, uy + row);
+    bool car_any = false;
+
+    __device__ __forceinline__ GrayStitchLane(const PlanArgs &a, int pitch)
+        : car_pitch(pitch), rcar(__builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(a.car != nullptr ? a.car : a.out), 0,
+                                                                   a.car != nullptr ? (uint32_t)pitch * (uint32_t)a.bh : 0u, kBufferWord3)) {}
+
+    __device__ __forceinline__ uint32_t load(int j, const uint4 *ent)
+    {
         uint32_t e0 = 0;
 #pragma unroll
         for (int con = 0; con < NCON; ++con) {
-            const uint4 e4 = unit_plan_load(a.un_entries + ((size_t)ent_off + sidx * kFPart + con) * 64 + lane);   // the lane's 4 pixels of this slot
+            const uint4 e4 = unit_plan_load(ent + con * 64);
             const uint32_t e[4] = {e4.x, e4.y, e4.z, e4.w};
             if (con == 0) e0 = e[0];
 #pragma unroll
@@ -103,79 +89,42 @@ __device__ __forceinline__ void gray_stitch_unit_run(const GrayStitchArgs &g, ui
             }
         }
         if (kWeights) {
-            const uint4 w4 = unit_plan_load(a.un_entries + ((size_t)ent_off + sidx * kFPart + 2) * 64 + lane);
+            const uint4 w4 = unit_plan_load(ent + 2 * 64);
             const uint32_t w[4] = {w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
             for (int p = 0; p < 4; ++p) { wq[j][0][p] = blend_weight_q23(w[p] & 255u); wq[j][NCON - 1][p] = blend_weight_q23((w[p] >> 8) & 255u); }
         }
-        const bool store = 4 * qx < uw && row < uh && x >= 0 && x < a.pitch && !(unit_no_contributor(e0) && (e0 & kUnitSkip));
-        // out of range of the image's (the sprite's) buffer descriptor: not written (not read)
-        ooff[j] = store ? (uint32_t)(uy + row) * (uint32_t)a.pitch + (uint32_t)x : kPairNoGroup;
-        const uint32_t coff = (store && x < g.car_pitch) ? (uint32_t)(uy + row) * (uint32_t)g.car_pitch + (uint32_t)x : kPairNoGroup;
+        return e0;
+    }
+    // the sprite's dword under the quad; out of range of the sprite's buffer descriptor: not read
+    __device__ __forceinline__ void place(int j, bool store, int x, int y)
+    {
+        const uint32_t coff = (store && x < car_pitch) ? (uint32_t)y * (uint32_t)car_pitch + (uint32_t)x : kPairNoGroup;
         car[j] = __builtin_amdgcn_raw_buffer_load_b32(rcar, (int)coff, 0, 0);
         car_or |= car[j];
     }
-    const bool car_any = __builtin_amdgcn_ballot_w64(car_or != 0) != 0;
-    const int b_begin = (int)chunk * a.nb, b_end = min(a.batch, b_begin + a.nb);
-    auto frame_of = [&](int b) { return min(b, b_end - 1); };   // past the chunk: the last frame once more
-    auto image = [&](int b) { return __builtin_amdgcn_make_buffer_rsrc(a.out + (size_t)frame_of(b) * img_bytes, 0, (uint32_t)img_bytes, kBufferWord3); };
-
-    if (ngroups == 0) {
-        // no contributor anywhere (under the car): every frame of the chunk gets the sprite or zeros, in whole row runs
-#pragma unroll 1
-        for (int b = b_begin; b < b_end; ++b) {
-            const __amdgpu_buffer_rsrc_t ro = image(b);
+    __device__ __forceinline__ void ready() { car_any = __builtin_amdgcn_ballot_w64(car_or != 0) != 0; }
+    __device__ __forceinline__ Quad empty(int j) const { return car[j]; }   // under the car: the sprite or zeros
+    __device__ __forceinline__ Quad quad(int j, const uint8_t *pw) const
+    {
+        uint32_t acc[NCON][4];
 #pragma unroll
-            for (int j = 0; j < NQ; ++j) unit_store_dword(car[j], ro, (int)ooff[j], streaming);
-        }
-        return;
+        for (int con = 0; con < NCON; ++con)
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                acc[con][p] = gray_pixel(*reinterpret_cast<const uint2 *>(pw + a0[j][con][p]), *reinterpret_cast<const uint2 *>(pw + a1[j][con][p]),
+                                         pk[j][con][p], wx[j][con][p], wy[j][con][p]);
+        const uint32_t d = gray_stitch_quad<BLEND, NCON>(acc, wq[j]);
+        return car_any ? gray_add_sat4(d, car[j]) : d;   // uniform over the wave
     }
-#pragma unroll
-    for (int r = 0; r < GR; ++r) gs[r] = once_load<BEVW_PLAN_NT>(a.un_gsrc + ((size_t)gs_off + r) * kUnitThreads + threadIdx.x);
+};
 
-    pair_u32x2 pf[2][GR];
-    auto issue = [&](int b, int ring) {
-        const uint8_t *src = a.frames + (size_t)frame_of(b) * set_bytes;
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(src), 0, (uint32_t)set_bytes, kBufferWord3);
-#pragma unroll
-        for (int r = 0; r < GR; ++r) pf[ring][r] = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)gs[r], 0, kPairLoadAux);
-    };
-    auto land = [&](int ring) {   // the groups of ring slot `ring` -> the patch half of that frame: 8 bytes per group slot, as fetched
-#pragma unroll
-        for (int r = 0; r < GR; ++r)
-            reinterpret_cast<uint2 *>(lds + ring * kPatch)[r * kUnitThreads + (int)threadIdx.x] = make_uint2(pf[ring][r].x, pf[ring][r].y);
-    };
-    auto frame = [&](int b, int ring) {
-        const uint8_t *const pw = lds + ring * kPatch;
-        issue(b + 2, ring);        // the ring slot of frame b has landed
-        uint32_t d[NQ];
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-            uint32_t acc[NCON][4];
-#pragma unroll
-            for (int con = 0; con < NCON; ++con)
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-                    acc[con][p] = gray_pixel(*reinterpret_cast<const uint2 *>(pw + a0[j][con][p]), *reinterpret_cast<const uint2 *>(pw + a1[j][con][p]),
-                                             pk[j][con][p], wx[j][con][p], wy[j][con][p]);
-            d[j] = gray_stitch_quad<BLEND, NCON>(acc, wq[j]);
-            if (car_any) d[j] = gray_add_sat4(d[j], car[j]);   // uniform over the wave
-        }
-        land(ring ^ 1);            // frame b+1 into the other half: nobody reads it before the barrier
-        const __amdgpu_buffer_rsrc_t ro = image(b);   // past the chunk: re-writes the last frame with the same bytes
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) unit_store_dword(d[j], ro, (int)ooff[j], streaming);
-        block_lds_barrier();       // half[ring ^ 1] complete for everybody, half[ring] free for frame b+2
-    };
-    issue(b_begin, 0);
-    issue(b_begin + 1, 1);
-    land(0);
-    block_lds_barrier();
-#pragma unroll 1
-    for (int b = b_begin; b < b_end; b += 2) {
-        frame(b, 0);
-        frame(b + 1, 1);
-    }
+// a unit of class C through the shared loop
+template <bool BLEND, int C>
+__device__ __forceinline__ void gray_stitch_class(const GrayStitchArgs &g, uint32_t chunk, uint32_t unit, uint8_t *lds)
+{
+    GrayStitchLane<BLEND, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C]> ln(g.p, g.car_pitch);
+    mono_unit_run(g.p, ln, chunk, unit, lds);
 }
 
 // every unit of every class in the partition's own order, one launch per step: plan_unit_any's block map and class switch
@@ -187,11 +136,11 @@ __global__ void __launch_bounds__(kUnitThreads) __attribute__((amdgpu_waves_per_
     if (!plan_block_map(g.p, blockIdx.x, chunk, group)) return;
     if ((int)group >= g.p.nlist) return;
     const uint32_t e = __builtin_amdgcn_readfirstlane(g.p.tile_list[group]), unit = e & 0x0fffffffu;
-#define BEVW_GRAY_STITCH_CASE(C) case C: gray_stitch_unit_run<BLEND, kUnitClassNQ[C], kUnitClassGR[C], kUnitClassCON[C]>(g, chunk, unit, patch); break;
+#define BEVW_GRAY_STITCH_CASE(C) case C: gray_stitch_class<BLEND, C>(g, chunk, unit, patch); break;
     switch (e >> 28) {
         BEVW_GRAY_STITCH_CASE(0) BEVW_GRAY_STITCH_CASE(1) BEVW_GRAY_STITCH_CASE(2) BEVW_GRAY_STITCH_CASE(3)
         BEVW_GRAY_STITCH_CASE(4) BEVW_GRAY_STITCH_CASE(5) BEVW_GRAY_STITCH_CASE(7)
-        default: gray_stitch_unit_run<BLEND, kUnitClassNQ[6], kUnitClassGR[6], kUnitClassCON[6]>(g, chunk, unit, patch); break;
+        default: gray_stitch_class<BLEND, 6>(g, chunk, unit, patch); break;
     }
 #undef BEVW_GRAY_STITCH_CASE
 }

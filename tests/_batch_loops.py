@@ -2,7 +2,7 @@
 worker tests/_batch_loops_worker.py and the host leg tests/test_batch_loops_host.py): the cases, their pools and yardsticks, and the runners
 over tests/_harness.run_batches.  Imported as `tests._batch_loops`; the library is loaded inside the functions that need it.
 
-k_units_gray, k_units_gray16, k_units_nn8 / k_units_nn16 and k_stitch_units_gray each carry a copy of plan_unit_run's frame loop (b_begin /
+k_units_gray, k_units_gray16, k_units_nn8 / k_units_nn16 and k_stitch_units_gray all run mono_unit_run (csrc/bevw_mono_unit.h), the one-channel form of plan_unit_run's frame loop (b_begin /
 b_end, frame_of, issue(b + 2), land(ring ^ 1), two frames per step); k_units_yuv422 is a new instantiation of the shared one, and
 k_stitch_moving has a loop and a chunk rule (moving_nb) of its own.  tests/test_batch_chunks_gpu.py says what such a loop gets wrong and how
 the batch sizes of H.BATCHES were chosen; plan_args is shared, so the table H.PLAIN applies to every unit kernel here unchanged.

@@ -1,5 +1,5 @@
 """The batch loop of the kernels that came after tests/test_batch_chunks_gpu.py, on the GPU: k_units_gray, k_units_gray16, k_units_nn8 /
-k_units_nn16 and k_stitch_units_gray (each a hand-written copy of plan_unit_run's frame loop) with their per-tap kernels, k_units_yuv422 /
+k_units_nn16 and k_stitch_units_gray (mono_unit_run, the one-channel form of plan_unit_run's frame loop) with their per-tap kernels, k_units_yuv422 /
 k_units_out_yuv422 (the shared loop, instantiated with 16-byte group loads) and k_stitch_moving (a loop and a chunk rule of its own).
 
 tests/_batch_loops.py has the cases, pools and yardsticks; tests/test_batch_chunks_gpu.py says what a wrong frame_of() clamp does and why

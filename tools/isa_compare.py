@@ -3,12 +3,14 @@
 
     python tools/isa_compare.py <object dir A> <object dir B>      (e.g. csrc/build of two checkouts, or csrc/build and csrc/build_<tag>)
 
-For every translation unit (cameracalibration_amd/build.py: ALL_UNITS) the gfx950 code object is taken out of <dir>/<unit>.o and
-disassembled; the text is cut at the function symbols, addresses are dropped and every <symbol> operand becomes a placeholder, so a
-function's stream does not depend on its (mangled) name or on where it lies.  Printed per unit: the number of kernels on each side, whether
-the multisets of stream hashes are equal, the demangled names on either side whose stream has no partner, and whether the multisets of the
-kernels' (VGPRs, SGPRs, LDS bytes, scratch bytes, kernarg bytes) of the code-object notes are equal.  Exit status 1 unless everything is
-equal.  It compares two builds and nothing else: for a refactor that must not change what the compiler emits.
+For every translation unit that is compiled and linked (cameracalibration_amd/build.py: LINKED) the gfx950 code object is taken out of
+<dir>/<unit>.o and disassembled; the text is cut at the function symbols, addresses are dropped and every <symbol> operand becomes a
+placeholder, so a function's stream does not depend on its (mangled) name or on where it lies.  Printed per unit: the number of kernels on
+each side, whether the multisets of stream hashes are equal, and whether the multisets of the kernels' (VGPRs, SGPRs, LDS bytes, scratch
+bytes, kernarg bytes) of the code-object notes are equal.  For every function both sides hold under one symbol with different streams: both
+instruction counts, every opcode whose count differs (A|B) and, for a kernel, its resources on either side; for every other stream without
+a partner, the demangled name.  Exit status 1 unless everything is equal.  It compares two builds and nothing else: for a refactor that
+must not change what the compiler emits, or that has to say exactly where it does.
 """
 import collections
 import hashlib
@@ -21,7 +23,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from cameracalibration_amd.build import ALL_UNITS  # noqa: E402
+from cameracalibration_amd.build import LINKED  # noqa: E402
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 LLVM_BIN = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))), "llvm", "bin")
@@ -42,17 +44,18 @@ def code_object(obj, tmp, tag):
 
 
 def streams(co):
-    """{function symbol: sha256 of its instructions and their encodings}, names and addresses removed."""
+    """{function symbol: (sha256 of its instructions and their encodings, names and addresses removed; Counter of its opcodes)}"""
     out, cur = {}, None
     for line in tool("llvm-objdump", "-d", "--no-show-raw-insn", co).splitlines():
         m = re.match(r"^[0-9a-f]+ <(\S+)>:$", line)
         if m:
-            cur = out.setdefault(m.group(1), hashlib.sha256())
+            cur = out.setdefault(m.group(1), (hashlib.sha256(), collections.Counter()))
             continue
         line = re.sub(r"<[^<>]+>", "<sym>", re.sub(r"//\s*[0-9A-Fa-f]+:", "//", line)).strip()   # (the comment: address, then encoding)
         if cur is not None and line:
-            cur.update(" ".join(line.split()).encode() + b"\n")
-    return {k: v.hexdigest() for k, v in out.items()}
+            cur[0].update(" ".join(line.split()).encode() + b"\n")
+            cur[1][line.split()[0]] += 1
+    return {k: (h.hexdigest(), ops) for k, (h, ops) in out.items()}
 
 
 def resources(co):
@@ -75,7 +78,7 @@ def demangle(names):
 def main(dir_a, dir_b):
     same = True
     with tempfile.TemporaryDirectory() as tmp:
-        for unit in ALL_UNITS:
+        for unit in LINKED:
             obj = unit.replace(".hip", ".o")
             cos = [code_object(os.path.join(d, obj), tmp, t) for d, t in ((dir_a, "a"), (dir_b, "b"))]
             st, rs = [streams(c) for c in cos], [resources(c) for c in cos]
@@ -83,23 +86,33 @@ def main(dir_a, dir_b):
             other = [{k: v for k, v in s.items() if k not in r} for s, r in zip(st, rs)]
             for s, r in zip(st, rs):
                 assert r and set(r) <= set(s), "a kernel of the notes has no code: " + ", ".join(sorted(set(r) - set(s))[:3])
-            ha, hb = (collections.Counter(s.values()) for s in st)
+            ha, hb = (collections.Counter(h for h, _ in s.values()) for s in st)
             streams_equal = ha == hb
             res_equal = collections.Counter(rs[0].values()) == collections.Counter(rs[1].values())
             print("%-16s kernels %3d | %3d   other functions %d | %d   streams %s   resources (vgpr, sgpr, lds, scratch, kernarg) %s" % (
                 unit.replace(".hip", ""), len(kern[0]), len(kern[1]), len(other[0]), len(other[1]),
                 "EQUAL" if streams_equal else "DIFFER", "EQUAL" if res_equal else "DIFFER"))
+            # a function of the same symbol on both sides whose stream differs: both instruction counts, the opcodes whose counts differ, and
+            # for a kernel its resources on either side
+            changed = sorted(k for k in set(st[0]) & set(st[1]) if st[0][k][0] != st[1][k][0] and (ha - hb)[st[0][k][0]] > 0)
+            for name, d in zip(changed, demangle(changed)):
+                oa, ob = st[0][name][1], st[1][name][1]
+                print("    differs: %s\n        instructions %d | %d   %s" % (d, sum(oa.values()), sum(ob.values()), "  ".join(
+                    "%s %d|%d" % (op, oa[op], ob[op]) for op in sorted(set(oa) | set(ob)) if oa[op] != ob[op]) or "(the same opcode counts)"))
+                if name in rs[0] and name in rs[1]:
+                    print("        resources %s | %s" % (rs[0][name], rs[1][name]))
             for side, mine, theirs in (("A", st[0], hb), ("B", st[1], ha)):   # one name per copy of a stream the other side lacks
-                lack = collections.Counter(mine.values()) - theirs
+                lack = collections.Counter(h for h, _ in mine.values()) - theirs
                 lone = []
-                for name, h in sorted(mine.items()):
+                for name, (h, _) in sorted(mine.items()):
                     if lack[h] > 0:
                         lack[h] -= 1
-                        lone.append(name)
+                        if name not in changed:
+                            lone.append(name)
                 for d in demangle(lone):
                     print("    only in %s: %s" % (side, d))
             same = same and streams_equal and res_equal and len(kern[0]) == len(kern[1])
-    print("identical machine code in all %d units" % len(ALL_UNITS) if same else "THE BUILDS DIFFER")
+    print("identical machine code in all %d units" % len(LINKED) if same else "THE BUILDS DIFFER")
     return 0 if same else 1
 
 

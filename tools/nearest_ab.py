@@ -8,7 +8,8 @@ At the geometry of workloads.CONFIG_UNDISTORT and batches 64 and 256, on device-
   (a) nn<depth>_units       the nearest step of this build on `--unique` seeded label frames (replicated over the batch);
   (b) nn<depth>_per_pixel   the same remapper with the destination 2 bytes off a 4-byte boundary: the per-pixel kernel;
   (c) lin<depth>_parent     the linear one-channel step of `--parent-lib` at that depth on random texels: the bar's reference;
-  (d) lin<depth>            the linear step of this build (the same machine code: what loading it from another file costs, if anything).
+  (d) lin<depth>            the linear step of this build beside (c): the A/B of k_units_gray / k_units_gray16 wherever the two builds' code differs;
+  (e) nn<depth>_parent      where `--parent-lib` has the nearest mode: its nearest step on (a)'s frames, beside (a).
 Before any timing (a)'s and (b)'s first image is compared with the NumPy statement of cv2's rule and the path of every remapper is read
 (bevw_remapper_last_path).  After a warm-up of every shape the variants alternate (order reversed every round) over `--rounds` rounds of
 `--steps` steps; a round of one variant is bracketed by the remapper's event timer, and the median over the rounds of the ms per step is
@@ -132,7 +133,6 @@ def main():
     a = p.parse_args()
     _ffi.require_device()
     L, P = _ffi.lib(), load(a.parent_lib)
-    assert not hasattr(P, "bevw_remapper_set_interpolation"), "--parent-lib has the nearest entry points: not the parent commit's library"
     c = W.CONFIG_UNDISTORT
     fw, fh = c["FRAME_WIDTH"], c["FRAME_HEIGHT"]
     rng = np.random.default_rng(a.seed)
@@ -145,6 +145,8 @@ def main():
             nn, pp, par, lin = "nn%d_units" % d, "nn%d_per_pixel" % d, "lin%d_parent" % d, "lin%d" % d
             runs = {nn: Step(L, d, True, labels[d], batch), pp: Step(L, d, True, labels[d], batch, dst_shift=2),
                     par: Step(P, d, False, noise[d], batch), lin: Step(L, d, False, noise[d], batch)}
+            if hasattr(P, "bevw_remapper_set_interpolation"):
+                runs["nn%d_parent" % d] = Step(P, d, True, labels[d], batch)
             for run in runs.values():
                 for _ in range(a.warmup):
                     run.step()
